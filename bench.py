@@ -11,9 +11,15 @@ timed region.  `python bench.py --gpus N` by itself (no WORLD_SIZE in the enviro
 N ranks -- `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process,
 before anything in this process touches the GPU -- and forwards the child's line; launched by
 torch.distributed.run it is one of the ranks.  The N > 1 line carries `rccl_ranks` /
-`dist_backend` from the initialised process group, and every line carries a `train` block: the
-SEQTrainer step of BASELINE configs[3] (64 clips x 4 frames per GPU, GradSync over RCCL) -- the
-series in which the ranks actually exchange data.
+`dist_backend` from the initialised process group.
+
+A plain run sets up, warms up, times `--steps` steps and prints the headline line (`value`,
+`ms_per_step`, ...).  `--full` also measures everything else, after the timed steps: the eval
+roofline and per-stage table, a `train` block (the SEQTrainer step of BASELINE configs[3], 64 clips x
+4 frames per GPU, GradSync over RCCL -- the series in which the ranks actually exchange data), the
+other precisions, host-resident inputs, the secondary series and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32), from
+seeded inputs, so that two builds can be compared output for output.
 
 Prints ONE JSON line (rank 0).
 """
@@ -264,6 +270,35 @@ def eval_kernel_timing(cnn, siam, clips, math):
             "stages (one stream; mfma_util = algorithmic FLOPs / stage wall time / MFMA peak, hbm_gbs = algorithmic bytes / stage wall time)": stages}
 
 
+def eval_roofline(cnn, siam, clips, math):
+    """`roofline` object of the headline eval series (--full): the dominant kernels timed live (gemm_roofline, its own
+    passes after the timed region) against the dense MFMA peak of the datapath, and the per-stage table."""
+    stages = {}
+    flops, gemm_ms, launches = gemm_roofline(cnn, siam, clips, stages=stages)
+    achieved = flops / (gemm_ms * 1e-3) / 1e12
+    # dense MFMA peak of the datapath (MI355X_MICROARCH.md): fp32 157.3, bf16 2500; bf16x3
+    # issues three bf16 MFMAs per product, so its fp32-equivalent peak is 2500/3
+    peak = {'f32': PEAK_FP32_MFMA_TFLOPS, 'bf16': 2500.0, 'bf16s': 2500.0, 'bf16x3': 2500.0 / 3}[math]
+    # counter traffic of the SAME kernels (GEMM + fused-tail launches of one step): only from a profile of this build
+    pmc_series = {(32, 4, 'f32'): 'eval_f32', (64, 8, 'bf16s'): 'eval_c3_bf16s'}.get((B, T, math))
+    prec, pwhy = pmc_record(pmc_series) if pmc_series else (None, 'no profiled series for this configuration')
+    traffic = prec['dominant']['hbm_bytes_per_step'] if prec else None
+    alg_bytes = sum(v["algorithmic_gb"] for v in stages.values()) * 1e9
+    return {"bound": "mfma" if flops / (peak * 1e12) >= (traffic or alg_bytes) / (PEAK_HBM_GBS * 1e9) else "hbm",
+            "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+            "frac": round(achieved / peak, 4), "traffic": traffic,
+            "traffic_note": ("profiles/%s_pmc_%s.json, taken on THIS build (fingerprint checked): rocprofv3 FETCH_SIZE x2 + "
+                             "WRITE_SIZE, separate passes, summed over the same kernels' launches of ONE step "
+                             "like the GFLOP figure; %.2f x their algorithmic bytes; MFMA busy %s" % (
+                                 PMC_ROUND, pmc_series, traffic / alg_bytes, prec['dominant'].get('mfma_busy_frac')))
+            if prec else "null: %s" % pwhy,
+            "algorithmic_gb_per_step": round(alg_bytes / 1e9, 2),
+            "kernel": "gemm_f32_kernel + fused bottleneck tails (%s MFMA implicit-GEMM conv), %d launches/step, "
+                      "%.3f ms/step, %.1f algorithmic GFLOP/step" % (
+                          'fp32' if math == 'f32' else 'bf16', launches, gemm_ms, flops / 1e9),
+            "stages (one stream; mfma_util = algorithmic FLOPs / stage wall time / MFMA peak; hbm_gbs = algorithmic bytes / stage wall time)": stages}
+
+
 def train_kernel_timing(tr, clips, pids, math, iters=2):
     """Dominant-kernel record of a train series: every forward / data-gradient GEMM (engine.gemm) and every weight
     gradient (train_engine.wgrad) launch of one step, HIP events, with the weight-gradient and TRL side streams off so
@@ -353,10 +388,11 @@ def cpu_baseline(sd, ssd):
 
 
 def train_series(dev, math, steps=20, warmup=5, b=32, t=4, rank=0, world=1, dist=None, profile='default', graph=False,
-                 roofline=False):
+                 roofline=False, outputs=None):
     """One SEQTrainer step (forward + 5-term loss + HIP backward + bucketed gradient all-reduce when a process
     group is up + SGD) on b x t synthetic pair-interleaved clips per rank.  Timed with a barrier + device sync on
-    both sides, MAX over ranks.  Returns a dict (ms_per_step, and the gradient-sync bookkeeping)."""
+    both sides, MAX over ranks.  Returns a dict (ms_per_step, and the gradient-sync bookkeeping).  `outputs`: a dict
+    to fill with what the last timed step computed (its loss, a seeded sample of the updated parameters)."""
     from grl_amd.reid import models
     from grl_amd.reid.train import SEQTrainer
     from grl_amd.reid.loss import OIMLoss, PairLoss
@@ -437,6 +473,9 @@ def train_series(dev, math, steps=20, warmup=5, b=32, t=4, rank=0, world=1, dist
         dt = time.perf_counter() - t0
         per_step = sorted(marks[k].elapsed_time(marks[k + 1]) for k in range(steps))
         assert bool(torch.isfinite(loss).all())
+        if outputs is not None:
+            outputs["loss"] = loss.detach().float().reshape(-1)
+            outputs["params_sample"] = seeded_sample(torch.cat([p.detach().float().reshape(-1) for p in params]))
     finally:
         train_engine.set_math(old)
     dt = max_over_ranks(dist, dev, dt)
@@ -614,9 +653,12 @@ def train_bench(args, dev, dist, rank, world, backend):
     pair-interleaved clips per rank (mars_train.py -b 32 --seq_len 4)."""
     if args.math not in ('f32', 'mixed', 'bf16x3', 'bf16', 'bf16s'):
         raise SystemExit('--mode train supports --math f32 | mixed | bf16x3 | bf16 | bf16s')
+    dumped = {} if (args.dump_outputs and rank == 0) else None
     r = train_series(dev, args.math, steps=args.steps, warmup=args.warmup, b=B, t=T, rank=rank, world=world, dist=dist,
-                     graph=args.graph, roofline=True)
+                     graph=args.graph, roofline=True, outputs=dumped)
     if rank == 0:
+        if dumped:
+            dump_outputs(args.dump_outputs, dumped)
         n = max(world, 1)
         line = {
             "metric": "train clips/sec", "value": r["clips_per_sec"], "unit": "clips/sec", "n_gpus": n,
@@ -656,6 +698,8 @@ def distmat_bench(args, dev, rank):
         d = engine.cosin_dist(qd, gd)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"distmat_sample": seeded_sample(d)})
     idx = engine.rank_rows(d)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
@@ -799,6 +843,34 @@ def emit(obj):
         os.write(_REAL_STDOUT[0], line)
 
 
+DUMP_MAX_BYTES = 64 << 20               # --dump-outputs: all arrays together
+DUMP_SAMPLE = 1 << 22                   # elements kept of an output too large to write whole (16 MB in float32)
+
+
+def seeded_sample(t, n=DUMP_SAMPLE, seed=0):
+    """A fixed sample of n elements of a large tensor: the same flat indices in every run (seeded, sorted)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= n:
+        return flat
+    idx = torch.randint(flat.numel(), (n,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 (float64 stays float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        host[name] = a.numpy() if a.dtype == torch.float64 else a.float().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit('bench.py --dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_MAX_BYTES))
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -823,7 +895,16 @@ def main():
     ap.add_argument('--dry-run', action='store_true',
                     help='launcher check (CPU tests): every rank joins a gloo group, the ranks are counted with an '
                          'all-reduce, rank 0 prints {"dry_run": true, "world_size": N}; no GPU is touched')
+    ap.add_argument('--full', action='store_true',
+                    help='eval: after the timed steps also measure the roofline / per-stage table, the configs[3] '
+                         '`train` block, the other precisions, host-resident inputs, the secondary series and the CPU '
+                         'baseline (a plain run prints the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps write what the last timed step computed as DIR/<name>.npy (float32; '
+                         'a fixed seeded sample of an output too large to keep whole), rank 0 only')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     globals()['B'], globals()['T'] = args.clips, args.seq_len
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -914,23 +995,14 @@ def main():
     barrier()
     dt = max_over_ranks(dist, dev, time.perf_counter() - t0)
     assert bool(torch.isfinite(feat).all())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"features": feat})
     train = None
-    want_train = not args.no_train_block and (B, T, args.math) == (32, 4, 'f32')
+    want_train = args.full and not args.no_train_block and (B, T, args.math) == (32, 4, 'f32')
     out, guard = None, None
     if rank == 0:
         n = max(world, 1)
         value = n * B * args.steps / dt
-        stages = {}
-        flops, gemm_ms, launches = gemm_roofline(cnn, siam, clips, stages=stages)
-        achieved = flops / (gemm_ms * 1e-3) / 1e12
-        # dense MFMA peak of the datapath (MI355X_MICROARCH.md): fp32 157.3, bf16 2500; bf16x3
-        # issues three bf16 MFMAs per product, so its fp32-equivalent peak is 2500/3
-        peak = {'f32': PEAK_FP32_MFMA_TFLOPS, 'bf16': 2500.0, 'bf16s': 2500.0, 'bf16x3': 2500.0 / 3}[args.math]
-        # counter traffic of the SAME kernels (GEMM + fused-tail launches of one step): only from a profile of this build
-        pmc_series = {(32, 4, 'f32'): 'eval_f32', (64, 8, 'bf16s'): 'eval_c3_bf16s'}.get((B, T, args.math))
-        prec, pwhy = pmc_record(pmc_series) if pmc_series else (None, 'no profiled series for this configuration')
-        traffic = prec['dominant']['hbm_bytes_per_step'] if prec else None
-        alg_bytes = sum(v["algorithmic_gb"] for v in stages.values()) * 1e9
         out = {
             "metric": "clip-features/sec", "value": round(value, 2), "unit": "clip-features/sec",
             "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
@@ -946,19 +1018,6 @@ def main():
                                        '2' if (B, T) == (64, 8) and args.math in ('bf16', 'bf16s') else '1 (variant)'),
                        "clips_per_gpu": B, "seq_len": T, "frame": "256x128",
                        "parallelism": "replicas x%d (no collective)" % n},
-            "roofline": {"bound": "mfma" if flops / (peak * 1e12) >= (traffic or alg_bytes) / (PEAK_HBM_GBS * 1e9) else "hbm",
-                         "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4), "traffic": traffic,
-                         "traffic_note": ("profiles/%s_pmc_%s.json, taken on THIS build (fingerprint checked): rocprofv3 FETCH_SIZE x2 + "
-                                          "WRITE_SIZE, separate passes, summed over the same kernels' launches of ONE step "
-                                          "like the GFLOP figure; %.2f x their algorithmic bytes; MFMA busy %s" % (
-                                              PMC_ROUND, pmc_series, traffic / alg_bytes, prec['dominant'].get('mfma_busy_frac')))
-                         if prec else "null: %s" % pwhy,
-                         "algorithmic_gb_per_step": round(alg_bytes / 1e9, 2),
-                         "kernel": "gemm_f32_kernel + fused bottleneck tails (%s MFMA implicit-GEMM conv), %d launches/step, "
-                                   "%.3f ms/step, %.1f algorithmic GFLOP/step" % (
-                                       'fp32' if args.math == 'f32' else 'bf16', launches, gemm_ms, flops / 1e9),
-                         "stages (one stream; mfma_util = algorithmic FLOPs / stage wall time / MFMA peak; hbm_gbs = algorithmic bytes / stage wall time)": stages},
             "end_to_end_tflops": round(value / n * GFLOP_PER_FRAME * T / 1e3, 2),
             # strong-scaling readiness: how much of a step's wall time the host needs just to issue its
             # launches.  >= 1: the step is launch-bound (the GPU waits for the host) -- what `--clips 4` (configs[1] split
@@ -967,6 +1026,8 @@ def main():
                      "launch_bound_frac": round(min(1.0, t_issue / dt), 3)},
         }
         out["config"]["math"] = args.math
+        if args.full:
+            out["roofline"] = eval_roofline(cnn, siam, clips, args.math)
         if dist is not None:
             # what the process group itself reports (the eval data path has no collective; the timed region is
             # bracketed by dist.barrier and the per-rank times are MAX-reduced through it)
@@ -987,7 +1048,7 @@ def main():
     if rank == 0:
         if train is not None:
             out["train"] = train
-        if n == 1 and not args.no_alt:
+        if args.full and n == 1 and not args.no_alt:
             # secondary, informational: the opt-in bf16 multiplier datapaths on the SAME
             # workload, with their deviation from the exact-fp32 features measured live
             alt = {}
@@ -1007,7 +1068,7 @@ def main():
                              "max_rel_dev_vs_headline_features": float(
                                  ((f2 - feat).abs().max() / feat.abs().max()).item())}
             out["alt_math"] = alt
-        if n == 1 and not args.no_alt:
+        if args.full and n == 1 and not args.no_alt:
             # informational (never `value`): the same step fed from HOST-resident pinned batches through
             # engine.DevicePrefetcher (next batch's PCIe copy overlapped on a side stream)
             from grl_amd.synthetic import synth_clips as _sc
@@ -1049,9 +1110,9 @@ def main():
             out["host_resident_inputs"] = {"clip_features_per_sec": host,
                                            "note": "pinned host batches, H2D overlapped; uint8 is normalised in the stem; jpeg: compressed "
                                                    "frames decoded on the device (bit-identical to Pillow), two batches in flight"}
-        if n == 1 and not args.no_alt and (B, T, args.math) == (32, 4, 'f32'):
+        if args.full and n == 1 and not args.no_alt and (B, T, args.math) == (32, 4, 'f32'):
             out["secondary"] = secondary_block(dev, cnn, siam, args.steps)
-        if n == 1 and not args.no_cpu_baseline:
+        if args.full and n == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sd, ssd)
         emit(out)
     if dist is not None:

@@ -265,7 +265,7 @@ def test_rccl_backend_in_a_world_of_one_rank():
 
 
 def test_bench_gpus_2_prints_one_line_with_a_train_block():
-    """The driver's form `python bench.py --gpus N`: the parent starts N fresh ranks (before any GPU call) and
+    """The driver's form `python bench.py --gpus N --full`: the parent starts N fresh ranks (before any GPU call) and
     rank 0 prints ONE line.  On this 1-GPU box both ranks share cuda:0 and talk over gloo
     (GRL_SINGLE_DEVICE=1 GRL_DIST_BACKEND=gloo); the line must say n_gpus 2, carry the process group's world
     size, and a `train` block (configs[3] per GPU) whose gradient buckets were reduced with no stray
@@ -274,7 +274,7 @@ def test_bench_gpus_2_prints_one_line_with_a_train_block():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env.update(GRL_SINGLE_DEVICE='1', GRL_DIST_BACKEND='gloo')
-    res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1'],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--full'],
                          env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith('{')]
