@@ -14,7 +14,8 @@
 //   1'. jpeg_entropy_kernel  the same with a lane per frame (64 frames per workgroup): clean reader with the next dword loaded
 //                            ahead, or the general reader (stuffing / RSTn handled while decoding); a block is assembled in LDS
 //                            (dword-interleaved over the lanes) and leaves as eight 16-byte stores.
-//   2. jpeg_idct_kernel      dequantisation + jidctint.c's jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2), one lane per 8 x 8
+//   2. jpeg_idct_kernel      dequantisation + jidctint.c's jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2) in the integer widths of
+//                            libjpeg-turbo's SIMD form, one lane per 8 x 8
 //                            block, both passes in registers, eight 8-byte row stores into the component plane.
 //   3. jpeg_color_kernel     jdsample.c's triangle-filter ("fancy") chroma upsampling + jdcolor.c's fixed-point YCbCr -> RGB,
 //                            one lane per output pixel, planar uint8 out ([n][3][H][W]: the clip tensor's layout).
@@ -40,15 +41,18 @@ const uint8_t kNaturalHost[64] = {
     0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-// geometry shared by every frame of a batch (from frame 0, checked on the host for the others)
+// geometry shared by every frame of a batch (from frame 0, checked on the host for the others).  Sizes and offsets that
+// grow with the frame area are 64-bit: a 16-bit width and height reach 4 G samples per plane.  The parser refuses frames
+// above the caps below (grl_jpeg_geometry_ok), so per-frame block indices and plane rows stay in int.
 struct Geo {
     int width, height, ncomp, hmax, vmax;
-    int mcux, mcuy, bpm, blocks;          // MCUs per row / column, blocks per MCU, blocks per frame
+    int mcux, mcuy, bpm;                  // MCUs per row / column, blocks per MCU
+    int64_t blocks;                       // blocks per frame
     int hs[3], vs[3];
     int pw[3], ph[3];                     // plane sizes (whole blocks)
     int cw[3], ch[3];                     // real samples per component (downsampled_width / height)
-    int poff[3];                          // byte offset of each component plane inside a frame's plane block
-    int plane_bytes;                      // planes of one frame
+    int64_t poff[3];                      // byte offset of each component plane inside a frame's plane block
+    int64_t plane_bytes;                  // planes of one frame
 };
 
 Geo make_geo(const GrlJpegFrame& f) {
@@ -57,7 +61,7 @@ Geo make_geo(const GrlJpegFrame& f) {
     g.width = f.width; g.height = f.height; g.ncomp = f.ncomp; g.hmax = f.hmax; g.vmax = f.vmax;
     g.mcux = (f.width + 8 * f.hmax - 1) / (8 * f.hmax);
     g.mcuy = (f.height + 8 * f.vmax - 1) / (8 * f.vmax);
-    int off = 0;
+    int64_t off = 0;
     for (int c = 0; c < f.ncomp; ++c) {
         g.hs[c] = f.hs[c]; g.vs[c] = f.vs[c];
         g.bpm += f.hs[c] * f.vs[c];
@@ -66,11 +70,20 @@ Geo make_geo(const GrlJpegFrame& f) {
         g.cw[c] = (f.width * f.hs[c] + f.hmax - 1) / f.hmax;
         g.ch[c] = (f.height * f.vs[c] + f.vmax - 1) / f.vmax;
         g.poff[c] = off;
-        off += g.pw[c] * g.ph[c];
+        off += (int64_t)g.pw[c] * g.ph[c];
     }
-    g.blocks = g.mcux * g.mcuy * g.bpm;
-    g.plane_bytes = (off + 15) & ~15;
+    g.blocks = (int64_t)g.mcux * g.mcuy * g.bpm;
+    g.plane_bytes = (off + 15) & ~(int64_t)15;
     return g;
+}
+
+// the decoder's size caps: at most GRL_JPEG_MAX_PIXELS samples per frame and INT_MAX / 64 blocks (a frame's
+// coefficients are indexed in int).  A header inside T.81's 16-bit limits but above the caps is refused, not wrapped.
+constexpr int64_t GRL_JPEG_MAX_PIXELS = 64ll << 20;
+constexpr int64_t GRL_JPEG_MAX_BLOCKS = 0x7fffffffll / 64;
+bool geometry_ok(const GrlJpegFrame& f) {
+    if ((int64_t)f.width * f.height > GRL_JPEG_MAX_PIXELS || !f.hmax || !f.vmax) return false;
+    return make_geo(f).blocks <= GRL_JPEG_MAX_BLOCKS;
 }
 
 // ---- 1. entropy decoding (the per-lane logic lives in jpeg_core.h: it also compiles as host C++ for the CPU tests) -------
@@ -308,40 +321,43 @@ __global__ __launch_bounds__(PT) void jpeg_entropy_par_kernel(const GrlJpegFrame
         }
 }
 
-// ---- 2. dequantisation + jidctint.c jpeg_idct_islow ---------------------------------------------------------------------
+// ---- 2. dequantisation + jpeg_idct_islow in the integer widths of libjpeg-turbo's SIMD form (what Pillow runs) -------------
+// jidctint.c's algorithm and constants (CONST_BITS 13, PASS1_BITS 2); dequantisation is a 16-bit multiply, in0 +- in4,
+// in7 + in3 and in5 + in1 are 16-bit sums, products are 16 x 16 -> 32-bit multiply-adds, 32-bit sums wrap; pass 1 packs to
+// int16 with saturation, or -- when the coefficients of rows 1..7 are all zero -- takes the DC shortcut (dequantised row 0
+// << PASS1_BITS in 16 bits); pass 2 saturates to -128..127 around 128.  For the values an 8-bit encoder writes this is
+// jidctint.c's result; beyond, it is Pillow's (oracle/ref_c/jpeg_baseline.c idct_islow: the same arithmetic).
 #define GJ_CONST_BITS 13
 #define GJ_PASS1_BITS 2
-#define GJ_DESCALE(x, n) (((x) + (1 << ((n) - 1))) >> (n))
 
-__device__ __forceinline__ uint32_t range_limit(int v) {       // post-IDCT range table: index v & 1023, centred on 128
-    const int i = v & 1023;
-    return i < 128 ? (uint32_t)(i + 128) : (i < 512 ? 255u : (i < 896 ? 0u : (uint32_t)(i - 896)));
-}
+__device__ __forceinline__ int32_t s16(int32_t v) { return (int32_t)(int16_t)(uint16_t)(uint32_t)v; }
+__device__ __forceinline__ int32_t sat16(int32_t v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
+__device__ __forceinline__ uint32_t out8(int32_t v) { return v < -128 ? 0u : (v > 127 ? 255u : (uint32_t)(v + 128)); }
+__device__ __forceinline__ int32_t descale(uint32_t x, int n) { return (int32_t)(x + (1u << (n - 1))) >> n; }
 
-__device__ __forceinline__ void idct_1d(int32_t in0, int32_t in1, int32_t in2, int32_t in3, int32_t in4, int32_t in5, int32_t in6,
-                                        int32_t in7, int32_t (&t)[8]) {
-    // one column (pass 1) or row (pass 2) of jpeg_idct_islow up to the final butterflies: t[0..3] = tmp10..13 (even part),
-    // t[4..7] = tmp0..3 (odd part)
-    int32_t z2 = in2, z3 = in6;
-    int32_t z1 = (z2 + z3) * 4433;
-    const int32_t e2 = z1 + z3 * (-15137), e3 = z1 + z2 * 6270;
-    const int32_t e0 = (int32_t)((uint32_t)(in0 + in4) << GJ_CONST_BITS), e1 = (int32_t)((uint32_t)(in0 - in4) << GJ_CONST_BITS);
-    t[0] = e0 + e3; t[3] = e0 - e3; t[1] = e1 + e2; t[2] = e1 - e2;
-    int32_t tmp0 = in7, tmp1 = in5, tmp2 = in3, tmp3 = in1;
-    z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2;
-    int32_t z4 = tmp1 + tmp3;
-    const int32_t z5 = (z3 + z4) * 9633;
-    tmp0 *= 2446; tmp1 *= 16819; tmp2 *= 25172; tmp3 *= 12299;
-    z1 *= -7373; z2 *= -20995; z3 *= -16069; z4 *= -3196;
-    z3 += z5; z4 += z5;
-    t[4] = tmp0 + z1 + z3; t[5] = tmp1 + z2 + z4; t[6] = tmp2 + z2 + z3; t[7] = tmp3 + z1 + z4;
+// one column (pass 1) or row (pass 2) on 16-bit inputs: o[0..7] = the output sums in front of the descale
+__device__ __forceinline__ void idct_1d(int32_t i0, int32_t i1, int32_t i2, int32_t i3, int32_t i4, int32_t i5, int32_t i6,
+                                        int32_t i7, uint32_t (&o)[8]) {
+    const uint32_t e0 = (uint32_t)s16(i0 + i4) << GJ_CONST_BITS, e1 = (uint32_t)s16(i0 - i4) << GJ_CONST_BITS;
+    const uint32_t e3 = (uint32_t)(i2 * (4433 + 6270)) + (uint32_t)(i6 * 4433);
+    const uint32_t e2 = (uint32_t)(i2 * 4433) + (uint32_t)(i6 * (4433 - 15137));
+    const uint32_t t10 = e0 + e3, t13 = e0 - e3, t11 = e1 + e2, t12 = e1 - e2;
+    const int32_t z3 = s16(i7 + i3), z4 = s16(i5 + i1);
+    const uint32_t Z3 = (uint32_t)(z3 * (9633 - 16069)) + (uint32_t)(z4 * 9633);
+    const uint32_t Z4 = (uint32_t)(z3 * 9633) + (uint32_t)(z4 * (9633 - 3196));
+    const uint32_t T0 = (uint32_t)(i7 * (2446 - 7373)) + (uint32_t)(i1 * -7373) + Z3;
+    const uint32_t T3 = (uint32_t)(i7 * -7373) + (uint32_t)(i1 * (12299 - 7373)) + Z4;
+    const uint32_t T1 = (uint32_t)(i5 * (16819 - 20995)) + (uint32_t)(i3 * -20995) + Z4;
+    const uint32_t T2 = (uint32_t)(i5 * -20995) + (uint32_t)(i3 * (25172 - 20995)) + Z3;
+    o[0] = t10 + T3; o[7] = t10 - T3; o[1] = t11 + T2; o[6] = t11 - T2;
+    o[2] = t12 + T1; o[5] = t12 - T1; o[3] = t13 + T0; o[4] = t13 - T0;
 }
 
 __global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restrict__ coef, const GrlJpegFrame* __restrict__ frames,
                                                         int n, uint8_t* __restrict__ planes, Geo g) {
     const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (gid >= (int64_t)n * g.blocks) return;
-    const int f = (int)(gid / g.blocks), blk = (int)(gid % g.blocks);
+    const int f = (int)(gid / g.blocks), blk = (int)(gid % g.blocks);     // (blocks <= GRL_JPEG_MAX_BLOCKS)
     const int mcu = blk / g.bpm;
     int within = blk % g.bpm, c = 0;
     while (within >= g.hs[c] * g.vs[c]) { within -= g.hs[c] * g.vs[c]; ++c; }
@@ -350,39 +366,46 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restric
     const uint16_t* q = frames[f].q[frames[f].tq[c] & 3];
     const int16_t* in = coef + gid * 64;
     int32_t v[64];
+    uint32_t ac = 0;                              // any coefficient of rows 1..7 nonzero (before dequantisation)
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {                 // 8 x 16-byte loads, dequantised on the way in
+    for (int i = 0; i < 8; ++i) {                 // 8 x 16-byte loads, dequantised (16-bit multiply) on the way in
         const uint4 cw = *reinterpret_cast<const uint4*>(in + 8 * i);
         const uint4 qw = *reinterpret_cast<const uint4*>(q + 8 * i);
+        if (i) ac |= cw.x | cw.y | cw.z | cw.w;
         const uint32_t cc[4] = {cw.x, cw.y, cw.z, cw.w}, qq[4] = {qw.x, qw.y, qw.z, qw.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            v[8 * i + 2 * e] = (int32_t)(int16_t)(cc[e] & 0xffffu) * (int32_t)(qq[e] & 0xffffu);
-            v[8 * i + 2 * e + 1] = (int32_t)(int16_t)(cc[e] >> 16) * (int32_t)(qq[e] >> 16);
+            v[8 * i + 2 * e] = s16((int32_t)(int16_t)(cc[e] & 0xffffu) * (int32_t)(int16_t)(qq[e] & 0xffffu));
+            v[8 * i + 2 * e + 1] = s16((int32_t)(int16_t)(cc[e] >> 16) * (int32_t)(int16_t)(qq[e] >> 16));
         }
     }
-    int32_t t[8];
+    uint32_t t[8];
+    if (ac) {
 #pragma unroll
-    for (int col = 0; col < 8; ++col) {           // pass 1: columns
-        idct_1d(v[col], v[8 + col], v[16 + col], v[24 + col], v[32 + col], v[40 + col], v[48 + col], v[56 + col], t);
-        const int sh = GJ_CONST_BITS - GJ_PASS1_BITS;
-        v[col] = GJ_DESCALE(t[0] + t[7], sh);      v[56 + col] = GJ_DESCALE(t[0] - t[7], sh);
-        v[8 + col] = GJ_DESCALE(t[1] + t[6], sh);  v[48 + col] = GJ_DESCALE(t[1] - t[6], sh);
-        v[16 + col] = GJ_DESCALE(t[2] + t[5], sh); v[40 + col] = GJ_DESCALE(t[2] - t[5], sh);
-        v[24 + col] = GJ_DESCALE(t[3] + t[4], sh); v[32 + col] = GJ_DESCALE(t[3] - t[4], sh);
+        for (int col = 0; col < 8; ++col) {       // pass 1: columns, packed to int16 with saturation
+            idct_1d(v[col], v[8 + col], v[16 + col], v[24 + col], v[32 + col], v[40 + col], v[48 + col], v[56 + col], t);
+#pragma unroll
+            for (int r = 0; r < 8; ++r) v[8 * r + col] = sat16(descale(t[r], GJ_CONST_BITS - GJ_PASS1_BITS));
+        }
+    } else {
+#pragma unroll
+        for (int col = 0; col < 8; ++col) {       // the DC shortcut: row 0 << PASS1_BITS in 16 bits, every row
+            const int32_t d = s16(v[col] * (1 << GJ_PASS1_BITS));
+#pragma unroll
+            for (int r = 0; r < 8; ++r) v[8 * r + col] = d;
+        }
     }
     uint8_t* dst = planes + (int64_t)f * g.plane_bytes + g.poff[c] + (int64_t)((my * g.vs[c] + by) * 8) * g.pw[c] + (mx * g.hs[c] + bx) * 8;
 #pragma unroll
-    for (int r = 0; r < 8; ++r) {                 // pass 2: rows, through the range table, one 8-byte store per row
+    for (int r = 0; r < 8; ++r) {                 // pass 2: rows, saturated around 128, one 8-byte store per row
         idct_1d(v[8 * r], v[8 * r + 1], v[8 * r + 2], v[8 * r + 3], v[8 * r + 4], v[8 * r + 5], v[8 * r + 6], v[8 * r + 7], t);
         const int sh = GJ_CONST_BITS + GJ_PASS1_BITS + 3;
-        const uint32_t o0 = range_limit(GJ_DESCALE(t[0] + t[7], sh)), o7 = range_limit(GJ_DESCALE(t[0] - t[7], sh));
-        const uint32_t o1 = range_limit(GJ_DESCALE(t[1] + t[6], sh)), o6 = range_limit(GJ_DESCALE(t[1] - t[6], sh));
-        const uint32_t o2 = range_limit(GJ_DESCALE(t[2] + t[5], sh)), o5 = range_limit(GJ_DESCALE(t[2] - t[5], sh));
-        const uint32_t o3 = range_limit(GJ_DESCALE(t[3] + t[4], sh)), o4 = range_limit(GJ_DESCALE(t[3] - t[4], sh));
+        uint32_t o[8];
+#pragma unroll
+        for (int x = 0; x < 8; ++x) o[x] = out8(descale(t[x], sh));
         uint2 w;
-        w.x = o0 | (o1 << 8) | (o2 << 16) | (o3 << 24);
-        w.y = o4 | (o5 << 8) | (o6 << 16) | (o7 << 24);
+        w.x = o[0] | (o[1] << 8) | (o[2] << 16) | (o[3] << 24);
+        w.y = o[4] | (o[5] << 8) | (o[6] << 16) | (o[7] << 24);
         *reinterpret_cast<uint2*>(dst + (int64_t)r * g.pw[c]) = w;
     }
 }
@@ -494,7 +517,9 @@ extern "C" int grl_jpeg_parse(const uint8_t* p, int64_t len, int64_t base_off, G
     GrlJpegFrame& f = *out;
     memset(&f, 0, sizeof(f));
     bool have_sof = false, have_scan = false, qpresent[4] = {false, false, false, false}, hpresent[4] = {false, false, false, false};
+    bool jfif = false, q16[4] = {false, false, false, false};
     int adobe = -1;
+    uint8_t cid[3] = {0, 0, 0};                         // component ids in SOF order (the SOS selectors refer to them)
     const size_t n = (size_t)len;
     size_t i = 2;
     while (i + 4 <= n) {
@@ -520,7 +545,10 @@ extern "C" int grl_jpeg_parse(const uint8_t* p, int64_t len, int64_t base_off, G
                 f.hs[c] = s[7 + 3 * c] >> 4;
                 f.vs[c] = s[7 + 3 * c] & 15;
                 f.tq[c] = s[8 + 3 * c];
+                cid[c] = s[6 + 3 * c];
                 if (f.tq[c] > 3 || !f.hs[c] || !f.vs[c]) return grl_fail(GRL_EINVAL, "jpeg_parse: bad SOF component");
+                for (int d = 0; d < c; ++d)
+                    if (cid[d] == cid[c]) return grl_fail(GRL_EUNSUPPORTED, "jpeg_parse: component id %d appears twice in SOF", (int)cid[c]);
             }
             have_sof = true;
         } else if (m >= 0xC2 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
@@ -554,21 +582,31 @@ extern "C" int grl_jpeg_parse(const uint8_t* p, int64_t len, int64_t base_off, G
                 for (int k = 0; k < 64; ++k)
                     f.q[tq][kNaturalHost[k]] = pq ? (uint16_t)((s[o + 1 + 2 * k] << 8) | s[o + 2 + 2 * k]) : s[o + 1 + k];
                 qpresent[tq] = true;
+                q16[tq] = pq != 0;
                 o += need;
             }
         } else if (m == 0xDD) {
             if (sl < 2) return grl_fail(GRL_EINVAL, "jpeg_parse: bad DRI");
             f.restart_interval = (uint16_t)((s[0] << 8) | s[1]);
+        } else if (m == 0xE0) {
+            if (sl >= 14 && !memcmp(s, "JFIF", 5)) jfif = true;      // (libjpeg's examine_app0: APP0_DATA_LEN = 14)
         } else if (m == 0xEE) {
             if (sl >= 12 && !memcmp(s, "Adobe", 5)) adobe = s[11];
         } else if (m == 0xDA) {
             if (!have_sof) return grl_fail(GRL_EINVAL, "jpeg_parse: SOS before SOF");
             if (sl < 1 || s[0] != f.ncomp || sl < 1 + 2 * (size_t)f.ncomp + 3)
                 return grl_fail(GRL_EUNSUPPORTED, "jpeg_parse: non-interleaved scans are outside the device decoder's scope");
+            // selectors name SOF components by id; the kernels decode an MCU's components in SOF order, so the scan must
+            // list them in that order (libjpeg takes any order: a permuted scan is refused, not misread)
             for (int c = 0; c < f.ncomp; ++c) {
-                f.td[c] = s[2 + 2 * c] >> 4;
-                f.ta[c] = s[2 + 2 * c] & 15;
-                if (f.td[c] > 1 || f.ta[c] > 1) return grl_fail(GRL_EUNSUPPORTED, "jpeg_parse: Huffman table id > 1");
+                const uint8_t sel = s[1 + 2 * c];
+                int k = 0;
+                while (k < f.ncomp && cid[k] != sel) ++k;
+                if (k == f.ncomp) return grl_fail(GRL_EINVAL, "jpeg_parse: scan selector %d names no frame component", (int)sel);
+                if (k != c) return grl_fail(GRL_EUNSUPPORTED, "jpeg_parse: scan lists the components in another order than the frame");
+                f.td[k] = s[2 + 2 * c] >> 4;
+                f.ta[k] = s[2 + 2 * c] & 15;
+                if (f.td[k] > 1 || f.ta[k] > 1) return grl_fail(GRL_EUNSUPPORTED, "jpeg_parse: Huffman table id > 1");
             }
             f.scan_off = (uint32_t)(base_off + (int64_t)(i + seg));
             f.scan_len = (uint32_t)(n - (i + seg));
@@ -583,6 +621,9 @@ extern "C" int grl_jpeg_parse(const uint8_t* p, int64_t len, int64_t base_off, G
         if (f.hs[c] > f.hmax) f.hmax = f.hs[c];
         if (f.vs[c] > f.vmax) f.vmax = f.vs[c];
         if (!qpresent[f.tq[c]] || !hpresent[f.td[c]] || !hpresent[2 + f.ta[c]]) return grl_fail(GRL_EINVAL, "jpeg_parse: a table the scan uses is missing");
+        // T.81 B.2.4.1: 16-bit quantisers (Pq = 1) only with 12-bit samples.  libjpeg-turbo keeps them as 16-bit signed
+        // multipliers and dequantises in 16 bits in its SIMD IDCT: no arithmetic of ours could be pinned to its output.
+        if (q16[f.tq[c]]) return grl_fail(GRL_EUNSUPPORTED, "jpeg_parse: 16-bit quantisation table with 8-bit samples");
     }
     if (f.ncomp == 3) {
         const bool chroma11 = f.hs[1] == 1 && f.vs[1] == 1 && f.hs[2] == 1 && f.vs[2] == 1;
@@ -590,11 +631,16 @@ extern "C" int grl_jpeg_parse(const uint8_t* p, int64_t len, int64_t base_off, G
         if (!chroma11 || !luma_ok)
             return grl_fail(GRL_EUNSUPPORTED, "jpeg_parse: sampling %dx%d / %dx%d / %dx%d (4:4:4, 4:2:2, 4:2:0 are in scope)", f.hs[0], f.vs[0],
                             f.hs[1], f.vs[1], f.hs[2], f.vs[2]);
-        if (adobe == 0) f.rgb = 1;
-        else if (adobe == 2) return grl_fail(GRL_EUNSUPPORTED, "jpeg_parse: Adobe YCCK");
+        // libjpeg's default_decompress_parms: JFIF -> YCbCr; else an Adobe marker decides (transform 0 -> RGB); else the
+        // ids R, G, B -> RGB; else YCbCr.  One exception: Adobe transform 2 (YCCK) is refused even with a JFIF marker,
+        // where libjpeg would read YCbCr (refusing is within the contract; such a stream contradicts itself).
+        if (adobe == 2) return grl_fail(GRL_EUNSUPPORTED, "jpeg_parse: Adobe YCCK");
+        if (!jfif) f.rgb = adobe >= 0 ? adobe == 0 : (cid[0] == 'R' && cid[1] == 'G' && cid[2] == 'B');
     } else {
         f.hs[0] = f.vs[0] = f.hmax = f.vmax = 1;      // a single-component scan is never interleaved: the factors are moot
     }
+    if (!geometry_ok(f))
+        return grl_fail(GRL_EUNSUPPORTED, "jpeg_parse: %d x %d frame above the decoder's caps (64 Mpx, INT_MAX / 64 blocks)", (int)f.width, (int)f.height);
     return GRL_OK;
 }
 
@@ -639,6 +685,7 @@ static Layout make_layout(const Geo& g, int n, uint32_t nbytes) {
 
 extern "C" int64_t grl_jpeg_workspace_bytes(const GrlJpegFrame* frames_host, int n) {
     if (!frames_host || n <= 0 || !frames_host[0].width || !frames_host[0].hmax) return 0;
+    if (!geometry_ok(frames_host[0])) return grl_fail(GRL_EUNSUPPORTED, "jpeg_workspace_bytes: frame above the decoder's caps");
     return make_layout(make_geo(frames_host[0]), n, scan_extent(frames_host, n)).total;
 }
 
@@ -678,6 +725,7 @@ extern "C" int grl_jpeg_decode_batch(const uint8_t* bytes, const GrlJpegFrame* f
     const GrlJpegFrame& f0 = frames_host[0];
     GRL_REQUIRE(f0.width && f0.height && (f0.ncomp == 1 || f0.ncomp == 3) && f0.hmax >= 1 && f0.hmax <= 2 && f0.vmax >= 1 && f0.vmax <= 2,
                 "jpeg_decode_batch: frame 0 was not parsed by grl_jpeg_parse");
+    if (!geometry_ok(f0)) return grl_fail(GRL_EUNSUPPORTED, "jpeg_decode_batch: frame above the decoder's caps (grl_jpeg_parse refuses it)");
     uint32_t nbytes = 0;
     for (int i = 0; i < n; ++i) {
         const GrlJpegFrame& f = frames_host[i];
@@ -688,7 +736,7 @@ extern "C" int grl_jpeg_decode_batch(const uint8_t* bytes, const GrlJpegFrame* f
         if (e < f.scan_off) return grl_fail(GRL_EINVAL, "jpeg_decode_batch: frame %d: stream range wraps", i);
         if (e > nbytes) nbytes = e;
     }
-    GRL_REQUIRE(workspace_bytes >= grl_jpeg_workspace_bytes(frames_host, n), "jpeg_decode_batch: workspace too small (grl_jpeg_workspace_bytes)");
+    GRL_REQUIRE(workspace_bytes > 0 && workspace_bytes >= grl_jpeg_workspace_bytes(frames_host, n), "jpeg_decode_batch: workspace too small (grl_jpeg_workspace_bytes)");
     // table sets (grl_jpeg_assign_tables): a frame's tables must be the ones of its set's first frame
     constexpr size_t TB = sizeof(f0.maxcode) + sizeof(f0.valoff) + sizeof(f0.vals);
     int sets = 0;
@@ -735,9 +783,10 @@ extern "C" int grl_jpeg_decode_batch(const uint8_t* bytes, const GrlJpegFrame* f
     for (int i = 0; i < n; ++i) any_restart = any_restart || frames_host[i].restart_interval != 0;
     uint32_t max_scan = 0;
     for (int i = 0; i < n; ++i) max_scan = frames_host[i].scan_len > max_scan ? frames_host[i].scan_len : max_scan;
-    if (!any_restart && g_jpeg_parallel && max_scan <= (uint32_t)PAR_MAX_SCAN && g.blocks <= PAR_MAX_BLOCKS) {
+    const int blocks = (int)g.blocks;                      // (<= GRL_JPEG_MAX_BLOCKS: geometry_ok above)
+    if (!any_restart && g_jpeg_parallel && max_scan <= (uint32_t)PAR_MAX_SCAN && blocks <= PAR_MAX_BLOCKS) {
         // the common case: stuffing removed by a pre-pass, then ONE WORKGROUP PER FRAME decodes self-synchronising subsequences
-        const ParLayout lay = par_layout(g.blocks, (int)((max_scan + 3) / 4));
+        const ParLayout lay = par_layout(blocks, (int)((max_scan + 3) / 4));
         static int attr_bytes = 0;
         if (lay.total > attr_bytes) {
             (void)hipFuncSetAttribute((const void*)jpeg_entropy_par_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lay.total);
@@ -746,16 +795,16 @@ extern "C" int grl_jpeg_decode_batch(const uint8_t* bytes, const GrlJpegFrame* f
         if (hipMemsetAsync(coef, 0, (size_t)n * g.blocks * 64 * sizeof(int16_t), s) != hipSuccess) return grl_check_launch("jpeg_decode_batch (memset)");
         hipLaunchKernelGGL(jpeg_unstuff_kernel, dim3(n), dim3(UT), 0, s, bytes, frames_dev, clean, clean_len);
         static const uint32_t seq_bits = [] { const char* e = getenv("GRL_JPEG_SEQ_BITS"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 32 ? (v + 31) & ~31 : 512); }();
-        hipLaunchKernelGGL(jpeg_entropy_par_kernel, dim3(n), dim3(PT), (size_t)lay.total, s, frames_dev, coef, g.blocks, g.mcux * g.mcuy, lut,
+        hipLaunchKernelGGL(jpeg_entropy_par_kernel, dim3(n), dim3(PT), (size_t)lay.total, s, frames_dev, coef, blocks, g.mcux * g.mcuy, lut,
                            clean, clean_len, lay, seq_bits);
     } else if (!any_restart) {
         // frames too large for the workgroup form: one lane per frame on the clean stream
         hipLaunchKernelGGL(jpeg_unstuff_kernel, dim3(n), dim3(UT), 0, s, bytes, frames_dev, clean, clean_len);
         hipLaunchKernelGGL(jpeg_entropy_kernel<0>, dim3(grl_ceil_div(n, EW)), dim3(EW), e_lds, s, bytes, nbytes, frames_dev, n, coef, sg,
-                           g.blocks, lut, lds_sets, clean, clean_len);
+                           blocks, lut, lds_sets, clean, clean_len);
     } else {
         hipLaunchKernelGGL(jpeg_entropy_kernel<1>, dim3(grl_ceil_div(n, EW)), dim3(EW), e_lds, s, bytes, nbytes, frames_dev, n, coef, sg,
-                           g.blocks, lut, lds_sets, clean, clean_len);
+                           blocks, lut, lds_sets, clean, clean_len);
     }
     const int64_t nblk = (int64_t)n * g.blocks;
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, s, coef, frames_dev, n, planes, g);

@@ -108,10 +108,15 @@ GRL_HD static inline void gj_bits_init(GjBits& b, const uint8_t* bytes, uint32_t
     b.caddr = 0xffffffffu; b.cword = 0;
 }
 
-// discard the partial byte, find the RSTn marker, step over it (restart intervals: the general reader only)
+// discard the partial byte, find the RSTn marker, step over it (restart intervals: the general reader only).  When gj_fill
+// stopped on an 0xFF (the last byte of a dword; ffp pending) that byte is the marker's first one: the search starts there.
+// (GJ_RESTART_HOOK: a test build's probe of that state.)
 GRL_HD static inline void gj_restart(GjBits& b) {
+#ifdef GJ_RESTART_HOOK
+    GJ_RESTART_HOOK(b);
+#endif
+    uint32_t q = b.ffp && !b.marker ? b.pos - 1 : b.pos;
     b.cnt = 0; b.acc = 0; b.ffp = 0;
-    uint32_t q = b.pos;
     while (q + 1 < b.end) {
         if (gj_byte_at(b, q) == 0xFF) {
             const int m2 = gj_byte_at(b, q + 1);

@@ -1,6 +1,8 @@
 """Frame decode on the device: the counterpart of `Image.open(img_path).convert('RGB')` in the reference's loaders
 (/root/reference/reid/data/video_loader.py:124-141, :91-96, :108-113) through grl_jpeg_parse / grl_jpeg_decode_batch
-(include/grl_hip.h, grl_amd/csrc/jpeg.hip) -- bit-identical to Pillow for baseline JPEGs (4:4:4 / 4:2:2 / 4:2:0 / grey).
+(include/grl_hip.h, grl_amd/csrc/jpeg.hip) -- bit-identical to Pillow for baseline JPEGs (4:4:4 / 4:2:2 / 4:2:0 / grey; one
+scan listing the components in frame order; 8-bit quantisers; at most 64 Mpx), colour space by libjpeg's rule (JFIF ->
+YCbCr, else an Adobe marker, else component ids 'R', 'G', 'B' -> RGB).
 
 A loader worker only READS the files; a batch crosses PCIe as compressed bytes (MARS: ~6-13 KB per 98 KB frame) and is
 decoded on the prefetch stream next to the previous batch's compute.  There is no host fallback in here: a stream the
@@ -19,7 +21,8 @@ __all__ = ['JpegUnsupported', 'JpegBatch', 'decode_jpeg_batch', 'jpeg_collate', 
 
 
 class JpegUnsupported(GrlHipError):
-    """A valid JPEG outside the device decoder's scope (progressive, arithmetic, CMYK, 12-bit, 4:4:0 ...)."""
+    """A valid JPEG outside the device decoder's scope (progressive, arithmetic, CMYK, 12-bit, 4:4:0, a permuted scan,
+    16-bit quantisers, frames above 64 Mpx ...)."""
 
 
 def read_file(path):
@@ -164,6 +167,8 @@ def decode_jpeg_batch(batch, device, size=None):
     dframes = fpin[:fsize].to(device, non_blocking=True)
     ring_f.mark(jf)
     need = int(lib.grl_jpeg_workspace_bytes(frames, n))
+    if need <= 0:
+        _lib.check(need or _lib.GRL_EINVAL, 'grl_jpeg_workspace_bytes')
     ws = torch.empty(need, dtype=torch.uint8, device=device)
     out = torch.empty(batch.shape + (3, H, W), dtype=torch.uint8, device=device)
     rc = lib.grl_jpeg_decode_batch(dbytes.data_ptr(), dframes.data_ptr(), frames, n, out.data_ptr(), ws.data_ptr(), need,

@@ -673,8 +673,14 @@ int grl_bottleneck_tail_f32_supported(int P, int C4, int Pn);
  * subsequences of the bit stream; one lane per frame for scans with restart intervals or frames too large for the
  * workgroup form), dequantisation + jidctint's integer IDCT (one lane per 8 x 8 block), triangle-filter chroma
  * upsampling + YCbCr -> RGB (one lane per pixel).
- * Scope: 8-bit baseline / extended-sequential Huffman, one interleaved scan, 1 or 3 components, luma sampling 1x1,
- * 2x1 or 2x2 (4:4:4, 4:2:2, 4:2:0 -- MARS' frames are 256 x 128 4:2:0), table ids 0..1, restart intervals.
+ * Scope: 8-bit baseline / extended-sequential Huffman, one interleaved scan whose selectors list the components in
+ * SOF order, 1 or 3 components (unique ids), luma sampling 1x1, 2x1 or 2x2 (4:4:4, 4:2:2, 4:2:0 -- MARS' frames are
+ * 256 x 128 4:2:0), table ids 0..1, 8-bit quantisers (Pq = 0, as T.81 requires with 8-bit samples), restart
+ * intervals, width x height <= 64 Mpx.  Colour space by libjpeg's rule: JFIF -> YCbCr; else an Adobe marker decides
+ * (transform 0 -> RGB, 1 -> YCbCr); else component ids 'R', 'G', 'B' -> RGB; else YCbCr.  Adobe transform 2 (YCCK)
+ * is refused even where a JFIF marker would make libjpeg read YCbCr.  The IDCT is jidctint.c's in the integer widths of
+ * libjpeg-turbo's SIMD form, which Pillow runs (16-bit dequantisation and sums, saturating packs): bit-identical for
+ * any coefficient under any 8-bit quantiser, also past the values an encoder of 8-bit samples writes.
  * Anything else is refused by the parser with GRL_EUNSUPPORTED: the caller (grl_amd/reid/data/jpeg.py) says so
  * loudly -- it does not decode on the host behind the caller's back.
  */
@@ -685,7 +691,7 @@ typedef struct GrlJpegFrame {      /* one parsed frame: filled on the host by gr
     uint32_t scan_len;
     uint16_t width, height;
     uint16_t restart_interval;     /* MCUs between RSTn markers, 0 = none */
-    uint8_t  ncomp, hmax, vmax, rgb;   /* rgb: components are R, G, B (Adobe transform 0): no colour conversion */
+    uint8_t  ncomp, hmax, vmax, rgb;   /* rgb: components are R, G, B (libjpeg's rule above): no colour conversion */
     uint8_t  hs[4], vs[4];         /* sampling factors per component */
     uint8_t  tq[4], td[4], ta[4];  /* quantisation / DC / AC table of each component */
     uint16_t tabset;               /* index of this frame's Huffman table set inside its batch (grl_jpeg_assign_tables) */
@@ -710,7 +716,7 @@ int grl_jpeg_assign_tables(GrlJpegFrame* frames, int n);
  * grl_jpeg_assign_tables.  On failure *bad_index is the offending frame and the return value its code. */
 int grl_jpeg_parse_batch(const uint8_t* buf, const int64_t* offsets, int n, GrlJpegFrame* frames, int* bad_index);
 /* bytes of device scratch grl_jpeg_decode_batch needs for the n parsed frames of a batch (coefficients, planes,
- * look-ahead tables, unstuffed streams) */
+ * look-ahead tables, unstuffed streams); GRL_EUNSUPPORTED for a frame above the size caps */
 int64_t grl_jpeg_workspace_bytes(const GrlJpegFrame* frames_host, int n);
 /* n frames of ONE geometry (width, height, components, sampling: as frames[0]; frames_host is checked) ->
  * out uint8 [n][3][height][width] (planar RGB: the layout the clip tensors [B][T][3][H][W] have).

@@ -5,16 +5,22 @@
  * decoder with libjpeg's defaults dct_method = JDCT_ISLOW, do_fancy_upsampling = TRUE).  The arithmetic follows the
  * published libjpeg algorithms, which libjpeg-turbo's SIMD paths reproduce bit for bit:
  *   entropy decoding     ITU-T T.81 Annex F.2.2 (jdhuff.c decode_mcu), byte stuffing, restart intervals
- *   dequantisation+IDCT  jidctint.c jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2), output through the post-IDCT range table
+ *   dequantisation+IDCT  jidctint.c jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2) in the integer widths of
+ *                        libjpeg-turbo's SIMD form (idct_islow below)
  *   chroma upsampling    jdsample.c h2v2_fancy_upsample / h2v1_fancy_upsample / h1v2_fancy_upsample (triangle filter),
  *                        edge context rows replicated as jdmainct.c does; plain replication when downsampled_width <= 2
  *   colour conversion    jdcolor.c ycc_rgb_convert (16-bit fixed-point tables)
  * Pinned by tests/test_jpeg_cpu.py against Pillow itself on generated frames (sizes off the MCU grid, 4:4:4 / 4:2:2 /
  * 4:2:0 / 4:4:0 / grey, qualities 30..100, restart intervals) and by tests/golden/jpeg_frames.npz.
  *
- * Scope: 8-bit baseline / extended-sequential Huffman (SOF0 / SOF1), one scan, 1 or 3 components (YCbCr by JFIF
- * convention, RGB when an Adobe marker says transform 0), luma sampling 1x1, 2x1 or 2x2 with 1x1 chroma.
- * Anything else (progressive, arithmetic, CMYK, 12-bit) returns an error code -- the caller decides.
+ * Scope: 8-bit baseline / extended-sequential Huffman (SOF0 / SOF1), one scan listing the components in frame order,
+ * 1 or 3 components, luma sampling 1x1, 2x1 or 2x2 with 1x1 chroma, 8-bit quantisers (T.81 B.2.4.1: Pq = 0 with 8-bit
+ * samples).  Colour space as libjpeg's default_decompress_parms decides it: JFIF -> YCbCr; else an Adobe marker
+ * (transform 0 -> RGB, 1 -> YCbCr); else component ids 'R', 'G', 'B' -> RGB; else YCbCr.  Adobe transform 2 is refused,
+ * with or without JFIF.
+ * Anything else (progressive, arithmetic, CMYK, 12-bit, a permuted scan) returns an error code -- the caller decides.
+ * The IDCT follows libjpeg-turbo's SIMD integer widths (16-bit dequantisation and sums, saturating packs): what Pillow
+ * returns for any 8-bit quantiser and any coefficient, including values no encoder of 8-bit samples writes.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -43,7 +49,7 @@ typedef struct {
     int hs[3], vs[3], tq[3], td[3], ta[3];
     int hmax, vmax;
     int restart_interval;
-    int rgb;                /* 1: components are R,G,B (Adobe transform 0) */
+    int rgb;                /* 1: components are R, G, B (libjpeg's colour-space rule, see the scope note) */
     uint16_t q[4][64];      /* natural order */
     int qpresent[4];
     HuffTab dc[4], ac[4];
@@ -71,7 +77,8 @@ static int parse(const uint8_t* p, size_t n, Jpeg* j) {
     memset(j, 0, sizeof(*j));
     if (n < 4 || p[0] != 0xFF || p[1] != 0xD8) return GJ_EFORMAT;
     size_t i = 2;
-    int have_sof = 0, adobe = -1;
+    int have_sof = 0, adobe = -1, jfif = 0, q16[4] = {0, 0, 0, 0};
+    int cid[3] = {0, 0, 0};
     while (i + 4 <= n) {
         if (p[i] != 0xFF) return GJ_EFORMAT;
         while (i < n && p[i] == 0xFF) ++i;           /* fill bytes */
@@ -95,7 +102,10 @@ static int parse(const uint8_t* p, size_t n, Jpeg* j) {
                 j->hs[c] = s[7 + 3 * c] >> 4;
                 j->vs[c] = s[7 + 3 * c] & 15;
                 j->tq[c] = s[8 + 3 * c];
+                cid[c] = s[6 + 3 * c];
                 if (j->tq[c] > 3) return GJ_EFORMAT;
+                for (int d = 0; d < c; ++d)
+                    if (cid[d] == cid[c]) return GJ_EUNSUPPORTED;   /* duplicate ids: libjpeg invents ids, we do not */
             }
             have_sof = 1;
         } else if (m == 0xC2 || (m >= 0xC3 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC)) {
@@ -130,19 +140,26 @@ static int parse(const uint8_t* p, size_t n, Jpeg* j) {
                     o += 129;
                 }
                 j->qpresent[tq] = 1;
+                q16[tq] = pq != 0;
             }
         } else if (m == 0xDD) {
             if (sl < 2) return GJ_EFORMAT;
             j->restart_interval = (s[0] << 8) | s[1];
+        } else if (m == 0xE0) {
+            if (sl >= 14 && !memcmp(s, "JFIF", 5)) jfif = 1;
         } else if (m == 0xEE) {
             if (sl >= 12 && !memcmp(s, "Adobe", 5)) adobe = s[11];
         } else if (m == 0xDA) {
             if (!have_sof) return GJ_EFORMAT;
             if (sl < 1 || s[0] != j->ncomp || sl < 1 + 2 * (size_t)j->ncomp + 3) return GJ_EUNSUPPORTED;   /* one interleaved scan */
-            for (int c = 0; c < j->ncomp; ++c) {
-                j->td[c] = s[2 + 2 * c] >> 4;
-                j->ta[c] = s[2 + 2 * c] & 15;
-                if (j->td[c] > 3 || j->ta[c] > 3) return GJ_EFORMAT;
+            for (int c = 0; c < j->ncomp; ++c) {      /* selectors name components by id; only the frame's order is taken */
+                int k = 0;
+                while (k < j->ncomp && cid[k] != s[1 + 2 * c]) ++k;
+                if (k == j->ncomp) return GJ_EFORMAT;
+                if (k != c) return GJ_EUNSUPPORTED;
+                j->td[k] = s[2 + 2 * c] >> 4;
+                j->ta[k] = s[2 + 2 * c] & 15;
+                if (j->td[k] > 3 || j->ta[k] > 3) return GJ_EFORMAT;
             }
             j->scan = p + i + len;
             j->scan_len = n - (i + len);
@@ -157,12 +174,13 @@ static int parse(const uint8_t* p, size_t n, Jpeg* j) {
         if (j->hs[c] > j->hmax) j->hmax = j->hs[c];
         if (j->vs[c] > j->vmax) j->vmax = j->vs[c];
         if (!j->qpresent[j->tq[c]] || !j->dc[j->td[c]].present || !j->ac[j->ta[c]].present) return GJ_EFORMAT;
+        if (q16[j->tq[c]]) return GJ_EUNSUPPORTED;
     }
     if (j->ncomp == 3) {
         if (j->hs[1] != 1 || j->vs[1] != 1 || j->hs[2] != 1 || j->vs[2] != 1 || j->hs[0] > 2 || j->vs[0] > 2) return GJ_EUNSUPPORTED;
         if (j->hs[0] == 1 && j->vs[0] == 2) return GJ_EUNSUPPORTED;   /* 4:4:0: Pillow cannot write it, so it cannot be pinned here */
-        if (adobe == 0) j->rgb = 1;
-        else if (adobe == 2) return GJ_EUNSUPPORTED;
+        if (adobe == 2) return GJ_EUNSUPPORTED;
+        if (!jfif) j->rgb = adobe >= 0 ? adobe == 0 : (cid[0] == 'R' && cid[1] == 'G' && cid[2] == 'B');
     } else if (j->hs[0] != 1 || j->vs[0] != 1) {
         j->hs[0] = j->vs[0] = j->hmax = j->vmax = 1;    /* a single-component scan is never interleaved: sampling factors are moot */
     }
@@ -227,72 +245,59 @@ static void restart(Bits* b) {
     b->hit_marker = 0;
 }
 
-/* ---- jidctint.c jpeg_idct_islow ----------------------------------------------------------------------------------- */
+/* ---- jpeg_idct_islow as libjpeg-turbo's SIMD builds compute it (Pillow's decoder) --------------------------------------
+ * jidctint.c's algorithm and constants (CONST_BITS 13, PASS1_BITS 2) in the SIMD form's integer widths:
+ *   - dequantisation is a 16-bit multiply (low 16 bits of coef x quantiser);
+ *   - in0 +- in4, in7 + in3 and in5 + in1 are 16-bit sums (wrapping); products pair up as 16 x 16 -> 32-bit
+ *     multiply-adds; 32-bit sums wrap;
+ *   - pass 1 leaves int16 (saturating pack); a block whose coefficients of rows 1..7 are all zero takes the DC
+ *     shortcut instead, dequantised row 0 << PASS1_BITS in 16 bits (wrapping);
+ *   - pass 2 saturates to -128..127 and adds 128.
+ * For dequantised values an 8-bit encoder writes this is jidctint.c's result; beyond it, it is what Pillow returns. */
 #define CONST_BITS 13
 #define PASS1_BITS 2
-#define DESCALE(x, n) (((x) + (1 << ((n) - 1))) >> (n))
-static inline uint8_t range_limit(int v) {   /* post-IDCT table: index (v & 1023), centred on 128 */
-    const int i = v & 1023;
-    if (i < 128) return (uint8_t)(i + 128);
-    if (i < 512) return 255;
-    if (i < 896) return 0;
-    return (uint8_t)(i - 896);
+static inline int32_t s16(int32_t v) { return (int16_t)(uint16_t)(uint32_t)v; }          /* wrap to int16 */
+static inline int32_t sat16(int32_t v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
+static inline uint8_t out8(int32_t v) { return (uint8_t)(v < -128 ? 0 : (v > 127 ? 255 : v + 128)); }
+/* one 1-D pass on 16-bit inputs: o[0..7] = the 32-bit (wrapped) sums in front of the descale */
+static void idct_1d_s16(const int32_t* in, int step, uint32_t* o) {
+    const int32_t i0 = in[0], i1 = in[step], i2 = in[2 * step], i3 = in[3 * step], i4 = in[4 * step], i5 = in[5 * step],
+                  i6 = in[6 * step], i7 = in[7 * step];
+    const uint32_t e0 = (uint32_t)s16(i0 + i4) << CONST_BITS, e1 = (uint32_t)s16(i0 - i4) << CONST_BITS;
+    const uint32_t e3 = (uint32_t)(i2 * (4433 + 6270)) + (uint32_t)(i6 * 4433);
+    const uint32_t e2 = (uint32_t)(i2 * 4433) + (uint32_t)(i6 * (4433 - 15137));
+    const uint32_t t10 = e0 + e3, t13 = e0 - e3, t11 = e1 + e2, t12 = e1 - e2;
+    const int32_t z3 = s16(i7 + i3), z4 = s16(i5 + i1);
+    const uint32_t Z3 = (uint32_t)(z3 * (9633 - 16069)) + (uint32_t)(z4 * 9633);
+    const uint32_t Z4 = (uint32_t)(z3 * 9633) + (uint32_t)(z4 * (9633 - 3196));
+    const uint32_t T0 = (uint32_t)(i7 * (2446 - 7373)) + (uint32_t)(i1 * -7373) + Z3;
+    const uint32_t T3 = (uint32_t)(i7 * -7373) + (uint32_t)(i1 * (12299 - 7373)) + Z4;
+    const uint32_t T1 = (uint32_t)(i5 * (16819 - 20995)) + (uint32_t)(i3 * -20995) + Z4;
+    const uint32_t T2 = (uint32_t)(i5 * -20995) + (uint32_t)(i3 * (25172 - 20995)) + Z3;
+    o[0] = t10 + T3; o[7] = t10 - T3; o[1] = t11 + T2; o[6] = t11 - T2;
+    o[2] = t12 + T1; o[5] = t12 - T1; o[3] = t13 + T0; o[4] = t13 - T0;
 }
+static inline int32_t descale(uint32_t x, int n) { return (int32_t)(x + (1u << (n - 1))) >> n; }
 static void idct_islow(const int16_t* coef, const uint16_t* q, uint8_t* out, int stride) {
-    int32_t ws[64];
+    int32_t dq[64], ws[64];
+    int ac = 0;
+    for (int i = 0; i < 64; ++i) {
+        dq[i] = s16((int32_t)coef[i] * (int32_t)(int16_t)q[i]);
+        if (i >= 8) ac |= coef[i];
+    }
+    uint32_t o[8];
     for (int c = 0; c < 8; ++c) {
-        int32_t z2 = coef[16 + c] * q[16 + c], z3 = coef[48 + c] * q[48 + c];
-        int32_t z1 = (z2 + z3) * 4433;
-        int32_t tmp2 = z1 + z3 * (-15137), tmp3 = z1 + z2 * 6270;
-        z2 = coef[c] * q[c];
-        z3 = coef[32 + c] * q[32 + c];
-        int32_t tmp0 = (int32_t)((uint32_t)(z2 + z3) << CONST_BITS), tmp1 = (int32_t)((uint32_t)(z2 - z3) << CONST_BITS);
-        const int32_t tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-        tmp0 = coef[56 + c] * q[56 + c];
-        tmp1 = coef[40 + c] * q[40 + c];
-        tmp2 = coef[24 + c] * q[24 + c];
-        tmp3 = coef[8 + c] * q[8 + c];
-        z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2;
-        int32_t z4 = tmp1 + tmp3;
-        const int32_t z5 = (z3 + z4) * 9633;
-        tmp0 *= 2446; tmp1 *= 16819; tmp2 *= 25172; tmp3 *= 12299;
-        z1 *= -7373; z2 *= -20995; z3 *= -16069; z4 *= -3196;
-        z3 += z5; z4 += z5;
-        tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
-        ws[c] = DESCALE(tmp10 + tmp3, CONST_BITS - PASS1_BITS);
-        ws[56 + c] = DESCALE(tmp10 - tmp3, CONST_BITS - PASS1_BITS);
-        ws[8 + c] = DESCALE(tmp11 + tmp2, CONST_BITS - PASS1_BITS);
-        ws[48 + c] = DESCALE(tmp11 - tmp2, CONST_BITS - PASS1_BITS);
-        ws[16 + c] = DESCALE(tmp12 + tmp1, CONST_BITS - PASS1_BITS);
-        ws[40 + c] = DESCALE(tmp12 - tmp1, CONST_BITS - PASS1_BITS);
-        ws[24 + c] = DESCALE(tmp13 + tmp0, CONST_BITS - PASS1_BITS);
-        ws[32 + c] = DESCALE(tmp13 - tmp0, CONST_BITS - PASS1_BITS);
+        if (!ac) {                                          /* DC shortcut: 16-bit shift */
+            for (int r = 0; r < 8; ++r) ws[8 * r + c] = s16(dq[c] * (1 << PASS1_BITS));
+            continue;
+        }
+        idct_1d_s16(dq + c, 8, o);
+        for (int r = 0; r < 8; ++r) ws[8 * r + c] = sat16(descale(o[r], CONST_BITS - PASS1_BITS));
     }
     for (int r = 0; r < 8; ++r) {
-        const int32_t* w = ws + 8 * r;
-        int32_t z2 = w[2], z3 = w[6];
-        int32_t z1 = (z2 + z3) * 4433;
-        int32_t tmp2 = z1 + z3 * (-15137), tmp3 = z1 + z2 * 6270;
-        int32_t tmp0 = (int32_t)((uint32_t)(w[0] + w[4]) << CONST_BITS), tmp1 = (int32_t)((uint32_t)(w[0] - w[4]) << CONST_BITS);
-        const int32_t tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-        tmp0 = w[7]; tmp1 = w[5]; tmp2 = w[3]; tmp3 = w[1];
-        z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2;
-        int32_t z4 = tmp1 + tmp3;
-        const int32_t z5 = (z3 + z4) * 9633;
-        tmp0 *= 2446; tmp1 *= 16819; tmp2 *= 25172; tmp3 *= 12299;
-        z1 *= -7373; z2 *= -20995; z3 *= -16069; z4 *= -3196;
-        z3 += z5; z4 += z5;
-        tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
-        uint8_t* o = out + (size_t)r * stride;
-        const int sh = CONST_BITS + PASS1_BITS + 3;
-        o[0] = range_limit(DESCALE(tmp10 + tmp3, sh));
-        o[7] = range_limit(DESCALE(tmp10 - tmp3, sh));
-        o[1] = range_limit(DESCALE(tmp11 + tmp2, sh));
-        o[6] = range_limit(DESCALE(tmp11 - tmp2, sh));
-        o[2] = range_limit(DESCALE(tmp12 + tmp1, sh));
-        o[5] = range_limit(DESCALE(tmp12 - tmp1, sh));
-        o[3] = range_limit(DESCALE(tmp13 + tmp0, sh));
-        o[4] = range_limit(DESCALE(tmp13 - tmp0, sh));
+        idct_1d_s16(ws + 8 * r, 1, o);
+        uint8_t* d = out + (size_t)r * stride;
+        for (int x = 0; x < 8; ++x) d[x] = out8(descale(o[x], CONST_BITS + PASS1_BITS + 3));
     }
 }
 

@@ -4,6 +4,9 @@
 #include <string.h>
 #include <vector>
 #define GRL_HD
+// restarts entered while gj_fill had stopped on an 0xFF whose marker decision was pending (the RSTn's first byte)
+static int g_restart_ffp = 0;
+#define GJ_RESTART_HOOK(b) (g_restart_ffp += (b).ffp && !(b).marker)
 #include "../grl_amd/csrc/jpeg_core.h"
 #include "../grl_amd/csrc/jpeg_par.h"
 
@@ -11,6 +14,12 @@ static const uint8_t kNat[80] = {
     0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63,
     63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63};
+
+extern "C" int gj_host_restarts_at_pending_ff(int reset) {
+    const int v = g_restart_ffp;
+    if (reset) g_restart_ffp = 0;
+    return v;
+}
 
 static void setup(const GrlJpegFrame* fr, uint16_t* lut, GjScanGeo& g) {
     for (int t = 0; t < 4; ++t)

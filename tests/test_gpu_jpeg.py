@@ -1,6 +1,7 @@
 """Frame decode on the device (grl_jpeg_decode_batch, grl_amd/csrc/jpeg.hip) through the C ABI: bit-identical to Pillow's
 `Image.open(f).convert('RGB')` (/root/reference/reid/data/video_loader.py:124-141), to the committed fixture and to the C
 oracle; batches across workgroup boundaries; the loader -> prefetcher -> extract_features path on real files."""
+import ctypes as C
 import io
 import os
 
@@ -343,3 +344,97 @@ def test_trainer_input_from_jpeg_bytes_with_device_augmentation(tmp_path):
         outs[mode] = (imgs.clone(), pids.clone(), batch[3].clone())
     assert torch.equal(outs['device'][2], outs['host'][2]) and torch.equal(outs['device'][1], outs['host'][1])
     assert outs['device'][0].dtype == torch.float32 and torch.equal(outs['device'][0], outs['host'][0])
+
+
+def _forged_corpus():
+    """every stream of the CPU tests' forged matrix (tests/jpeg_forge.py) that the product parser accepts"""
+    import jpeg_forge as F
+    from grl_amd.reid.data.jpeg import JpegBatch, JpegUnsupported
+    out = []
+    for d in [m[0] for m in F.id_matrix()] + F.restart_streams() + F.edge_streams() + F.qrange_streams():
+        try:
+            JpegBatch([d], (1,)).pack()
+        except JpegUnsupported:
+            continue
+        out.append(d)
+    return out
+
+
+def test_forged_streams_decode_on_the_device_like_pillow():
+    """Selectors, ids and colour spaces, restart intervals ending on a pending 0xFF (the general reader), 16-bit codes,
+    single-symbol tables, DC categories 0..11, coefficients past the 16-bit limits of Pillow's IDCT: bit-identical to Pillow under both entropy
+    decoders (grl_jpeg_parallel_mode 1 / 0)."""
+    from grl_amd import _lib
+    from grl_amd.reid.data.jpeg import decode_jpeg_batch
+    lib = _lib.load()
+    corpus = _forged_corpus()
+    assert len(corpus) > 90
+    want = [_pil_chw(d) for d in corpus]
+    for mode in (1, 0):
+        was = lib.grl_jpeg_parallel_mode(mode)
+        try:
+            for i, d in enumerate(corpus):
+                got = decode_jpeg_batch([d], 'cuda')[0].cpu().numpy()
+                assert np.array_equal(got, want[i]), (mode, i)
+        finally:
+            lib.grl_jpeg_parallel_mode(was)
+    torch.cuda.synchronize()
+
+
+def _padded(data, scan_len):
+    """the stream with 0xFF fill bytes in front of its EOI so that its scan (as grl_jpeg_parse counts it) is scan_len long"""
+    from grl_amd.reid.data.jpeg import JpegBatch
+    f = JpegBatch([data], (1,)).pack()[1][0]
+    extra = scan_len - f.scan_len
+    assert extra >= 0 and data[-2:] == b'\xff\xd9'
+    out = data[:-2] + b'\xff' * extra + b'\xff\xd9'
+    assert JpegBatch([out], (1,)).pack()[1][0].scan_len == scan_len
+    return out
+
+
+def test_entropy_path_boundaries_against_pillow():
+    """grl_jpeg_decode_batch's three entropy paths at their limits: scans of PAR_MAX_SCAN (32704) bytes and one more,
+    8192 blocks (1024 x 512 grey) and more (1024 x 520), a batch of small frames with one frame over the scan limit
+    (the whole batch takes the lane-per-frame path), and one 2048 x 2048 4:2:0 frame (a large frame inside the cap; the
+    64-bit layout of frames near the cap is checked on the host: test_jpeg_cpu.test_oversized_geometry_is_refused_on_the_host)."""
+    from grl_amd.reid.data.jpeg import JpegBatch, decode_jpeg_batch
+    rng = np.random.default_rng(51)
+    par_max_scan = 32768 - 64
+    cases = []
+    noise = _encode(rng.integers(0, 256, (96, 96, 3), dtype=np.uint8), quality=90, subsampling=2)
+    assert JpegBatch([noise], (1,)).pack()[1][0].scan_len < par_max_scan
+    cases.append([_padded(noise, par_max_scan)])
+    cases.append([_padded(noise, par_max_scan + 1)])
+    for h in (512, 520):                                              # (smooth content: a short scan)
+        yy, xx = np.mgrid[0:h, 0:1024]
+        d = _encode((128 + 100 * np.sin(xx / 97.0) * np.cos(yy / 61.0)).astype(np.uint8), quality=60)
+        fr = JpegBatch([d], (1,)).pack()[1][0]
+        assert fr.scan_len < par_max_scan and (h == 512) == (1024 * h // 64 <= 8192)
+        cases.append([d])
+    small = [_encode(rng.integers(0, 256, (96, 96, 3), dtype=np.uint8), quality=int(q), subsampling=2) for q in (30, 60, 85)]
+    cases.append(small + [_padded(noise, par_max_scan + 40)] + small)
+    cases.append([_encode(_frame(2048, 2048, rng), quality=85, subsampling=2)])
+    for streams in cases:
+        got = decode_jpeg_batch(streams, 'cuda').cpu().numpy()
+        for i, s in enumerate(streams):
+            assert np.array_equal(got[i], _pil_chw(s)), (len(streams), i)
+    torch.cuda.synchronize()
+
+
+def test_oversized_geometry_never_reaches_the_device():
+    """A header above the 64 Mpx cap is refused on the host (parser and workspace query) before anything is decoded;
+    decode_jpeg_batch raises JpegUnsupported for it and the device is only then used, for a frame at the cap's side."""
+    from jpeg_forge import with_size
+    from grl_amd import _lib
+    from grl_amd.reid.data.jpeg import JpegUnsupported, decode_jpeg_batch
+    lib = _lib.load()
+    rng = np.random.default_rng(52)
+    base = _encode(_frame(16, 16, rng), quality=80, subsampling=2)
+    for w, h in ((65535, 65535), (38000, 38000), (8192, 8193)):
+        d = with_size(base, w, h)
+        f = _lib.GrlJpegFrame()
+        assert lib.grl_jpeg_parse(d, len(d), 0, C.byref(f)) == _lib.GRL_EUNSUPPORTED
+        with pytest.raises(JpegUnsupported, match='caps'):
+            decode_jpeg_batch([d], 'cuda')
+    ok = _encode(_frame(16, 16, rng), quality=80, subsampling=2)
+    assert np.array_equal(decode_jpeg_batch([ok], 'cuda')[0].cpu().numpy(), _pil_chw(ok))

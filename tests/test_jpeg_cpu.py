@@ -7,6 +7,7 @@ import io
 import numpy as np
 import pytest
 
+import jpeg_forge as F
 from oracle.ref_c import jpeg_decode
 
 
@@ -173,6 +174,8 @@ def test_host_header_parser_survives_mutated_and_truncated_headers(golden):
             assert fr.ncomp in (1, 3) and fr.width and fr.height and fr.hmax in (1, 2) and fr.vmax in (1, 2)
             for c in range(fr.ncomp):
                 assert 1 <= fr.hs[c] <= 2 and 1 <= fr.vs[c] <= 2 and fr.tq[c] <= 3 and fr.td[c] <= 1 and fr.ta[c] <= 1
+            assert fr.width * fr.height <= MAX_PIXELS
+            assert lib.grl_jpeg_workspace_bytes(C.byref(fr), 1) == _layout_bytes([fr])
         return rc
 
     for s in streams:
@@ -182,6 +185,15 @@ def test_host_header_parser_survives_mutated_and_truncated_headers(golden):
             b = bytearray(s)
             for _ in range(int(rng.integers(1, 5))):
                 b[int(rng.integers(2, head))] = int(rng.integers(0, 256))
+            parse(bytes(b))
+    for s in streams:                           # the SOF's width / height fields: anything up to 65535 x 65535
+        i = s.index(b'\xff\xc0')
+        for _ in range(100):
+            w, h = (int(rng.choice([int(rng.integers(1, 65536)), int(rng.integers(1, 9000)), 65535, 8192])) for _ in range(2))
+            parse(F.with_size(s, w, h))
+        b = bytearray(s)
+        for _ in range(100):
+            b[i + 5 + int(rng.integers(0, 4))] = int(rng.integers(0, 256))
             parse(bytes(b))
     s = streams[0]
     assert parse(s) == 0
@@ -431,3 +443,194 @@ def test_parallel_entropy_decoder_emulated_on_the_cpu_matches_the_oracle(tmp_pat
                 rounds.append(r)
             n += 1
     assert n > 400 and rounds and max(rounds) < 256           # (4-6 rounds for quality-90 MARS frames; quality 100 needs up to ~40)
+
+
+# ---- forged streams (tests/jpeg_forge.py): what Pillow's encoder never writes -----------------------------------------
+# Pillow decides: the oracle's pixels must equal `Image.open(f).convert('RGB')`, the device core's coefficients the oracle's.
+
+def _host_core(tmp_path):
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    so = os.path.join(str(tmp_path), 'libgjhost.so')
+    subprocess.check_call(['g++', '-O2', '-shared', '-fPIC', os.path.join(root, 'tests', 'jpeg_core_host.cpp'), '-o', so])
+    lib = C.CDLL(so)
+    for fn in (lib.gj_host_decode, lib.gj_host_decode_clean):
+        fn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.gj_host_decode_par.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    lib.gj_host_restarts_at_pending_ff.argtypes = [C.c_int]
+    return lib
+
+
+def _core_matches_oracle(lib, data, leads=(0,)):
+    """every reader of the device core (general, clean, parallel emulation) leaves the oracle's coefficients"""
+    from grl_amd.reid.data.jpeg import JpegBatch
+    from oracle.ref_c import jpeg_coefficients
+    ref = jpeg_coefficients(data)
+    for lead in leads:
+        host, fr = JpegBatch([data], (1,)).pack()
+        buf = np.ascontiguousarray(np.concatenate([np.full(lead, 0xFF, np.uint8), host.numpy(), np.zeros(8, np.uint8)]))
+        f = fr[0]
+        f.scan_off += lead
+        fns = [lib.gj_host_decode] if f.restart_interval else [lib.gj_host_decode, lib.gj_host_decode_clean]
+        for fn in fns:
+            out = np.full_like(ref, 7)
+            fn(buf.ctypes.data, len(buf) - 8, C.addressof(f), out.ctypes.data)
+            assert np.array_equal(out, ref), (fn, lead)
+        if not f.restart_interval:
+            out = np.full_like(ref, 7)
+            lib.gj_host_decode_par(buf.ctypes.data, len(buf) - 8, C.addressof(f), out.ctypes.data, 7, 32)
+            assert np.array_equal(out, ref), ('par', lead)
+    return ref
+
+
+def test_forger_streams_decode_to_the_blocks_it_was_given():
+    """tests/jpeg_forge.py itself: on ordinary streams it writes (Annex K tables, JFIF, all four samplings, restart
+    intervals with fill bytes) the oracle returns the blocks the forger was given, and Pillow the oracle's pixels."""
+    from oracle.ref_c import jpeg_coefficients
+    rng = np.random.default_rng(40)
+    n = 0
+    for layout in F.LAYOUTS:
+        for (w, h) in ((8, 8), (33, 17), (48, 32), (5, 19)):
+            comps = F.comps_for(layout)
+            co = F.random_coefs(rng, w, h, comps)
+            dc, ac = F.std_tables(len(comps))
+            for rst, fill in ((0, 0), (1, 0), (2, 3)):
+                d = F.forge(w, h, comps, co, F.std_q(len(comps)), dc, ac, restart=rst, fill=fill)
+                assert np.array_equal(jpeg_coefficients(d), F.mcu_blocks(co, comps, w, h)), (layout, w, h, rst)
+                assert np.array_equal(jpeg_decode(d), _pil(d)), (layout, w, h, rst)
+                n += 1
+    assert n == 48
+
+
+def test_restart_after_a_pending_ff_byte(tmp_path):
+    """gj_restart when gj_fill stopped on the RSTn's 0xFF as the last byte of a dword (ffp pending): the general reader
+    must find that marker, not the next one.  The corpus reaches that state several times (counted by the CPU build),
+    the core's coefficients equal the oracle's at every buffer alignment, and the oracle's pixels equal Pillow's."""
+    lib = _host_core(tmp_path)
+    lib.gj_host_restarts_at_pending_ff(1)
+    for d in F.restart_streams():
+        _core_matches_oracle(lib, d, leads=(0, 1, 2, 3))
+        assert np.array_equal(jpeg_decode(d), _pil(d))
+    assert lib.gj_host_restarts_at_pending_ff(0) >= 4
+
+
+def test_scan_selectors_component_ids_and_colour_space_follow_pillow():
+    """SOS selectors map to SOF components by id (td / ta taken per component), libjpeg's colour-space rule (JFIF ->
+    YCbCr; else Adobe transform 0 -> RGB, 1 -> YCbCr; else ids R, G, B -> RGB; else YCbCr).  Every stream is either
+    accepted by the product parser with Pillow's colour space and decoded by the oracle to Pillow's pixels, or refused by
+    both with GRL_EUNSUPPORTED (a scan listing the components in another order than the frame)."""
+    from grl_amd import _lib
+    from grl_amd.reid.data.jpeg import JpegBatch, JpegUnsupported
+    n_ok = n_refused = 0
+    for d, rgb, perm, key in F.id_matrix():
+        if perm:
+            with pytest.raises(JpegUnsupported, match='order'):
+                JpegBatch([d], (1,)).pack()
+            with pytest.raises(ValueError, match=r'\(-2\)'):
+                jpeg_decode(d)
+            n_refused += 1
+            continue
+        _, fr = JpegBatch([d], (1,)).pack()
+        assert fr[0].rgb == rgb, key
+        assert np.array_equal(jpeg_decode(d), _pil(d)), key
+        n_ok += 1
+    assert n_ok == 36 and n_refused == 36
+    lib = _lib.load()
+    d = F.id_matrix()[0][0]
+    i = d.index(b'\xff\xda')
+    bad = bytearray(d)
+    bad[i + 5] = 99                                           # a selector that names no component
+    f = _lib.GrlJpegFrame()
+    assert lib.grl_jpeg_parse(bytes(bad), len(bad), 0, C.byref(f)) == _lib.GRL_EINVAL
+
+
+def test_huffman_and_coefficient_edges_agree_everywhere(tmp_path):
+    """DC categories 0..11, ZRL runs, EOB at k = 63 and none after k = 63, 16-bit codes (the canonical-search fallback
+    of both readers), single-symbol tables: the device core (general / clean / parallel readers on the CPU) leaves the
+    oracle's coefficients, and the oracle's pixels are Pillow's."""
+    lib = _host_core(tmp_path)
+    streams = F.edge_streams()
+    for d in streams:
+        _core_matches_oracle(lib, d, leads=(0, 3))
+        assert np.array_equal(jpeg_decode(d), _pil(d))
+    assert len(streams) == 16
+
+
+def test_quantisation_range_follows_pillow_past_16_bit_limits_and_16_bit_tables_are_refused():
+    """8-bit quantisers up to 255 with coefficients past every 16-bit limit of libjpeg-turbo's SIMD IDCT (wrapping
+    dequantisation, a DC shortcut whose << 2 wraps, saturating pass-1 packs): the oracle -- the device IDCT's arithmetic --
+    returns Pillow's pixels, and the parser accepts the streams.  16-bit quantisers (Pq = 1; T.81 allows them with 12-bit
+    samples only) are refused by parser and oracle."""
+    from grl_amd.reid.data.jpeg import JpegBatch, JpegUnsupported
+    for d in F.qrange_streams():
+        assert np.array_equal(jpeg_decode(d), _pil(d))
+        JpegBatch([d], (1,)).pack()
+    rng = np.random.default_rng(44)
+    comps = F.comps_for('grey')
+    dc, ac = F.std_tables(1)
+    for qv in (1, 255, 256, 40000):
+        co = F.random_coefs(rng, 16, 16, comps, amp=8)
+        d = F.forge(16, 16, comps, co, {0: np.full(64, qv)}, dc, ac, pq={0: 1})
+        with pytest.raises(JpegUnsupported, match='16-bit quantisation'):
+            JpegBatch([d], (1,)).pack()
+        with pytest.raises(ValueError, match=r'\(-2\)'):
+            jpeg_decode(d)
+
+
+# ---- geometry caps (host only: nothing here reaches a device) -------------------------------------------------------
+MAX_PIXELS = 64 << 20
+
+
+def _layout_bytes(frames):
+    """grl_jpeg_workspace_bytes recomputed with Python integers (jpeg.hip make_geo / make_layout)"""
+    f = frames[0]
+    n = len(frames)
+    hv = [(f.hs[c], f.vs[c]) for c in range(f.ncomp)]
+    mcux, mcuy = -(-f.width // (8 * f.hmax)), -(-f.height // (8 * f.vmax))
+    off = sum(mcux * h * 8 * mcuy * v * 8 for h, v in hv)
+    blocks = mcux * mcuy * sum(h * v for h, v in hv)
+    plane_bytes = (off + 15) // 16 * 16
+    nbytes = max(fr.scan_off + fr.scan_len for fr in frames)
+    up = lambda v: (v + 255) // 256 * 256                                   # noqa: E731
+    lut_per_set = 2 * 512 + 2 * 4096
+    return up(n * blocks * 128) + up(n * plane_bytes) + up(n * lut_per_set * 2) + up(nbytes + 32) + up(n * 4)
+
+
+def test_oversized_geometry_is_refused_on_the_host():
+    """Headers up to 65535 x 65535 (grey, 4:4:4, 4:2:0) and sizes on both sides of the 64 Mpx cap through
+    grl_jpeg_parse, grl_jpeg_parse_batch and grl_jpeg_workspace_bytes: above the cap GRL_EUNSUPPORTED, at or below it a
+    workspace size equal to the layout recomputed with Python integers (no 32-bit wrap)."""
+    from grl_amd import _lib
+    lib = _lib.load()
+    rng = np.random.default_rng(45)
+    sizes = [(65535, 65535, False), (65535, 1024, True), (65535, 1025, False), (8192, 8192, True), (8192, 8193, False),
+             (8193, 8192, False), (1024, 65535, True), (38000, 38000, False), (4096, 16384, True), (4097, 16384, False)]
+    n = 0
+    for layout in ('grey', '444', '420'):
+        comps = F.comps_for(layout)
+        dc, ac = F.std_tables(len(comps))
+        base = F.forge(16, 16, comps, F.random_coefs(rng, 16, 16, comps), F.std_q(len(comps)), dc, ac)
+        for w, h, ok in sizes:
+            d = F.with_size(base, w, h)
+            f = _lib.GrlJpegFrame()
+            rc = lib.grl_jpeg_parse(d, len(d), 0, C.byref(f))
+            buf = np.frombuffer(d + d, np.uint8).copy()
+            offs = np.array([0, len(d), 2 * len(d)], np.int64)
+            frames = (_lib.GrlJpegFrame * 2)()
+            bad = C.c_int(-1)
+            rcb = lib.grl_jpeg_parse_batch(buf.ctypes.data, offs.ctypes.data, 2, frames, C.addressof(bad))
+            if not ok:
+                assert rc == _lib.GRL_EUNSUPPORTED and rcb == _lib.GRL_EUNSUPPORTED and bad.value == 0, (layout, w, h)
+                continue
+            assert rc == 0 and rcb == 0 and (f.width, f.height) == (w, h), (layout, w, h)
+            assert w * h <= MAX_PIXELS
+            ws = lib.grl_jpeg_workspace_bytes(frames, 2)
+            assert ws == _layout_bytes(frames) and ws > 2 * w * h, (layout, w, h, ws)
+            n += 1
+            # a descriptor pushed over the cap after parsing: the workspace query refuses it too
+            over = (_lib.GrlJpegFrame * 1)()
+            C.memmove(over, frames, C.sizeof(_lib.GrlJpegFrame))
+            over[0].width, over[0].height = 65535, 65535
+            assert lib.grl_jpeg_workspace_bytes(over, 1) == _lib.GRL_EUNSUPPORTED
+    assert n == 12
