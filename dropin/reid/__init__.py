@@ -5,7 +5,7 @@ import sys
 
 import grl_amd.reid as _impl
 
-for _name in ('models', 'evaluator', 'train', 'loss', 'data'):
+for _name in ('models', 'evaluator', 'train', 'loss', 'data', 'dataset'):
     try:
         _m = importlib.import_module('grl_amd.reid.' + _name)
     except ImportError:          # sub-package not provided (yet)
@@ -15,7 +15,7 @@ for _name in ('models', 'evaluator', 'train', 'loss', 'data'):
 
 # sub-modules callers import by path: ONE module object under both names, so that classes
 # (e.g. reid.data.jpeg.JpegBatch) are the ones grl_amd itself checks with isinstance
-for _sub in ('data.augment', 'data.jpeg'):
+for _sub in ('data.augment', 'data.jpeg', 'data.sampler'):
     try:
         sys.modules['reid.' + _sub] = importlib.import_module('grl_amd.reid.' + _sub)
     except ImportError:

@@ -17,7 +17,7 @@ import torch
 from grl_amd import _lib
 from grl_amd._lib import GrlHipError, GrlJpegFrame
 
-__all__ = ['JpegUnsupported', 'JpegBatch', 'decode_jpeg_batch', 'jpeg_collate', 'read_file']
+__all__ = ['JpegUnsupported', 'JpegFile', 'JpegBatch', 'decode_jpeg_batch', 'jpeg_collate', 'read_file']
 
 
 class JpegUnsupported(GrlHipError):
@@ -25,7 +25,20 @@ class JpegUnsupported(GrlHipError):
     16-bit quantisers, frames above 64 Mpx ...)."""
 
 
-def read_file(path):
+class JpegFile(bytes):
+    """The bytes of one frame file together with its ``path``: a batch built from these names the FILE of a stream the
+    device decoder refuses (``read_file(path, keep_path=True)``; RawVideoDataset(decode='device') yields them)."""
+
+    def __new__(cls, data, path):
+        self = super(JpegFile, cls).__new__(cls, data)
+        self.path = path
+        return self
+
+    def __reduce__(self):           # (loader workers hand batches over by pickle)
+        return JpegFile, (bytes(self), self.path)
+
+
+def read_file(path, keep_path=False):
     """The bytes of one frame file.  A file whose scan is not closed by an EOI marker raises OSError like the reference's
     `Image.open(path).convert('RGB')` does ("image file is truncated": Pillow runs libjpeg with a suspending source,
     which never reaches the end of such an image) -- the device decoder itself follows libjpeg's rule for damaged data
@@ -34,7 +47,7 @@ def read_file(path):
         data = fh.read()
     if data[:2] == b'\xff\xd8' and data.rfind(b'\xff\xd9') < data.rfind(b'\xff\xda'):
         raise OSError('image file is truncated (no EOI marker behind the scan): %s' % path)
-    return data
+    return JpegFile(data, path) if keep_path else data
 
 
 class JpegBatch(object):
@@ -81,10 +94,16 @@ class JpegBatch(object):
         rc = lib.grl_jpeg_parse_batch(buf.ctypes.data, offs.ctypes.data, n, frames, C.addressof(bad))   # headers + table sets: one call
         if rc:
             msg = lib.grl_last_error().decode('utf-8', 'replace')
+            path = getattr(self.streams[bad.value], 'path', None) if 0 <= bad.value < n else None
             if 0 <= bad.value < n and self.streams[bad.value][:8] == b'\x89PNG\r\n\x1a\n':
                 # iLIDS-VID / PRID 2011 ship PNG frames (ilidsvidsequence.py:113): inflate is not on the device
-                raise JpegUnsupported("frame %d is a PNG file: the device decoder covers baseline JPEG (MARS, DukeMTMC-"
-                                      "VideoReID); load this dataset with RawVideoDataset(decode='host')" % bad.value)
+                raise JpegUnsupported("frame %d%s is a PNG file: the device decoder covers baseline JPEG (MARS, DukeMTMC-"
+                                      "VideoReID); load this dataset with RawVideoDataset(decode='host')"
+                                      % (bad.value, " ('%s')" % path if path else ''))
+            if path is not None and rc == _lib.GRL_EUNSUPPORTED:
+                # a frame of a file-backed loader: name the file and the Pillow path (get_data: GRL_DECODE=host)
+                raise JpegUnsupported("frame %d ('%s'): %s -- decode this dataset on the host: GRL_DECODE=host for "
+                                      "get_data, RawVideoDataset(decode='host') otherwise" % (bad.value, path, msg))
             raise (JpegUnsupported if rc == _lib.GRL_EUNSUPPORTED else GrlHipError)('frame %d: %s' % (bad.value, msg))
         return host, frames
 

@@ -7,7 +7,12 @@ ms per iteration = (time of 70 iterations - time of 10) / 60.
 
 `--mode eval`: ATTEvaluator.extract_feature(loader) -- the evaluator's own loop -- over 60 batches, clip-features/s.
 
-  python tools/loop_rate.py [--mode train|eval] [--math bf16s] [--clips 32] [--seq-len 4]
+`--mars DIR` (train): the loop fed by get_data('mars', data_dir=DIR)'s train loader instead -- RawVideoDataset workers
+reading the JPEG files, the pair sampler, device decode + augmentation -- with `--workers` loader processes.  A DIR
+without a MARS layout is first filled with a generated tree (tests/dataset_tree.py: 625 pids x 4 tracklets of ~60
+frames, hard links to a pool of distinct frames).
+
+  python tools/loop_rate.py [--mode train|eval] [--math bf16s] [--clips 32] [--seq-len 4] [--mars DIR --workers 8]
 """
 import argparse
 import contextlib
@@ -24,6 +29,33 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
+
+
+class FirstBatches(object):
+    """a loader: the first n batches of a DataLoader (a fresh pass each time: the workers start again)"""
+
+    def __init__(self, loader, n):
+        self.loader, self.n = loader, n
+
+    def __len__(self):
+        return self.n
+
+    def __iter__(self):
+        import itertools
+        return itertools.islice(iter(self.loader), self.n)
+
+
+def mars_train_loader(path, batch, seq_len, workers):
+    """get_data('mars')'s train loader on ``path`` (a generated tree when it has no MARS layout yet)"""
+    if not os.path.isdir(os.path.join(path, 'info')):
+        sys.path.insert(0, os.path.join(ROOT, 'tests'))
+        import dataset_tree
+        test = [(p, c, 30) for p in range(2, 40, 2) for c in (1, 2)]
+        dataset_tree.make_mars_tree(path, train=dataset_tree.synthetic_mars_spec(625, 4, 60), test=test,
+                                    query=list(range(1, len(test) + 1, 2)), pool=512)
+    from grl_amd.reid.data import get_data
+    with contextlib.redirect_stdout(io.StringIO()):
+        return get_data('mars', 0, path, batch, seq_len, 4, workers)[2]
 
 
 class Batches(object):
@@ -47,6 +79,8 @@ def main():
     ap.add_argument('--seq-len', type=int, default=4)
     ap.add_argument('--dense', type=int, default=0, help='--mode eval: dense mode (test_all.py), this many clips per tracklet, one tracklet per batch')
     ap.add_argument('--clips', type=int, default=32)
+    ap.add_argument('--mars', default=None, help='--mode train: feed the loop from get_data(\'mars\') on this tree')
+    ap.add_argument('--workers', type=int, default=8)
     a = ap.parse_args()
     import decode_rate
     from grl_amd import train_engine
@@ -116,11 +150,15 @@ def main():
         print(json.dumps(out))
         return
     out = {"mode": "train", "math": a.math, "clips": B, "frames_per_clip": T, "loop": "SEQTrainer.train (meters read one step late; GRL_LAZY_METERS=0: loss.item() per step as upstream)"}
+    if a.mars:
+        loader = mars_train_loader(a.mars, B, T, a.workers)
+        feeds = {"get_data('mars') train loader, %d workers (device decode + augmentation)" % a.workers: loader}
+        out["train_tracklets"] = len(loader.dataset)
     for name, rows in feeds.items():
         def run(n):
             with contextlib.redirect_stdout(io.StringIO()):
                 t0 = time.perf_counter()
-                tr.train(0, Batches(rows, n), opt)
+                tr.train(0, FirstBatches(rows, n) if a.mars else Batches(rows, n), opt)
                 torch.cuda.synchronize()
                 return time.perf_counter() - t0
         run(10)
