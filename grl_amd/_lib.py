@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GRL_HIP_LIB') or os.path.join(_HERE, 'libgrl_hip.so')     # (override: A/B builds, tools/gemm_ko.sh)
 
-ABI_VERSION = 9       # = GRL_ABI_VERSION of include/grl_hip.h this binding was written against
+ABI_VERSION = 10      # = GRL_ABI_VERSION of include/grl_hip.h this binding was written against
 
 EPI_AFFINE, EPI_NEGDOT, EPI_EUCLID, EPI_SQDIFF = 0, 1, 2, 3
 
@@ -31,7 +31,7 @@ class GrlGemm(C.Structure):
                [(n, _fp) for n in ('bn_z', 'bn_mean', 'bn_invstd', 'bn_mscale', 'bn_mbeta', 'bn_bits')]
 
 
-MATH_F32, MATH_BF16, MATH_BF16X3, MATH_BF16S = 0, 1, 3, 2
+MATH_F32, MATH_BF16, MATH_BF16X3, MATH_BF16S, MATH_MXFP8 = 0, 1, 3, 2, 4
 
 
 class GrlWgrad(C.Structure):
@@ -78,6 +78,11 @@ _SIGNATURES = {
     'grl_gemm_force_tile': ([C.c_int, C.c_int], C.c_int),
     'grl_conv_gemm_f32_workspace_floats': ([C.POINTER(GrlGemm)], _i64),
     'grl_gemm_bf16_tile_mode': ([C.c_int], C.c_int),
+    'grl_mx_pack_weights': ([_fp, C.c_int, C.c_int, C.c_int, _fp, _fp], C.c_int),
+    'grl_mx_quantize_rows': ([_fp, C.c_int, C.c_int, C.c_int, _fp, _fp], C.c_int),
+    'grl_mx_image_bytes': ([C.c_int, C.c_int], _i64),
+    'grl_mx_e4m3_host': ([C.c_int, C.c_int], C.c_int),
+    'grl_mx_block_exp_host': ([C.c_int], C.c_int),
     'grl_pack_conv_weight': ([_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp], C.c_int),
     'grl_bn_fold': ([_fp, _fp, _fp, _fp, _fp, C.c_float, _fp, _fp, C.c_int, _fp], C.c_int),
     'grl_stem_conv7x7': ([_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp], C.c_int),

@@ -1692,12 +1692,14 @@ extern "C" int grl_conv_gemm_f32_stat_rows(const GrlGemm* desc) {
 int grl_gemm_validate(const GrlGemm& d) { return validate(d); }      // (common.h: the grouped entry point checks every descriptor)
 
 extern "C" int64_t grl_conv_gemm_f32_workspace_floats(const GrlGemm* desc) {
+    if (desc && desc->math == GRL_MATH_MXFP8) return grl_gemm_mxfp8_workspace_floats(*desc);     // (the activations' MX image)
     return desc ? splitk_floats(*desc) : 0;
 }
 
 extern "C" int grl_conv_gemm_f32(const GrlGemm* desc, void* stream) {
     if (!desc) return grl_fail(GRL_EINVAL, "null desc");
     const GrlGemm& d = *desc;
+    if (d.math == GRL_MATH_MXFP8) return grl_gemm_mxfp8(d, (hipStream_t)stream);     // gemm_mxfp8.hip (its own checks)
     if (int e = validate(d)) return e;
     hipStream_t s = (hipStream_t)stream;
     if (const int64_t need = splitk_floats(d); need > 0 && d.splitk_ws && d.splitk_ws_floats >= need &&

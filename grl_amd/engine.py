@@ -25,7 +25,7 @@ from ._lib import GrlGemm, GrlBneckTail, GrlBneckTailF32, EPI_AFFINE, EPI_NEGDOT
 import contextlib
 import os
 
-from ._lib import MATH_F32, MATH_BF16, MATH_BF16X3, MATH_BF16S
+from ._lib import MATH_F32, MATH_BF16, MATH_BF16X3, MATH_BF16S, MATH_MXFP8
 
 _MATH_NAMES = {'f32': MATH_F32, 'bf16': MATH_BF16, 'bf16x3': MATH_BF16X3, 'bf16s': MATH_BF16S}
 # Multiplier datapath of the conv / linear GEMMs (accumulation is always fp32):
@@ -35,6 +35,13 @@ _MATH_NAMES = {'f32': MATH_F32, 'bf16': MATH_BF16, 'bf16x3': MATH_BF16X3, 'bf16s
 #   'bf16s'  bf16 STORAGE: activations and weights are bf16 in HBM from the stem to the TRL
 #            memo (BASELINE configs[2] pipeline); per-clip vectors and the tail stay fp32.
 # The evaluator distance matrices always use 'f32' (bit-exact ranking contract).
+#
+# EXPERIMENTAL, not a user mode: 'mxfp8' = the 'bf16s' pipeline with its generic conv / linear GEMMs on MX-FP8 operands
+# (e4m3 elements, one power-of-two scale per 32 k: include/grl_hip.h "MX-FP8 datapath"; the fused bf16 kernels, the
+# fp32 per-clip linears and the tail stay as in 'bf16s').  It is measured SLOWER than 'bf16s' (EXPERIMENTS.md,
+# 'MX-FP8 eval datapath') and less accurate, so set_math / math_mode / GRL_MATH do not accept it; the tests and
+# tools/mxfp8_rate.py reach it through experimental_math('mxfp8').  Eval only: train_engine refuses it.
+_EXPERIMENTAL_MATH = {'mxfp8': MATH_MXFP8}
 _math = [_MATH_NAMES[os.environ.get('GRL_MATH', 'f32')]]
 
 
@@ -43,7 +50,19 @@ def set_math(name):
 
 
 def get_math():
-    return {v: k for k, v in _MATH_NAMES.items()}[_math[0]]
+    return {v: k for k, v in list(_MATH_NAMES.items()) + list(_EXPERIMENTAL_MATH.items())}[_math[0]]
+
+
+@contextlib.contextmanager
+def experimental_math(name):
+    """Run the enclosed eval calls on an experimental datapath (only 'mxfp8' today; see above) -- for measurement
+    and tests, not a supported mode."""
+    old = _math[0]
+    _math[0] = _EXPERIMENTAL_MATH[name]
+    try:
+        yield
+    finally:
+        _math[0] = old
 
 
 @contextlib.contextmanager
@@ -166,10 +185,15 @@ def gemm(a, w, y, M, N, K, lda=0, ldw=None, ldy=None, scale=None, shift=None, re
     d = GrlGemm(ptr(a), ptr(w), ptr(y), ptr(scale), ptr(shift), ptr(res), ptr(gbias), ptr(rowscale), ptr(rnorm), ptr(cnorm),
                 ptr(stats), M, N, K, lda or K, ldw or K, ldy or N, ldres or N, rows_per_group, 1 if relu else 0, epilogue,
                 cv[0], cv[1], cv[2], cv[3], cv[4], cv[5], cv[6], cv[7], cv[8], cv[9],
-                (MATH_F32 if _math[0] == MATH_BF16S else _math[0]) if math is None else math, 1 if out_f32 else 0,
+                (MATH_F32 if _math[0] in (MATH_BF16S, MATH_MXFP8) else _math[0]) if math is None else math, 1 if out_f32 else 0,
                 res_rows, res_gstride, 1 if kblock else 0, None, 0, *bnp)
     lib = _lib.load()
-    if SPLITK and kblock and conv is None and M <= 256 and K > 512:      # skinny K-blocked GEMM: split-K scratch (include/grl_hip.h)
+    if d.math == MATH_MXFP8:                  # the activations' MX image (include/grl_hip.h: required scratch)
+        need = lib.grl_conv_gemm_f32_workspace_floats(C.byref(d))
+        if need > 0:
+            ws = torch.empty(need, dtype=torch.float32, device=y.device)
+            d.splitk_ws, d.splitk_ws_floats = ptr(ws), need
+    elif SPLITK and kblock and conv is None and M <= 256 and K > 512:      # skinny K-blocked GEMM: split-K scratch (include/grl_hip.h)
         need = lib.grl_conv_gemm_f32_workspace_floats(C.byref(d))
         if need > 0:
             ws = torch.empty(need, dtype=torch.float32, device=y.device)
@@ -214,7 +238,7 @@ def gemm_group(calls):
         d.relu = 1 if c.get('relu') else 0
         d.epilogue = EPI_AFFINE
         m = c.get('math')
-        d.math = (MATH_F32 if _math[0] == MATH_BF16S else _math[0]) if m is None else m
+        d.math = (MATH_F32 if _math[0] in (MATH_BF16S, MATH_MXFP8) else _math[0]) if m is None else m
     check(_lib.load().grl_conv_gemm_f32_group(arr, n, _lib.stream()), 'grl_conv_gemm_f32_group')
     if _DEBUG_SYNC:
         _debug_sync('gemm_group x%d %s' % (n, (calls[0]['M'], calls[0]['N'], calls[0]['K'])))
@@ -239,7 +263,7 @@ def _kb():
     frames, K = 1024..2048) accumulate K-BLOCKED in the exact-fp32 datapath: their 512-k segments then run as separate
     workgroups (GrlGemm.splitk_ws) instead of one workgroup per tile walking all of K -- 55 -> ~15 us each -- and the
     result does not depend on whether the library splits (M <= 256) or not: a clip's row stays batch-independent."""
-    return _math[0] in (MATH_F32, MATH_BF16S)
+    return _math[0] in (MATH_F32, MATH_BF16S, MATH_MXFP8)
 
 
 def _call(name, *args):
@@ -258,7 +282,7 @@ def _call(name, *args):
 # ----------------------------------------------------------------------------
 class _Conv(object):
     """A conv (or linear) with its eval-folded affine."""
-    __slots__ = ('w', 'N', 'K', 'ldw', 'scale', 'shift', 'k', 'stride', 'cin', '_wb', '_wperm')
+    __slots__ = ('w', 'N', 'K', 'ldw', 'scale', 'shift', 'k', 'stride', 'cin', '_wb', '_wperm', '_wmx')
 
     def wb(self):
         """bf16 copy of the packed weight (bf16-storage pipeline), made on first use."""
@@ -267,6 +291,18 @@ class _Conv(object):
             self._wb = torch.empty(w.shape, dtype=torch.bfloat16, device=w.device)
             _call('grl_cast_bf16', ptr(w), ptr(self._wb), w.numel())
         return self._wb
+
+    def wmx(self, K=None):
+        """MX-FP8 image of the packed weight's first ``K`` (default all) columns (grl_mx_pack_weights; the
+        'mxfp8' datapath), made on first use.  The plan is rebuilt when the module's state changes, so is this."""
+        K = K or self.K
+        if getattr(self, '_wmx', None) is None or self._wmx[0] != K:
+            w = self.w.contiguous()
+            ldw = w.shape[1]
+            img = torch.empty(_lib.load().grl_mx_image_bytes(self.N, K), dtype=torch.uint8, device=w.device)
+            _call('grl_mx_pack_weights', ptr(w), self.N, K, ldw, ptr(img))
+            self._wmx = (K, img)
+        return self._wmx[1]
 
     def wperm(self):
         """bf16 copy of a 1x1 weight [N][K] in the k order the chained MFMA of grl_bottleneck_tail_bf16 consumes
@@ -321,6 +357,7 @@ class EvalPlan(object):
         c = _Conv()
         c._wb = None
         c._wperm = None
+        c._wmx = None
         w = conv.weight.detach()
         c.N, c.cin = w.shape[0], w.shape[1]
         c.k = w.shape[2] if w.dim() == 4 else 1
@@ -704,8 +741,8 @@ def trl_eval(plan, xu, xc, b, t, taps=None):
 
 
 def _grl_eval(model, inputs, taps=None, out_uncorr=None, ld_uncorr=2048):
-    if _math[0] == MATH_BF16S:
-        return _grl_eval_bf16s(model, inputs, taps, out_uncorr, ld_uncorr)
+    if _math[0] in (MATH_BF16S, MATH_MXFP8):
+        return _grl_eval_bf16s(model, inputs, taps, out_uncorr, ld_uncorr, dp=_math[0])
     plan = _plan(model, GrlEvalPlan)
     b, t, c, h, w = inputs.shape
     if (c, h, w) != (3, 256, 128):
@@ -743,22 +780,28 @@ def conv3x3_c64_bf16(x, c, n_img, H, W, relu=True):
     return y
 
 
-def _conv_b16(x, c, n_img, H, W, stride=1, relu=True, res=None, **kw):
+def _gw(c, dp, K=None):
+    """(weight, math) of a generic bf16-storage GEMM on datapath ``dp`` (MATH_BF16S or MATH_MXFP8)"""
+    return (c.wmx(K), MATH_MXFP8) if dp == MATH_MXFP8 else (c.wb(), MATH_BF16S)
+
+
+def _conv_b16(x, c, n_img, H, W, stride=1, relu=True, res=None, dp=MATH_BF16S, **kw):
     if (FUSE_C64 and c.k == 3 and stride == 1 and c.cin == 64 and c.N == 64 and W == 32 and H % 8 == 0 and res is None
             and not kw and n_img * H * W * 128 < (1 << 32)):          # (32-bit byte offsets inside that kernel)
         return conv3x3_c64_bf16(x, c, n_img, H, W, relu), H, W
+    wt, m = _gw(c, dp)
     if c.k == 1 and stride == 1:
         M = n_img * H * W
         y = _newb((M, c.N), x)
-        gemm(x, c.wb(), y, M, c.N, c.K, ldw=c.ldw, scale=c.scale, shift=c.shift, res=res, relu=relu,
-             math=MATH_BF16S, **kw)
+        gemm(x, wt, y, M, c.N, c.K, ldw=c.ldw, scale=c.scale, shift=c.shift, res=res, relu=relu,
+             math=m, **kw)
         return y, H, W
     pad = c.k // 2
     Ho, Wo = (H + 2 * pad - c.k) // stride + 1, (W + 2 * pad - c.k) // stride + 1
     M = n_img * Ho * Wo
     y = _newb((M, c.N), x)
-    gemm(x, c.wb(), y, M, c.N, c.K, ldw=c.ldw, scale=c.scale, shift=c.shift, res=res, relu=relu,
-         conv=(H, W, c.cin, Ho, Wo, c.k, c.k, stride, pad), math=MATH_BF16S, **kw)
+    gemm(x, wt, y, M, c.N, c.K, ldw=c.ldw, scale=c.scale, shift=c.shift, res=res, relu=relu,
+         conv=(H, W, c.cin, Ho, Wo, c.k, c.k, stride, pad), math=m, **kw)
     return y, Ho, Wo
 
 
@@ -827,10 +870,12 @@ def bneck_tail_f32(t2, c3, res, c1n, M):
     return y, u
 
 
-def _grl_eval_bf16s(model, inputs, taps=None, out_uncorr=None, ld_uncorr=2048):
+def _grl_eval_bf16s(model, inputs, taps=None, out_uncorr=None, ld_uncorr=2048, dp=MATH_BF16S):
     """Same launch order as _grl_eval with bf16 activations in HBM: stem -> trunk -> GCE ->
     TRL memo are bf16 tensors, every GEMM is the bf16-storage datapath, reductions land in
-    fp32 vectors, the BN1d + L2 tail is the fp32 one."""
+    fp32 vectors, the BN1d + L2 tail is the fp32 one.  ``dp`` = MATH_MXFP8: the generic conv / linear GEMMs
+    (those issued through gemm() with a bf16-storage weight) run on MX-FP8 operands instead; the fused kernels and
+    the fp32 per-clip linears do not change, and the TRL f1 GEMM takes the unfused squared-difference route."""
     plan = _plan(model, GrlEvalPlan)
     b, t, c, h, w = inputs.shape
     if (c, h, w) != (3, 256, 128):
@@ -862,8 +907,8 @@ def _grl_eval_bf16s(model, inputs, taps=None, out_uncorr=None, ld_uncorr=2048):
             _stage('layer%d' % ((0, 3, 7, 13).index(bi) + 1))
         s = e['stride']
         if o1 is None:
-            o1, _, _ = _conv_b16(cur, e['c1'], n, H, W)
-        o2, Ho, Wo = _conv_b16(o1, e['c2'], n, H, W, stride=s)
+            o1, _, _ = _conv_b16(cur, e['c1'], n, H, W, dp=dp)
+        o2, Ho, Wo = _conv_b16(o1, e['c2'], n, H, W, stride=s, dp=dp)
         nxt = plan.blocks[bi + 1]['c1'] if bi + 1 < len(plan.blocks) else None
         fuse = FUSE_BNECK and nxt is not None and _bneck_tail_ok(e['c3'], nxt, n * Ho * Wo)
         o1 = None
@@ -871,13 +916,13 @@ def _grl_eval_bf16s(model, inputs, taps=None, out_uncorr=None, ld_uncorr=2048):
             # layer 1's first block: the downsample branch too -- its 4P-wide output is neither written nor re-read
             cur, o1 = bneck_tail_bf16(o2, e['c3'], None, nxt, n * Ho * Wo, down=e['down'], x0=cur)
         else:
-            res = _conv_b16(cur, e['down'], n, H, W, stride=s, relu=False)[0] if e['down'] is not None else cur
+            res = _conv_b16(cur, e['down'], n, H, W, stride=s, relu=False, dp=dp)[0] if e['down'] is not None else cur
             if fuse:
                 # layers 1-2: conv3 + residual + ReLU AND the next block's conv1 in one launch -- the 4P-wide output is
                 # written once (the next block's residual) and never re-read (fuse_bf16.hip)
                 cur, o1 = bneck_tail_bf16(o2, e['c3'], res, nxt, n * Ho * Wo)
             else:
-                cur, _, _ = _conv_b16(o2, e['c3'], n, Ho, Wo, res=res)
+                cur, _, _ = _conv_b16(o2, e['c3'], n, Ho, Wo, res=res, dp=dp)
         H, W = Ho, Wo
     x4 = cur
     M = x4.shape[0]
@@ -892,11 +937,13 @@ def _grl_eval_bf16s(model, inputs, taps=None, out_uncorr=None, ld_uncorr=2048):
     gb = _new((b, 1024), x)
     gemm(glo, c0.w[:, 2048:], gb, b, 1024, 1024, ldw=3072, math=MATH_F32, kblock=True)
     h1 = _newb((M, 1024), x)
-    gemm(x4, c0.wb(), h1, M, 1024, 2048, ldw=3072, gbias=gb, rows_per_group=t * PIX,
-         scale=c0.scale, shift=c0.shift, relu=False, math=MATH_BF16S)
+    w0, m0 = _gw(c0, dp, 2048)                  # (the x4 half of corr0's [1024][3072] weight)
+    gemm(x4, w0, h1, M, 1024, 2048, ldw=3072, gbias=gb, rows_per_group=t * PIX,
+         scale=c0.scale, shift=c0.shift, relu=False, math=m0)
     c2 = plan.corr2
     h2 = _newb((M, 256), x)
-    gemm(h1, c2.wb(), h2, M, 256, 1024, scale=c2.scale, shift=c2.shift, relu=True, math=MATH_BF16S)
+    w2, m2 = _gw(c2, dp)
+    gemm(h1, w2, h2, M, 256, 1024, scale=c2.scale, shift=c2.shift, relu=True, math=m2)
     cmap = _new((M,), x)
     xc, xu = _newb((M, 2048), x), _newb((M, 2048), x)
     _call('grl_gce_gate_bf16', ptr(h2), ptr(plan.corr5_w), ptr(plan.corr6_scale), ptr(plan.corr6_shift),
@@ -920,7 +967,7 @@ def _grl_eval_bf16s(model, inputs, taps=None, out_uncorr=None, ld_uncorr=2048):
     # grouped launch beats two launches (44 vs 2 x 35 us), but the 128 x 64 ring kernel the separate launches run on keeps
     # two workgroups per CU, so the two streams' launches already share every CU -- and the hand-offs cost their bubbles.
     # Off by default (GRL_TRL_GROUP=1 switches it on; kept tested: test_trl_grouped_launches_equal_two_stream_form).
-    grouped = TRL_GROUP and len(plan.dirs) == 2
+    grouped = TRL_GROUP and len(plan.dirs) == 2 and dp == MATH_BF16S
     fk = _TrlFork(x.device, taps is None and len(plan.dirs) == 2, att=not grouped)
     bufs = None
     if grouped:
@@ -931,14 +978,15 @@ def _grl_eval_bf16s(model, inputs, taps=None, out_uncorr=None, ld_uncorr=2048):
     for di, d in enumerate(plan.dirs):
         with fk.on(di):
             y = _newb((b * t * PIX, Cc), x)
-            gemm(xc, d['f2'].wb(), y, b * t * PIX, Cc, Cc, shift=d['f2'].shift, relu=True, math=MATH_BF16S)
+            wf2, mf2 = _gw(d['f2'], dp)
+            gemm(xc, wf2, y, b * t * PIX, Cc, Cc, shift=d['f2'].shift, relu=True, math=mf2)
             f2.append(y)
             fc.append(_new((b, t, Cc), x) if fk.two else (torch.zeros((b, t, Cc), dtype=torch.float32, device=x.device) if di == 0 else fc[0]))
             scr.append((_new((b, Cc), x), _new((b, 128), x)))
     memo = [memo0, memo0]
 
     def f1_gemm(di, d, ti):
-        if FUSE_TRL_SQDIFF and Mb % 256 == 0:
+        if FUSE_TRL_SQDIFF and Mb % 256 == 0 and dp == MATH_BF16S:
             # the squared difference reduced in the f1 GEMM's epilogue (32-row partial sums): conv_f1's output
             # never reaches HBM -- round 3: the bf16 256 x 256 kernel has the epilogue too
             dpart = _new((Mb // 32, Cc), x)
@@ -946,7 +994,8 @@ def _grl_eval_bf16s(model, inputs, taps=None, out_uncorr=None, ld_uncorr=2048):
                  res=f2[di][ti * PIX:], res_rows=PIX, res_gstride=t * PIX, math=MATH_BF16S)
             return dpart, None
         f1 = _newb((Mb, Cc), x)
-        gemm(memo[di], d['f1'].wb(), f1, Mb, Cc, Cc, shift=d['f1'].shift, relu=True, math=MATH_BF16S)
+        wf1, mf1 = _gw(d['f1'], dp)
+        gemm(memo[di], wf1, f1, Mb, Cc, Cc, shift=d['f1'].shift, relu=True, math=mf1)
         return None, f1
 
     def f1_tail(di, d, ti, dpart, f1):
@@ -992,11 +1041,12 @@ def _grl_eval_bf16s(model, inputs, taps=None, out_uncorr=None, ld_uncorr=2048):
                 _call('grl_add_strided_bf16', ptr(memo[di]), ptr(xu.view(-1)[ti * frame:]), ptr(s_), b, frame, t * frame)
                 c1, c2_, c3 = d['c1'], d['c2'], d['c3']
                 o = _newb((Mb, 512), x)
-                gemm(s_, c1.wb(), o, Mb, 512, Cc, scale=c1.scale, shift=c1.shift, relu=True, math=MATH_BF16S)
+                (w1, mm1), (w2_, mm2), (w3, mm3) = _gw(c1, dp), _gw(c2_, dp), _gw(c3, dp)
+                gemm(s_, w1, o, Mb, 512, Cc, scale=c1.scale, shift=c1.shift, relu=True, math=mm1)
                 o2 = _newb((Mb, 512), x)
-                gemm(o, c2_.wb(), o2, Mb, 512, 512, scale=c2_.scale, shift=c2_.shift, relu=True, math=MATH_BF16S)
+                gemm(o, w2_, o2, Mb, 512, 512, scale=c2_.scale, shift=c2_.shift, relu=True, math=mm2)
                 nm = _newb((Mb, Cc), x)
-                gemm(o2, c3.wb(), nm, Mb, Cc, 512, scale=c3.scale, shift=c3.shift, res=s_, relu=True, math=MATH_BF16S)
+                gemm(o2, w3, nm, Mb, Cc, 512, scale=c3.scale, shift=c3.shift, res=s_, relu=True, math=mm3)
                 memo[di] = nm
     fk.join(memo[1], fc[1])
     fcorr = fc[0]

@@ -52,6 +52,9 @@ _train_math = [_TRAIN_MATH[_train_mode[0]][0]]       # datapath of the GEMMs iss
 
 def set_math(name):
     """Select the training GEMM datapath ('f32' | 'mixed' | 'bf16x3' | 'bf16'); returns the previous name."""
+    if name == 'mxfp8':
+        raise ValueError("'mxfp8' is an eval-only datapath (engine.set_math('mxfp8')): there are no MX-FP8 training "
+                         "or gradient kernels")
     old = _train_mode[0]
     _train_math[0] = _TRAIN_MATH[name][0]
     _train_mode[0] = name

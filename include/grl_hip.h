@@ -36,8 +36,8 @@ const char* grl_last_error(void);
  * library whose version differs from the one it was written against (round 1: 1, round 2: 2 -- GrlGemm / GrlWgrad
  * grew, grl_bn_bwd gained two pointers -- round 3: 3, then 4 with grl_stem_wgrad, relu_bits, 5: GrlGemm.bn_*;
  * round 4: 6 with grl_bottleneck_tail_bf16, 7 grl_gemm_force_tile; round 5: 8 with grl_conv_gemm_f32_group;
- * round 6: 9 with the grl_jpeg_* entry points). */
-#define GRL_ABI_VERSION 9
+ * round 6: 9 with the grl_jpeg_* entry points; 10: GRL_MATH_MXFP8 and the grl_mx_* entry points, additive only). */
+#define GRL_ABI_VERSION 10
 int grl_abi_version(void);
 /* `waiter` (a hipStream_t) waits for everything enqueued on `signaler` so far: hipEventRecord + hipStreamWaitEvent on a
  * pooled event, one call instead of the host framework's Event / stream-context objects (round 6: the train step is
@@ -59,6 +59,42 @@ int grl_stream_wait_stream(void* waiter, void* signaler);
 #define GRL_MATH_BF16X3  3  /* split-bf16: hi*hi + hi*lo + lo*hi on the bf16 MFMA, ~2^-16 rel.   */
 #define GRL_MATH_BF16S   2  /* bf16 STORAGE: a, w, res and y are bf16 arrays (lda/ldw/ldy/ldres in
                              * elements), fp32 accumulate + epilogue; `out_f32` keeps y fp32      */
+#define GRL_MATH_MXFP8   4  /* MX-FP8 operands (eval only; see "MX-FP8 datapath" below): a, res, y bf16
+                             * as in GRL_MATH_BF16S, w an MX weight image (grl_mx_pack_weights)  */
+
+/*
+ * MX-FP8 datapath (GRL_MATH_MXFP8, gemm_mxfp8.hip): the bf16-storage GEMM on the block-scaled MFMA
+ * v_mfma_scale_f32_32x32x64_f8f6f4.  EXPERIMENTAL: correct to the contract below, but measured slower than
+ * GRL_MATH_BF16S on every pipeline shape (EXPERIMENTS.md, 'MX-FP8 eval datapath').  Numerics contract (OCP MX v1.0; model: tests/mx_ref.py):
+ *   - a block is 32 consecutive elements along K (of one row of A, one row of W);
+ *   - shared exponent e = floor(log2(amax)) - 8 (8 = emax of e4m3), clamped to [-127, 127]; amax is the block's
+ *     largest |x| with NaNs ignored and +inf counting as 2^128; the E8M0 scale byte is e + 127;
+ *   - an all-zero block gets scale byte 0 and zero elements;
+ *   - element = e4m3fn (OCP, not fnuz) of x * 2^-e, rounded to nearest even, saturated to +-448; a NaN element is
+ *     0x7F (sign kept), and the MFMA turns it into NaN in every output of its row (A) or column (W);
+ *   - W is quantised from the fp32 packed weight once per plan (grl_mx_pack_weights); A (bf16) is quantised per
+ *     (row, 32-k block) by a pass in front of the GEMM into the caller's scratch.  Implicit-GEMM convs need
+ *     C % 32 == 0: a block then lies inside one tap, so the pass quantises the input image per (pixel, 32-channel
+ *     block) -- the same bytes as per (row, block) of the im2col matrix; padding taps are all-zero blocks;
+ *   - fp32 accumulation; the GRL_MATH_BF16S affine epilogue in its order: v = acc * rowscale[m] + gbias, then
+ *     v * scale + shift, + bf16 res, ReLU that keeps NaN; bf16 store.
+ * Because the scales are per row and block, a clip's quantisation never depends on the other clips of its batch.
+ *
+ * MX image (weights from grl_mx_pack_weights, and the activation scratch): for R rows of K elements,
+ *   bytes [0, R*K)                     e4m3 elements, row r at r*K (row pitch K, whatever the source's ld was);
+ *   bytes [R*K, R*K + R*SK)            E8M0 scale bytes, row r at R*K + r*SK, SK = K/32 rounded up to a multiple of
+ *                                      4 (the padding bytes are 0).
+ * grl_mx_image_bytes(R, K) is its size.
+ *
+ * GrlGemm with math = GRL_MATH_MXFP8:
+ *   - a: bf16 (dense [M][lda], lda % 8 == 0, or the conv image [nimg][H][W][C]); res, y: bf16 as in GRL_MATH_BF16S;
+ *   - w: the MX image of the [N][K] weight (ldw is not read: the image is dense);
+ *   - splitk_ws / splitk_ws_floats: REQUIRED scratch for A's MX image, at least grl_conv_gemm_f32_workspace_floats()
+ *     floats, 16-byte aligned (GRL_EINVAL otherwise);
+ *   - epilogue GRL_EPI_AFFINE, dense or conv; K % 32 == 0 (and C % 32 == 0 for a conv).
+ *   GRL_EUNSUPPORTED (-3), before any launch: EUCLID / NEGDOT / SQDIFF epilogues, stats, bn_z, kblock, out_f32,
+ *   K % 32 != 0, conv C % 32 != 0.
+ */
 
 /*
  * One fp32 MFMA GEMM  Y[M][N] = epilogue( A[M][K] . W[N][K]^T ), K-contiguous on
@@ -155,6 +191,18 @@ int grl_conv_gemm_f32_stat_rows(const GrlGemm* desc);
  * (reid/models/grl_model.py:56-64 called at :155 and :167) -- two independent 8192-row GEMMs of the same shape that
  * each fill half a chip.  GRL_GEMM_GROUP=0: always n separate launches. */
 int grl_conv_gemm_f32_group(const GrlGemm* descs, int n, void* stream);
+
+/* fp32 weight w [N][ldw] (K used columns, K % 32 == 0) -> its MX image (out: grl_mx_image_bytes(N, K) bytes, 16-byte
+ * aligned; see "MX-FP8 datapath").  Eval packing of GRL_MATH_MXFP8; replaces nothing in the reference. */
+int grl_mx_pack_weights(const float* w, int N, int K, int ldw, uint8_t* out, void* stream);
+/* TEST HOOK: bf16 x [M][ldx] -> its MX image, with the device code the GRL_MATH_MXFP8 GEMM quantises A with. */
+int grl_mx_quantize_rows(const void* x, int M, int K, int ldx, uint8_t* out, void* stream);
+/* bytes of the MX image of rows x K (0 when K is not a positive multiple of 32) */
+int64_t grl_mx_image_bytes(int rows, int K);
+/* TEST HOOKS (host code, no device): the quantiser's element rule -- e4m3fn code of x * 2^-e for the fp32 bit pattern
+ * xbits -- and its exponent rule (e from the bits of a block's largest |x|, NaN excluded) */
+int grl_mx_e4m3_host(int32_t xbits, int e);
+int grl_mx_block_exp_host(int32_t amax_bits);
 
 /* [N][C][kh][kw] (torch layout) -> [N][kh*kw][C]; replaces nothing in the
  * reference (layout packing for the implicit GEMM). */
