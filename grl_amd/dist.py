@@ -289,6 +289,16 @@ def _all_gather(outs, t, group=None):
         dist.all_gather(outs, t, group=group)
 
 
+def _all_reduce_sum(t, group=None):
+    """In-place SUM all-reduce of ``t`` (staged through the host on gloo)."""
+    if _host_staged(t, group):
+        h = t.cpu()
+        dist.all_reduce(h, op=dist.ReduceOp.SUM, group=group)
+        t.copy_(h)
+    else:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+
+
 class _HostWork(object):
     """all-reduce of a device tensor through the host (gloo test backend): completes at wait()."""
 

@@ -1367,6 +1367,12 @@ def rank_metrics(indices, q_pids, g_pids, q_camids, g_camids, max_rank=100):
     ap = torch.empty(nq, dtype=torch.float64, device=dev)
     _call('grl_rank_metrics', ptr(indices), ng, ptr(qp), ptr(qc), ptr(gp), ptr(gc), nq, ng, ptr(first), ptr(nhit),
           ptr(ap))
+    return _cmc_map(first, nhit, ap, ng, max_rank)
+
+
+def _cmc_map(first, nhit, ap, ng, max_rank):
+    """(cmc[max_rank] float32, mAP) from the per-query (first match rank, #matches, AP) device arrays."""
+    import numpy as np
     first, nhit, ap = first.cpu().numpy(), nhit.cpu().numpy(), ap.cpu().numpy()
     valid = nhit > 0
     assert valid.any(), "Error: all query identities do not appear in gallery"
@@ -1376,3 +1382,181 @@ def rank_metrics(indices, q_pids, g_pids, q_camids, g_camids, max_rank=100):
     hit_by = (first[valid][:, None] <= np.arange(max_rank)[None, :]).astype(np.float32)
     return hit_by.sum(0) / float(valid.sum()), float(np.mean(ap[valid]))
 
+
+
+# ----------------------------------------------------------------------------
+# gallery search and ranking metrics over column blocks (search.hip)
+# ----------------------------------------------------------------------------
+SEARCH_BLOCK_BYTES = int(os.environ.get('GRL_SEARCH_BLOCK_BYTES', str(256 << 20)))   # distance block budget
+SEARCH_K_MAX = 1024
+
+
+class _ColumnBlocks(object):
+    """Column blocks D[:, c0:c1] of the distance matrix of ``qf`` against gallery rows [lo, hi) of ``gf``
+    ('cosine' = cosin_dist, 'euclidean' = pairwise_distance_tensor), one GEMM per block into one reused
+    buffer.  Every entry is computed by the same fma chain as in the full matrix (the GEMM's order does not
+    depend on N; no split-K scratch is handed over), so a block holds the full matrix's bits.  Without
+    ``block_cols`` the width is the largest multiple of 256 columns whose block fits ``block_bytes``."""
+
+    def __init__(self, qf, gf, metric='cosine', block_cols=None, block_bytes=None, lo=0, hi=None):
+        if metric not in ('cosine', 'euclidean'):
+            raise ValueError("metric must be 'cosine' or 'euclidean' (got %r)" % (metric,))
+        require_device(qf, 'qf'); require_device(gf, 'gf')
+        nq, ng = qf.shape[0], gf.shape[0]
+        self.qf = qf.contiguous().view(nq, -1)
+        self.gf = gf.contiguous().view(ng, -1)
+        if self.qf.shape[1] != self.gf.shape[1]:
+            raise ValueError('qf and gf have different feature sizes (%d, %d)' % (self.qf.shape[1], self.gf.shape[1]))
+        hi = ng if hi is None else hi
+        self.nq, self.ng, self.metric = nq, ng, metric
+        if block_cols is None:
+            budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
+            block_cols = max(256, budget // (4 * max(nq, 1)) // 256 * 256)
+        width = max(1, min(int(block_cols), hi - lo))
+        self.width = width
+        self.spans = [(c, min(c + width, hi)) for c in range(lo, hi, width)]
+        self.buf = _new((nq * width,), self.qf) if self.spans and nq else None
+        self.rn = self.cn = None
+        if metric == 'euclidean' and self.spans:
+            k = self.qf.shape[1]
+            self.rn, self.cn = _new((nq,), self.qf), _new((hi - lo,), self.qf)
+            _call('grl_row_sqnorm', ptr(self.qf), ptr(self.rn), nq, k, k)
+            _call('grl_row_sqnorm', ptr(self.gf[lo:hi]), ptr(self.cn), hi - lo, k, k)
+        self.lo = lo
+
+    def block(self, c0, c1):
+        n, k = c1 - c0, self.qf.shape[1]
+        out = self.buf[:self.nq * n].view(self.nq, n)
+        if self.metric == 'cosine':
+            return gemm(self.qf, self.gf[c0:c1], out, self.nq, n, k, epilogue=EPI_NEGDOT, math=MATH_F32)
+        return gemm(self.qf, self.gf[c0:c1], out, self.nq, n, k, epilogue=EPI_EUCLID, rnorm=self.rn,
+                    cnorm=self.cn[c0 - self.lo:c1 - self.lo], math=MATH_F32)
+
+
+def _shard(ng):
+    from . import dist as grl_dist
+    if not grl_dist.is_distributed():
+        return 0, ng, False
+    import torch.distributed as tdist
+    lo, hi = grl_dist.shard_rows(ng, tdist.get_rank(), tdist.get_world_size())
+    return lo, hi, True
+
+
+def search(qf, gf, k, metric='cosine', block_cols=None, block_bytes=None):
+    """Each query's ``k`` nearest gallery entries: ``(dist [nq, k] float32, idx [nq, k] int64)`` on the device,
+    without the query x gallery matrix.  Exactly ``rank_rows(D)[:, :k]`` and ``D`` at those indices, bit for
+    bit, for D = cosin_dist(qf, gf) ('cosine') or pairwise_distance_tensor(qf, gf) ('euclidean'): canonical
+    NaN, -0 == +0, ties to the smaller gallery index.  With fewer than ``k`` gallery entries the tail of every
+    row is padding: index -1, distance +inf.  k <= 1024.  The distances are computed in column blocks of
+    ``block_cols`` (default: as many as fit ``block_bytes``, GRL_SEARCH_BLOCK_BYTES, 256 MiB).  Under
+    torch.distributed the gallery rows are sharded over the ranks and only the per-rank top-k lists are
+    exchanged."""
+    if not 1 <= int(k) <= SEARCH_K_MAX:
+        raise ValueError('search: k must be in 1..%d (got %r)' % (SEARCH_K_MAX, k))
+    k = int(k)
+    nq, ng = qf.shape[0], gf.shape[0]
+    lo, hi, sharded = _shard(ng)
+    blocks = _ColumnBlocks(qf, gf, metric, block_cols, block_bytes, lo, hi)
+    dev = blocks.qf.device
+    run_key = torch.full((nq, k), -1, dtype=torch.int64, device=dev)          # all-ones composite = empty slot
+    run_val = torch.full((nq, k), float('inf'), dtype=torch.float32, device=dev)
+    if nq == 0:
+        return run_val, run_key
+    for c0, c1 in blocks.spans:
+        d = blocks.block(c0, c1)
+        _call('grl_topk_block', ptr(d), c1 - c0, None, 0, nq, c1 - c0, c0, k, ptr(run_key), ptr(run_val))
+    if sharded:
+        import torch.distributed as tdist
+        from . import dist as grl_dist
+        world = tdist.get_world_size()
+        vals = [torch.empty_like(run_val) for _ in range(world)]
+        keys = [torch.empty_like(run_key) for _ in range(world)]
+        grl_dist._all_gather(vals, run_val)
+        grl_dist._all_gather(keys, run_key)
+        cand_v = torch.cat(vals, 1).contiguous()                         # rank order; the merge is order-free
+        cand_i = (torch.cat(keys, 1) & 0xffffffff).to(torch.int32).contiguous()   # empty slots: -1 = skipped
+        run_key.fill_(-1)
+        run_val.fill_(float('inf'))
+        _call('grl_topk_block', ptr(cand_v), world * k, ptr(cand_i), world * k, nq, world * k, 0, k, ptr(run_key),
+              ptr(run_val))
+    idx = run_key & 0xffffffff
+    idx[idx == 0xffffffff] = -1
+    return run_val, idx
+
+
+def rank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, metric='cosine', max_rank=100,
+                           block_cols=None, block_bytes=None):
+    """``rank_metrics(rank_rows(D), ...)`` without D or its argsort: (cmc[max_rank] float32, mAP float) of
+    eva_functions.evaluate for D = cosin_dist(qf, gf) / pairwise_distance_tensor(qf, gf).  Per query, the
+    distances of its matches (its pid, another camera; same pid and camera is dropped) are gathered and sorted
+    in a first pass over the column blocks; a second pass counts, for each non-match, how many matches come
+    before it, and the matches' ranks follow from a prefix sum.  First-match rank and #matches per query are
+    those of rank_metrics exactly, AP agrees to ~1e-15 (fp64, another summation order), so the CMC is equal and
+    the mAP within 1e-12.  One GEMM pass when the whole matrix fits one block, two otherwise.  At most 8192
+    gallery entries may share a query's pid.  Under torch.distributed the gallery rows are sharded over the
+    ranks; they exchange only the match keys and the rank histograms (both sized by the matches)."""
+    first, nhit, ap = _rank_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, metric, block_cols, block_bytes)
+    return _cmc_map(first, nhit, ap, gf.shape[0], max_rank)
+
+
+def _rank_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, metric='cosine', block_cols=None, block_bytes=None):
+    """Per-query (first match rank, #matches, AP) device arrays of rank_metrics_streaming (= grl_rank_metrics's)."""
+    import numpy as np
+    from . import dist as grl_dist
+    nq, ng = qf.shape[0], gf.shape[0]
+    lo, hi, sharded = _shard(ng)
+    blocks = _ColumnBlocks(qf, gf, metric, block_cols, block_bytes, lo, hi)
+    dev = blocks.qf.device
+
+    def ids(a, n, what):
+        a = np.asarray(a).reshape(-1)
+        if a.size != n:
+            raise ValueError('%s: expected %d entries, got %d' % (what, n, a.size))
+        return a.astype(np.int32)
+    qp, qc = ids(q_pids, nq, 'q_pids'), ids(q_camids, nq, 'q_camids')
+    gp, gc = ids(g_pids, ng, 'g_pids'), ids(g_camids, ng, 'g_camids')
+    # pid -> ascending gallery indices (CSR); a query's candidates are its pid's list
+    order = np.argsort(gp, kind='stable').astype(np.int32)
+    uniq, starts = np.unique(gp[order], return_index=True)
+    pid_ptr = np.append(starts, ng).astype(np.int32)
+    slot = np.searchsorted(uniq, qp)
+    found = slot < uniq.size
+    found[found] = uniq[slot[found]] == qp[found]
+    q_slot = np.where(found, slot, -1).astype(np.int32)
+    cand_len = np.where(found, pid_ptr[np.minimum(slot + 1, uniq.size)] - pid_ptr[np.minimum(slot, uniq.size - 1)], 0)
+    cand_off = np.zeros(nq + 1, np.int64)
+    np.cumsum(cand_len, out=cand_off[1:])
+    total = max(int(cand_off[-1]), 1)
+
+    def dev32(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    t_qp, t_qc, t_gp, t_gc = dev32(qp), dev32(qc), dev32(gp), dev32(gc)
+    t_slot, t_ptr, t_list, t_off = dev32(q_slot), dev32(pid_ptr), dev32(order), dev32(cand_off)
+    cand_key = torch.zeros(total, dtype=torch.int32, device=dev)
+    one_pass = len(blocks.spans) == 1
+    d = None
+    for c0, c1 in blocks.spans:
+        d = blocks.block(c0, c1)
+        _call('grl_match_gather', ptr(d), c1 - c0, nq, c0, c1 - c0, ptr(t_slot), ptr(t_ptr), ptr(t_list), ptr(t_off),
+              ptr(cand_key))
+    if sharded:
+        grl_dist._all_reduce_sum(cand_key)          # each candidate was written by exactly one rank, zero elsewhere
+    match_key = torch.empty(total, dtype=torch.int64, device=dev)
+    n_match = torch.empty(nq, dtype=torch.int32, device=dev)
+    _call('grl_match_sort', nq, ptr(t_slot), ptr(t_ptr), ptr(t_list), ptr(t_qc), ptr(t_gc), ptr(t_off),
+          ptr(cand_key), int(cand_len.max()) if nq else 0, ptr(match_key), ptr(n_match))
+    max_match = int(n_match.max().item())
+    hist = torch.zeros(total, dtype=torch.int32, device=dev)
+    if max_match > 0:
+        for c0, c1 in blocks.spans:
+            if not one_pass:
+                d = blocks.block(c0, c1)
+            _call('grl_rank_count_block', ptr(d), c1 - c0, nq, c0, c1 - c0, ptr(t_qp), ptr(t_gp), ptr(t_off),
+                  ptr(match_key), ptr(n_match), max_match, ptr(hist))
+    if sharded:
+        grl_dist._all_reduce_sum(hist)
+    first = torch.empty(nq, dtype=torch.int32, device=dev)
+    nhit = torch.empty(nq, dtype=torch.int32, device=dev)
+    ap = torch.empty(nq, dtype=torch.float64, device=dev)
+    _call('grl_rank_finish', nq, ptr(t_off), ptr(n_match), ptr(hist), ptr(first), ptr(nhit), ptr(ap))
+    return first, nhit, ap

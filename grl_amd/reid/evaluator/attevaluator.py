@@ -3,6 +3,7 @@
 the query x gallery distance matrix run on the GPU through grl_amd.engine; the
 ranking metrics stay on the host."""
 import math
+import os
 
 import numpy as np
 import torch
@@ -21,6 +22,10 @@ def evaluate_seq(distmat, query_pids, query_camids, gallery_pids, gallery_camids
     (attevaluator.py:15-30)."""
     cmc_scores, mAP = evaluate(distmat, np.array(query_pids), np.array(gallery_pids),
                                np.array(query_camids), np.array(gallery_camids), indices=indices)
+    return _report(cmc_scores, mAP, cmc_topk)
+
+
+def _report(cmc_scores, mAP, cmc_topk=(1, 5, 10, 20)):
     print('Mean AP: {:4.1%}'.format(mAP))
     for r in cmc_topk:
         print("Rank-{:<3}: {:.1%}".format(r, cmc_scores[r - 1]))
@@ -99,6 +104,10 @@ class ATTEvaluator(object):
     def evaluate(self, query, gallery, query_loader, gallery_loader, path, visual, rerank):
         if visual:
             raise NotImplementedError('ranked-result visualisation is outside the GRL hot path')
+        stream = os.environ.get('GRL_EVAL_STREAM') == '1'
+        if stream and rerank:
+            raise ValueError('GRL_EVAL_STREAM=1 cannot re-rank: k-reciprocal re-ranking needs the full query/gallery '
+                             'distance matrices, which the streaming evaluator never builds (unset GRL_EVAL_STREAM)')
         qf, q_pids, q_camids = self.extract_feature(query_loader)
         print('Done, obtained {}-by-{} matrix'.format(qf.size(0), qf.size(1)))
         gf, g_pids, g_camids = self.extract_feature(gallery_loader)
@@ -107,6 +116,10 @@ class ATTEvaluator(object):
         g_camids = np.append(q_camids, g_camids)
         print('Done, obtained {}-by-{} matrix'.format(gf.size(0), gf.size(1)))
         print("Computing distance matrix")
+        if stream:
+            # column blocks of the distance GEMM and exact CMC / mAP without a sort (engine.rank_metrics_streaming); under
+            # torch.distributed the gallery columns are sharded and only match keys and rank histograms travel
+            return _report(*engine.rank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids))
         dist_dev = grl_dist.sharded_distmat(qf, gf, cosin_dist)     # gallery rows sharded over the ranks
         # ranking AND the per-query CMC / AP work on the device (one LDS sort network per row up to
         # 16384 gallery entries -- MARS: 11310 -- the chunked network beyond): neither the distance nor

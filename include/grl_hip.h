@@ -36,7 +36,9 @@ const char* grl_last_error(void);
  * library whose version differs from the one it was written against (round 1: 1, round 2: 2 -- GrlGemm / GrlWgrad
  * grew, grl_bn_bwd gained two pointers -- round 3: 3, then 4 with grl_stem_wgrad, relu_bits, 5: GrlGemm.bn_*;
  * round 4: 6 with grl_bottleneck_tail_bf16, 7 grl_gemm_force_tile; round 5: 8 with grl_conv_gemm_f32_group;
- * round 6: 9 with the grl_jpeg_* entry points; 10: GRL_MATH_MXFP8 and the grl_mx_* entry points, additive only). */
+ * round 6: 9 with the grl_jpeg_* entry points; 10: GRL_MATH_MXFP8 and the grl_mx_* entry points, additive only).
+ * The column-block search / ranking entry points grl_topk_block .. grl_rank_finish were added at 10: they change no
+ * struct layout or argument list, and a library without them fails to bind in _lib.load. */
 #define GRL_ABI_VERSION 10
 int grl_abi_version(void);
 /* `waiter` (a hipStream_t) waits for everything enqueued on `signaler` so far: hipEventRecord + hipStreamWaitEvent on a
@@ -571,6 +573,37 @@ int grl_scale_dev(const float* x, const float* g, float alpha, float* y, int64_t
 int grl_rank_metrics(const int32_t* idx, int64_t ld, const int32_t* q_pids, const int32_t* q_cams,
                      const int32_t* g_pids, const int32_t* g_cams, int nq, int ng, int32_t* first_hit,
                      int32_t* n_hits, double* ap, void* stream);
+
+/* ---- gallery search and exact ranking metrics over column blocks (search.hip, engine.search /
+ * engine.rank_metrics_streaming).  ``d`` is a column block [nq][ld] (ncols used) of the query x gallery
+ * distance matrix whose first column is gallery entry col0.  Order: that of grl_row_argsort (canonical NaN,
+ * -0 -> +0, ascending, ties to the smaller gallery index); an entry is the composite (key << 32) | index. */
+/* running top-k per query: run_key [nq][k] (composites, sorted; initialised to all-ones = empty) and run_val
+ * [nq][k] (the distances' own bits; initialised to +inf) become the first k of their union with the block.
+ * cidx (may be NULL) [nq][ldc] gives each column's gallery index (< 0: skipped) instead of col0 + column.
+ * k <= 1024 (GRL_EUNSUPPORTED beyond). */
+int grl_topk_block(const float* d, int64_t ld, const int32_t* cidx, int64_t ldc, int nq, int ncols, int col0, int k,
+                   uint64_t* run_key, float* run_val, void* stream);
+/* candidates of query q = gallery entries with its pid: q_slot[q] indexes the CSR pid_ptr / pid_list (ascending
+ * gallery indices per pid; -1 = the pid is not in the gallery).  The keys of those inside the block go to
+ * cand_key[cand_off[q] + j] (j = position in the pid's list). */
+int grl_match_gather(const float* d, int64_t ld, int nq, int col0, int ncols, const int32_t* q_slot,
+                     const int32_t* pid_ptr, const int32_t* pid_list, const int64_t* cand_off, uint32_t* cand_key,
+                     void* stream);
+/* keep the candidates from another camera (same pid AND camera = junk) and sort them: match_key[cand_off[q] + i],
+ * i < n_match[q].  max_list = longest pid list, at most 8192 (GRL_EUNSUPPORTED beyond). */
+int grl_match_sort(int nq, const int32_t* q_slot, const int32_t* pid_ptr, const int32_t* pid_list,
+                   const int32_t* q_cams, const int32_t* g_cams, const int64_t* cand_off, const uint32_t* cand_key,
+                   int max_list, uint64_t* match_key, int32_t* n_match, void* stream);
+/* for each non-match g (another pid) of the block, p(g) = matches strictly before g; hist[cand_off[q] + p] += 1
+ * for p < n_match[q] (integer atomics; hist zero-filled by the caller).  max_match = max over q of n_match. */
+int grl_rank_count_block(const float* d, int64_t ld, int nq, int col0, int ncols, const int32_t* q_pids,
+                         const int32_t* g_pids, const int64_t* cand_off, const uint64_t* match_key,
+                         const int32_t* n_match, int max_match, int32_t* hist, void* stream);
+/* rank_i = i + sum_{p <= i} hist[p]: first_hit / n_hits / ap as grl_rank_metrics gives them (ap summed in
+ * ascending i, fp64) */
+int grl_rank_finish(int nq, const int64_t* cand_off, const int32_t* n_match, const int32_t* hist,
+                    int32_t* first_hit, int32_t* n_hits, double* ap, void* stream);
 
 /* ---- k-reciprocal re-ranking on the device (reid/evaluator/rerank.py:37-104) ----
  * N = nq + ng samples (<= 16384).  All matrices fp32 row-major, caller-owned:
