@@ -167,6 +167,12 @@ _SIGNATURES = {
     'grl_rerank_krecip': ([_fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
     'grl_rerank_expand': ([_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp], C.c_int),
     'grl_rerank_jaccard': ([_fp, _fp, _fp, C.c_int, C.c_int, C.c_float, C.c_float, _fp, _fp], C.c_int),
+    'grl_rrs_segment_rows': ([_fp, _i64, _fp, _i64, _i64, C.c_int, C.c_int, C.c_int, _fp, _fp, _i64, _fp], C.c_int),
+    'grl_rrs_lists': ([_fp, _i64, C.c_int, C.c_int, _fp, _fp, _fp], C.c_int),
+    'grl_rrs_weights': ([_fp, _i64, _fp, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp],
+                        C.c_int),
+    'grl_rrs_expand': ([_fp, _i64, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp], C.c_int),
+    'grl_rrs_final': ([_fp, _i64, C.c_int, C.c_int, C.c_int] + [_fp] * 7 + [C.c_float, C.c_float, _fp], C.c_int),
     'grl_row_argsort': ([_fp, _i64, C.c_int, C.c_int, _fp, _fp], C.c_int),
     'grl_row_argsort_workspace_bytes': ([C.c_int, C.c_int], _i64),
     'grl_row_argsort_wide': ([_fp, _i64, C.c_int, C.c_int, _fp, _fp, _fp], C.c_int),

@@ -1457,6 +1457,11 @@ def search(qf, gf, k, metric='cosine', block_cols=None, block_bytes=None):
     nq, ng = qf.shape[0], gf.shape[0]
     lo, hi, sharded = _shard(ng)
     blocks = _ColumnBlocks(qf, gf, metric, block_cols, block_bytes, lo, hi)
+    return _search_blocks(blocks, nq, k, sharded)
+
+
+def _search_blocks(blocks, nq, k, sharded):
+    """The running top-k of search over a block source (``spans``, ``block(c0, c1)``, ``qf``)."""
     dev = blocks.qf.device
     run_key = torch.full((nq, k), -1, dtype=torch.int64, device=dev)          # all-ones composite = empty slot
     run_val = torch.full((nq, k), float('inf'), dtype=torch.float32, device=dev)
@@ -1501,11 +1506,17 @@ def rank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, metric='c
 
 def _rank_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, metric='cosine', block_cols=None, block_bytes=None):
     """Per-query (first match rank, #matches, AP) device arrays of rank_metrics_streaming (= grl_rank_metrics's)."""
-    import numpy as np
-    from . import dist as grl_dist
     nq, ng = qf.shape[0], gf.shape[0]
     lo, hi, sharded = _shard(ng)
     blocks = _ColumnBlocks(qf, gf, metric, block_cols, block_bytes, lo, hi)
+    return _rank_blocks(blocks, nq, ng, q_pids, g_pids, q_camids, g_camids, sharded)
+
+
+def _rank_blocks(blocks, nq, ng, q_pids, g_pids, q_camids, g_camids, sharded):
+    """The two passes of _rank_streaming over a block source (``spans``, ``block(c0, c1)``, ``qf``); a block
+    must come back with the same bits every time it is asked for."""
+    import numpy as np
+    from . import dist as grl_dist
     dev = blocks.qf.device
 
     def ids(a, n, what):
@@ -1560,3 +1571,172 @@ def _rank_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, metric='cosine',
     ap = torch.empty(nq, dtype=torch.float64, device=dev)
     _call('grl_rank_finish', nq, ptr(t_off), ptr(n_match), ptr(hist), ptr(first), ptr(nhit), ptr(ap))
     return first, nhit, ap
+
+
+
+# ----------------------------------------------------------------------------
+# streaming k-reciprocal re-ranking (rerank_stream.hip)
+# ----------------------------------------------------------------------------
+RERANK_K1_MAX, RERANK_K2_MAX, RERANK_LMAX = 20, 8, 256
+
+
+class _SampleBlocks(object):
+    """Column blocks S[:, i0:i1] of the stacked distance matrix S = [[qq, qg], [qg^T, gg]] over the N = nq + ng
+    samples (qq, gg = pairwise_distance_tensor, qg = cosin_dist: what ATTEvaluator hands to re_ranking), as
+    SEGMENTS on one side of the query/gallery boundary.  A query segment's lower rows are a row block of qg
+    (gemm(qf[i0:i1], gf), read transposed), a gallery segment's come from a column block of gg; every entry has
+    the full matrix's bits.  Without ``block_cols`` the width is the multiple of 32 samples whose three buffers
+    (upper, lower, D rows) fit ``block_bytes``."""
+
+    def __init__(self, qf, gf, block_cols=None, block_bytes=None):
+        nq, ng = qf.shape[0], gf.shape[0]
+        self.nq, self.ng, self.N = nq, ng, nq + ng
+        if block_cols is None:
+            budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
+            block_cols = max(32, budget // (12 * self.N) // 32 * 32)
+            block_cols = min(block_cols, max(32, -(-self.N // 64) * 32))          # never the whole N x N matrix
+        self.width = w = max(1, min(int(block_cols), self.N))
+        self.spans = [(i, min(i + w, self.N)) for i in range(0, self.N, w)]
+        self.qq = _ColumnBlocks(qf, qf, 'euclidean', block_cols=min(w, nq))
+        self.qg = _ColumnBlocks(qf, gf, 'cosine', block_cols=min(w, ng))
+        self.gg = _ColumnBlocks(gf, gf, 'euclidean', block_cols=min(w, ng))
+        self.qf, self.gf = self.qq.qf, self.gg.qf
+        self.rows = _new((min(w, nq) * ng,), self.qf)
+        self.drows = None
+
+    def segments(self, i0, i1):
+        """(s0, s1, up, ldu, lo, lo_rs, lo_cs) for the parts of [i0, i1) left and right of the boundary."""
+        nq, ng, k = self.nq, self.ng, self.qf.shape[1]
+        if i0 < nq:
+            s1 = min(i1, nq)
+            n = s1 - i0
+            up = self.qq.block(i0, s1)
+            lo = self.rows[:n * ng].view(n, ng)
+            gemm(self.qf[i0:s1], self.gf, lo, n, ng, k, epilogue=EPI_NEGDOT, math=MATH_F32)
+            yield i0, s1, up, n, lo, 1, ng
+            i0 = s1
+        if i0 < i1:
+            n = i1 - i0
+            yield i0, i1, self.qg.block(i0 - nq, i1 - nq), n, self.gg.block(i0 - nq, i1 - nq), n, 1
+
+    def d_rows(self, i0, i1, colmax):
+        """D[i0:i1, :] of grl_rerank_build ([i1-i0][N] view of a reused buffer); colmax[i0:i1] is filled too."""
+        if self.drows is None:
+            self.drows = _new((self.width * self.N,), self.qf)
+        out = self.drows[:(i1 - i0) * self.N].view(i1 - i0, self.N)
+        for s0, s1, up, ldu, lo, lrs, lcs in self.segments(i0, i1):
+            _call('grl_rrs_segment_rows', ptr(up), ldu, ptr(lo), lrs, lcs, self.nq, self.ng, s1 - s0,
+                  ptr(colmax[s0:]), ptr(out[s0 - i0:]), self.N)
+        return out
+
+
+class _Rerank(object):
+    """The sparse state of the k-reciprocal re-ranking of (qf, gf): colmax [N], the first K rank entries of every
+    D row, the expansion lists with their weights ([N][256]), V2 as CSR over all samples and the gallery samples'
+    V2 as CSC.  Nothing of size N x N or nq x ng is allocated."""
+
+    def __init__(self, qf, gf, k1, k2, lambda_value, block_cols=None, block_bytes=None):
+        require_device(qf, 'qf'); require_device(gf, 'gf')
+        nq, ng = qf.shape[0], gf.shape[0]
+        N = nq + ng
+        if qf.dim() != 2 or gf.dim() != 2 or qf.shape[1] != gf.shape[1]:
+            raise ValueError('qf [nq, d] and gf [ng, d] must share d (got %s, %s)' % (tuple(qf.shape), tuple(gf.shape)))
+        if nq < 1 or ng < 1:
+            raise ValueError('re-ranking needs at least one query and one gallery entry')
+        if not (1 <= int(k1) <= RERANK_K1_MAX and int(k1) < N):
+            raise ValueError('k1 must be in 1..%d and below q + g = %d (got %r)' % (RERANK_K1_MAX, N, k1))
+        if not (1 <= int(k2) <= RERANK_K2_MAX and int(k2) <= N):
+            raise ValueError('k2 must be in 1..%d and at most q + g = %d (got %r)' % (RERANK_K2_MAX, N, k2))
+        self.nq, self.ng, self.N = nq, ng, N
+        self.k1, self.k2, self.K = int(k1), int(k2), max(int(k1) + 1, int(k2))
+        self.lam, self.one_minus = float(lambda_value), 1 - lambda_value     # float32(1 - lambda), as rerank.py passes it
+        sb = _SampleBlocks(qf, gf, block_cols, block_bytes)
+        dev, K = sb.qf.device, self.K
+        # pass A1: colmax and the first K entries of every D row (grl_row_argsort's order)
+        self.colmax = torch.empty(N, dtype=torch.float32, device=dev)
+        run_key = torch.full((N, K), -1, dtype=torch.int64, device=dev)
+        run_val = torch.full((N, K), float('inf'), dtype=torch.float32, device=dev)
+        for i0, i1 in sb.spans:
+            dr = sb.d_rows(i0, i1, self.colmax)
+            _call('grl_topk_block', ptr(dr), N, None, 0, i1 - i0, N, 0, K, ptr(run_key[i0:]), ptr(run_val[i0:]))
+        sb.drows = None
+        del run_val
+        self.rank = (run_key & 0xffffffff).to(torch.int32)
+        del run_key
+        # expansion lists, then pass A2: their weights
+        self.lcnt = torch.empty(N, dtype=torch.int32, device=dev)
+        self.lidx = torch.empty((N, RERANK_LMAX), dtype=torch.int32, device=dev)
+        _call('grl_rrs_lists', ptr(self.rank), K, N, self.k1, ptr(self.lcnt), ptr(self.lidx))
+        self.lval = torch.empty((N, RERANK_LMAX), dtype=torch.float32, device=dev)
+        for i0, i1 in sb.spans:
+            for s0, s1, up, ldu, lo, lrs, lcs in sb.segments(i0, i1):
+                _call('grl_rrs_weights', ptr(up), ldu, ptr(lo), lrs, lcs, nq, ng, s1 - s0, s0, ptr(self.colmax),
+                      ptr(self.lcnt), ptr(self.lidx), ptr(self.lval))
+        del sb
+        # local query expansion: V2 as CSR (a counting launch sizes it)
+        cnt = torch.empty(N, dtype=torch.int32, device=dev)
+        _call('grl_rrs_expand', ptr(self.rank), K, ptr(self.lcnt), ptr(self.lidx), ptr(self.lval), N, self.k2, None,
+              ptr(cnt), None, None)
+        self.row_ptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(cnt, 0, out=self.row_ptr[1:])
+        nnz = int(self.row_ptr[-1].item())
+        self.col = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+        self.val = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)
+        _call('grl_rrs_expand', ptr(self.rank), K, ptr(self.lcnt), ptr(self.lidx), ptr(self.lval), N, self.k2,
+              ptr(self.row_ptr), None, ptr(self.col), ptr(self.val))
+        # inverted index of the gallery samples' rows: a stable sort by column keeps ascending j within a column
+        g0 = int(self.row_ptr[nq].item())
+        kcol = self.col[g0:nnz].long()
+        order = torch.sort(kcol, stable=True).indices
+        grow = torch.repeat_interleave(torch.arange(nq, N, dtype=torch.int32, device=dev), cnt[nq:].long(),
+                                       output_size=nnz - g0)
+        self.csc_row = grow[order].contiguous() if nnz > g0 else torch.zeros(1, dtype=torch.int32, device=dev)
+        self.csc_val = self.val[g0:nnz][order].contiguous() if nnz > g0 else torch.zeros(1, device=dev)
+        self.csc_ptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(torch.bincount(kcol, minlength=N), 0, out=self.csc_ptr[1:])
+
+    def finish(self, d, col0, ncols):
+        """d [nq][ncols] (cosin_dist of gallery entries col0 ..) becomes the re-ranked distances, in place."""
+        _call('grl_rrs_final', ptr(d), ncols, self.nq, col0, ncols, ptr(self.colmax), ptr(self.row_ptr), ptr(self.col),
+              ptr(self.val), ptr(self.csc_ptr), ptr(self.csc_row), ptr(self.csc_val), C.c_float(self.lam),
+              C.c_float(self.one_minus))
+        return d
+
+
+class _RerankBlocks(object):
+    """Column blocks of the re-ranked q x g distances: cosin_dist blocks transformed in place."""
+
+    def __init__(self, qf, gf, rr, block_cols=None, block_bytes=None):
+        if block_cols is None:                      # as _ColumnBlocks, but never the whole q x g matrix in one block
+            budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
+            block_cols = max(256, budget // (4 * rr.nq) // 256 * 256)
+            block_cols = min(block_cols, max(256, -(-rr.ng // 512) * 256))
+        self.cos = _ColumnBlocks(qf, gf, 'cosine', block_cols)
+        self.spans, self.qf, self.rr = self.cos.spans, self.cos.qf, rr
+
+    def block(self, c0, c1):
+        return self.rr.finish(self.cos.block(c0, c1), c0, c1 - c0)
+
+
+def rerank_search(qf, gf, k, k1=20, k2=6, lambda_value=0.3, block_cols=None, block_bytes=None):
+    """``search`` on the k-reciprocal re-ranked distances F = re_ranking(cosin_dist(qf, gf), pairwise_distance_tensor(
+    qf, qf), pairwise_distance_tensor(gf, gf), k1, k2, lambda_value): ``(dist [nq, k] float32, idx [nq, k] int64)``,
+    bit for bit ``rank_rows(F)[:, :k]`` and F at those indices (search's tie, NaN and padding rules), without F, the
+    (q+g)^2 matrices or any nq x ng array.  k <= 1024, k1 <= 20, k2 <= 8; no limit on q + g.  Blocks follow
+    ``block_cols`` / ``block_bytes`` (GRL_SEARCH_BLOCK_BYTES).  Under torch.distributed every rank computes the full
+    result: nothing is sharded or exchanged."""
+    if not 1 <= int(k) <= SEARCH_K_MAX:
+        raise ValueError('rerank_search: k must be in 1..%d (got %r)' % (SEARCH_K_MAX, k))
+    rr = _Rerank(qf, gf, k1, k2, lambda_value, block_cols, block_bytes)
+    return _search_blocks(_RerankBlocks(qf, gf, rr, block_cols, block_bytes), rr.nq, int(k), False)
+
+
+def rerank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, k1=20, k2=6, lambda_value=0.3, max_rank=100,
+                             block_cols=None, block_bytes=None):
+    """``rank_metrics(rank_rows(F), ...)`` for the re-ranked distances F of ``rerank_search``: (cmc[max_rank] float32,
+    mAP float) with rank_metrics_streaming's contract (first hit and #matches exact, CMC equal, mAP within 1e-12,
+    at most 8192 gallery entries per query pid).  Under torch.distributed every rank computes the full result."""
+    rr = _Rerank(qf, gf, k1, k2, lambda_value, block_cols, block_bytes)
+    first, nhit, ap = _rank_blocks(_RerankBlocks(qf, gf, rr, block_cols, block_bytes), rr.nq, rr.ng, q_pids, g_pids,
+                                   q_camids, g_camids, False)
+    return _cmc_map(first, nhit, ap, rr.ng, max_rank)

@@ -105,7 +105,8 @@ class ATTEvaluator(object):
         if visual:
             raise NotImplementedError('ranked-result visualisation is outside the GRL hot path')
         stream = os.environ.get('GRL_EVAL_STREAM') == '1'
-        if stream and rerank:
+        rerank_stream = rerank and os.environ.get('GRL_EVAL_RERANK') == 'stream'
+        if stream and rerank and not rerank_stream:
             raise ValueError('GRL_EVAL_STREAM=1 cannot re-rank: k-reciprocal re-ranking needs the full query/gallery '
                              'distance matrices, which the streaming evaluator never builds (unset GRL_EVAL_STREAM)')
         qf, q_pids, q_camids = self.extract_feature(query_loader)
@@ -116,6 +117,12 @@ class ATTEvaluator(object):
         g_camids = np.append(q_camids, g_camids)
         print('Done, obtained {}-by-{} matrix'.format(gf.size(0), gf.size(1)))
         print("Computing distance matrix")
+        if rerank_stream:
+            # k-reciprocal re-ranking over column blocks (engine.rerank_metrics_streaming): the values of the device
+            # re_ranking below without its (q+g)^2 matrices, for any q + g.  Under torch.distributed every rank
+            # computes the whole result; nothing is sharded or exchanged.
+            print('Applying person re-ranking ...')
+            return _report(*engine.rerank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids))
         if stream:
             # column blocks of the distance GEMM and exact CMC / mAP without a sort (engine.rank_metrics_streaming); under
             # torch.distributed the gallery columns are sharded and only match keys and rank histograms travel

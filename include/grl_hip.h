@@ -38,7 +38,8 @@ const char* grl_last_error(void);
  * round 4: 6 with grl_bottleneck_tail_bf16, 7 grl_gemm_force_tile; round 5: 8 with grl_conv_gemm_f32_group;
  * round 6: 9 with the grl_jpeg_* entry points; 10: GRL_MATH_MXFP8 and the grl_mx_* entry points, additive only).
  * The column-block search / ranking entry points grl_topk_block .. grl_rank_finish were added at 10: they change no
- * struct layout or argument list, and a library without them fails to bind in _lib.load. */
+ * struct layout or argument list, and a library without them fails to bind in _lib.load.  So were the streaming
+ * re-ranking entry points grl_rrs_*. */
 #define GRL_ABI_VERSION 10
 int grl_abi_version(void);
 /* `waiter` (a hipStream_t) waits for everything enqueued on `signaler` so far: hipEventRecord + hipStreamWaitEvent on a
@@ -625,6 +626,34 @@ int grl_rerank_expand(const float* V, const int32_t* rank, const int32_t* lcnt, 
  * t = sum over the non-zero k of V2[i] (ascending) of min(V2[i][k], V2[j][k]);  out [nq][ng] */
 int grl_rerank_jaccard(const float* V2q, const float* V2T, const float* D, int N, int nq,
                        float lambda_value, float one_minus_lambda, float* out, void* stream);
+
+/* ---- streaming k-reciprocal re-ranking (rerank_stream.hip, engine.rerank_search / engine.rerank_metrics_streaming,
+ * DESIGN.md 4o): the values of the entry points above without any N x N or nq x ng array.  Same limits (k1 <= 20,
+ * k2 <= 8), no limit on N.  A SEGMENT is w sample columns [i0, i0 + w) on one side of the query/gallery boundary:
+ * S[r][i0 + c] = up[r * ldu + c] for r < nq and lo[(r - nq) * lo_rs + c * lo_cs] for r >= nq (unsquared distances). */
+/* colmax[c] = max_r S[r][i0+c]^2 and the D rows drows[c][j] = S[j][i0+c]^2 / colmax[c], j < nq + ng, bit-equal to
+ * grl_rerank_build's (colmax and drows point at sample i0) */
+int grl_rrs_segment_rows(const float* up, int64_t ldu, const float* lo, int64_t lo_rs, int64_t lo_cs, int nq, int ng,
+                         int w, float* colmax, float* drows, int64_t ldd, void* stream);
+/* lidx[i][0..lcnt[i]) = grl_rerank_krecip's sorted expansion list of every sample, from rank [N][ld] (the first
+ * ld >= k1 + 1 entries of each row of grl_row_argsort(D)) */
+int grl_rrs_lists(const int32_t* rank, int64_t ld, int N, int k1, int32_t* lcnt, int32_t* lidx, void* stream);
+/* lval[i][a] = V[i][lidx[i][a]] of grl_rerank_krecip for the segment's samples i = i0 .. i0 + w - 1 (colmax [N],
+ * lcnt / lidx / lval [N][256] indexed from sample 0) */
+int grl_rrs_weights(const float* up, int64_t ldu, const float* lo, int64_t lo_rs, int64_t lo_cs, int nq, int ng,
+                    int w, int i0, const float* colmax, const int32_t* lcnt, const int32_t* lidx, float* lval,
+                    void* stream);
+/* V2 = grl_rerank_expand's rows as CSR over all N samples, non-zero entries in ascending column order, bit-equal.
+ * row_ptr == NULL: cnt[i] = entries of row i; otherwise row_ptr [N+1] (int64 prefix sum of cnt) and col / val are
+ * filled. */
+int grl_rrs_expand(const int32_t* rank, int64_t ld, const int32_t* lcnt, const int32_t* lidx, const float* lval, int N,
+                   int k2, const int64_t* row_ptr, int32_t* cnt, int32_t* col, float* val, void* stream);
+/* in place: d [nq][ld] holds cosin_dist for gallery entries col0 .. col0 + ncols; each becomes grl_rerank_jaccard's
+ * out value.  q_ptr / q_col / q_val: the CSR of V2 (rows 0..nq-1 are read); csc_ptr [N+1] / csc_row / csc_val: for
+ * every k, the gallery samples j >= nq with V2[j][k] != 0 in ascending j and those values. */
+int grl_rrs_final(float* d, int64_t ld, int nq, int col0, int ncols, const float* colmax, const int64_t* q_ptr,
+                  const int32_t* q_col, const float* q_val, const int64_t* csc_ptr, const int32_t* csc_row,
+                  const float* csc_val, float lambda_value, float one_minus_lambda, void* stream);
 
 /* All weight re-layouts (and bf16 casts) of one training step in one launch: a table of gathers
  * dst[j] = src[base + i0*strides[0] + i1*strides[1] + i2*strides[2] + i3*strides[3]], j = ((i0*dims[1] + i1)*dims[2] +
