@@ -172,6 +172,11 @@ _SIGNATURES = {
     'grl_rrs_weights': ([_fp, _i64, _fp, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp],
                         C.c_int),
     'grl_rrs_expand': ([_fp, _i64, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp], C.c_int),
+    'grl_rrs_expand_rows': ([_fp, _i64, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp],
+                            C.c_int),
+    'grl_rrs_scan': ([_fp, C.c_int, _fp, _fp], C.c_int),
+    'grl_rrs_place': ([_fp, _fp, _i64, _fp, C.c_int, C.c_int, _fp, _fp, _fp], C.c_int),
+    'grl_rrs_transpose': ([_fp, _fp, _fp, C.c_int, C.c_int] + [_fp] * 6 + [_fp], C.c_int),
     'grl_rrs_final': ([_fp, _i64, C.c_int, C.c_int, C.c_int] + [_fp] * 7 + [C.c_float, C.c_float, _fp], C.c_int),
     'grl_row_argsort': ([_fp, _i64, C.c_int, C.c_int, _fp, _fp], C.c_int),
     'grl_row_argsort_workspace_bytes': ([C.c_int, C.c_int], _i64),

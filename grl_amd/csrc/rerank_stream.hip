@@ -7,12 +7,15 @@
 //   lists    each sample's expanded k-reciprocal list from the [N][K] rank lists (rr_expansion_list)
 //   pass A2  the same segments again: the weights V[i][lidx[i][a]] = exp(-D) / sum, kept sparse [N][256]
 //   expand   V2 rows as CSR (sorted union of the k2 nearest samples' lists, zero entries dropped)
+//   assemble row_ptr by an exclusive scan of the row counts, shards of other ranks placed at their offsets, and the
+//            gallery rows' CSC by a counting transpose whose result does not depend on the order of arrival
 //   final    per column block of the q x g distances: F = (1-lambda) * jaccard + lambda * D, in place
 //
 // Every value is produced by the same fp32 operations, in the same order, as in rerank.hip (the library
 // is built with -ffp-contract=off), so the final distances carry its bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include "../../include/grl_hip.h"
 #include "common.h"
 #include "rerank_common.h"
@@ -126,18 +129,19 @@ __device__ __forceinline__ float sparse_at(const int32_t* __restrict__ lcnt, con
 
 // One workgroup per sample i: V2[i] over the sorted union of its k2 nearest samples' lists,
 // V2[i][e] = (sum_u V[rows[u]][e]) / k2 in u order (rr_expand_kernel), non-zero entries only.
-// row_ptr == NULL: count them into cnt[i]; otherwise write them to col / val from row_ptr[i] on.
+// row_ptr == NULL: count them into cnt[i]; otherwise write them to col / val from row_ptr[i] on.  The grid covers
+// the samples row0 .. row0 + gridDim.x - 1; cnt and row_ptr are indexed by the sample.
 __global__ __launch_bounds__(256) void rrs_expand_kernel(const int32_t* __restrict__ rank, int64_t ld,
                                                          const int32_t* __restrict__ lcnt,
                                                          const int32_t* __restrict__ lidx,
-                                                         const float* __restrict__ lval, int k2,
+                                                         const float* __restrict__ lval, int k2, int row0,
                                                          const int64_t* __restrict__ row_ptr, int32_t* __restrict__ cnt,
                                                          int32_t* __restrict__ col, float* __restrict__ val) {
     __shared__ int rows[RR_K2MAX];
     __shared__ int offs[RR_K2MAX + 1];
     __shared__ int es[RRS_UNION];
     __shared__ int wcnt[4];
-    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i = row0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) {
         int o = 0;
         for (int t = 0; t < k2; ++t) {
@@ -266,6 +270,117 @@ __global__ __launch_bounds__(64) void rrs_final_kernel(float* __restrict__ d, in
     }
 }
 
+// ---- CSR / CSC assembly ----------------------------------------------------------------------------------
+constexpr int RRS_SCAN_T = 1024;              // one workgroup walks the counts, 1024 per step
+constexpr int RRS_RANK_CHUNK = 1024;          // rows of a CSC column staged in LDS at a time
+
+// ptr[i] = cnt[0] + .. + cnt[i-1], i <= n: shuffle scan inside each wave, the 16 wave totals through LDS and a
+// running carry from step to step.
+__global__ __launch_bounds__(RRS_SCAN_T) void rrs_scan_kernel(const int32_t* __restrict__ cnt, int n,
+                                                              int64_t* __restrict__ ptr) {
+    __shared__ long long wsum[RRS_SCAN_T / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    long long carry = 0;
+    for (int base = 0; base < n; base += RRS_SCAN_T) {
+        const int i = base + tid;
+        const long long v = i < n ? (long long)cnt[i] : 0;
+        long long inc = v;
+        for (int d = 1; d < 64; d <<= 1) {
+            const long long t = __shfl_up(inc, d);
+            if (lane >= d) inc += t;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        long long off = 0, tot = 0;
+        for (int w = 0; w < RRS_SCAN_T / 64; ++w) {
+            const long long sw = wsum[w];
+            if (w < wave) off += sw;
+            tot += sw;
+        }
+        if (i < n) ptr[i] = carry + off + inc - v;
+        carry += tot;
+        __syncthreads();
+    }
+    if (tid == 0) ptr[n] = carry;
+}
+
+// The entries of the rows row0 .. row1 - 1, packed from src[0] on, go to col / val at row_ptr[row0]
+__global__ __launch_bounds__(256) void rrs_place_kernel(const int32_t* __restrict__ src_col,
+                                                        const float* __restrict__ src_val, int64_t cap,
+                                                        const int64_t* __restrict__ row_ptr, int row0, int row1,
+                                                        int32_t* __restrict__ col, float* __restrict__ val) {
+    const int64_t o = row_ptr[row0], n = min(row_ptr[row1] - o, cap);
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+        col[o + e] = src_col[e];
+        val[o + e] = src_val[e];
+    }
+}
+
+// One wave per gallery sample j = nq + ..: ccnt[k] += 1 for every column k of its row (integer atomics: the counts
+// do not depend on the order)
+__global__ __launch_bounds__(256) void rrs_csc_count_kernel(const int64_t* __restrict__ row_ptr,
+                                                            const int32_t* __restrict__ col, int nq, int N,
+                                                            int32_t* __restrict__ ccnt) {
+    const int j = nq + blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (j >= N) return;
+    for (int64_t e = row_ptr[j] + lane; e < row_ptr[j + 1]; e += 64) {
+        const int k = col[e];
+        if ((unsigned)k < (unsigned)N) atomicAdd(&ccnt[k], 1);
+    }
+}
+
+// The same walk: every entry takes a slot of its column's range [csc_ptr[k], csc_ptr[k+1]) by counting ccnt[k]
+// down, so the column's entries arrive in no particular order; rrs_csc_order_kernel puts them in theirs.
+__global__ __launch_bounds__(256) void rrs_csc_scatter_kernel(const int64_t* __restrict__ row_ptr,
+                                                              const int32_t* __restrict__ col,
+                                                              const float* __restrict__ val, int nq, int N,
+                                                              const int64_t* __restrict__ csc_ptr,
+                                                              int32_t* __restrict__ ccnt, int32_t* __restrict__ tmp_row,
+                                                              float* __restrict__ tmp_val) {
+    const int j = nq + blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (j >= N) return;
+    for (int64_t e = row_ptr[j] + lane; e < row_ptr[j + 1]; e += 64) {
+        const int k = col[e];
+        if ((unsigned)k >= (unsigned)N) continue;
+        const int slot = atomicSub(&ccnt[k], 1) - 1;
+        if (slot < 0) continue;                           // cannot happen: the column was counted by the same walk
+        const int64_t o = csc_ptr[k] + slot;
+        tmp_row[o] = j;
+        tmp_val[o] = val[e];
+    }
+}
+
+// One workgroup per column k: a sample appears at most once in a column, so an entry's place in the ascending
+// order is the number of the column's samples below its own.  That number depends on the column's set of entries
+// alone, not on where the scatter left them.
+__global__ __launch_bounds__(256) void rrs_csc_order_kernel(const int64_t* __restrict__ csc_ptr,
+                                                            const int32_t* __restrict__ tmp_row,
+                                                            const float* __restrict__ tmp_val,
+                                                            int32_t* __restrict__ csc_row, float* __restrict__ csc_val) {
+    __shared__ int rows[RRS_RANK_CHUNK];
+    const int64_t s = csc_ptr[blockIdx.x], L = csc_ptr[blockIdx.x + 1] - s;
+    const int tid = threadIdx.x;
+    for (int64_t a0 = 0; a0 < L; a0 += 256) {
+        const int64_t a = a0 + tid;
+        const int r = a < L ? tmp_row[s + a] : 0;
+        int64_t below = 0;
+        for (int64_t c0 = 0; c0 < L; c0 += RRS_RANK_CHUNK) {
+            const int n = (int)min((int64_t)RRS_RANK_CHUNK, L - c0);
+            if (a0 == 0 || L > RRS_RANK_CHUNK) {          // a column of one chunk stays in LDS for every a0
+                __syncthreads();
+                for (int t = tid; t < n; t += 256) rows[t] = tmp_row[s + c0 + t];
+                __syncthreads();
+            }
+            if (a < L)
+                for (int t = 0; t < n; ++t) below += rows[t] < r;
+        }
+        if (a < L) {
+            csc_row[s + below] = r;
+            csc_val[s + below] = tmp_val[s + a];
+        }
+    }
+}
+
 Seg make_seg(const float* up, int64_t ldu, const float* lo, int64_t lrs, int64_t lcs, int nq, int ng, int w) {
     Seg s;
     s.up = up; s.ldu = ldu; s.lo = lo; s.lrs = lrs; s.lcs = lcs; s.nq = nq; s.ng = ng; s.w = w;
@@ -308,15 +423,58 @@ extern "C" int grl_rrs_weights(const float* up, int64_t ldu, const float* lo, in
     return grl_check_launch("grl_rrs_weights");
 }
 
-extern "C" int grl_rrs_expand(const int32_t* rank, int64_t ld, const int32_t* lcnt, const int32_t* lidx,
-                              const float* lval, int N, int k2, const int64_t* row_ptr, int32_t* cnt, int32_t* col,
-                              float* val, void* stream) {
+extern "C" int grl_rrs_expand_rows(const int32_t* rank, int64_t ld, const int32_t* lcnt, const int32_t* lidx,
+                                   const float* lval, int N, int k2, int row0, int nrows, const int64_t* row_ptr,
+                                   int32_t* cnt, int32_t* col, float* val, void* stream) {
     GRL_REQUIRE(rank && lcnt && lidx && lval && N > 0, "rrs_expand: bad args");
     GRL_REQUIRE(k2 >= 1 && k2 <= RR_K2MAX && k2 <= N && ld >= k2, "rrs_expand: 1 <= k2 <= 8, k2 <= N, ld >= k2");
     GRL_REQUIRE(row_ptr ? (col && val) : (cnt != nullptr), "rrs_expand: count needs cnt, fill needs col and val");
-    hipLaunchKernelGGL(rrs_expand_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, rank, ld, lcnt, lidx, lval, k2,
-                       row_ptr, cnt, col, val);
+    GRL_REQUIRE(row0 >= 0 && nrows >= 0 && (int64_t)row0 + nrows <= N, "rrs_expand: rows outside 0..N");
+    if (nrows == 0) return GRL_OK;
+    hipLaunchKernelGGL(rrs_expand_kernel, dim3(nrows), dim3(256), 0, (hipStream_t)stream, rank, ld, lcnt, lidx, lval,
+                       k2, row0, row_ptr, cnt, col, val);
     return grl_check_launch("grl_rrs_expand");
+}
+
+extern "C" int grl_rrs_expand(const int32_t* rank, int64_t ld, const int32_t* lcnt, const int32_t* lidx,
+                              const float* lval, int N, int k2, const int64_t* row_ptr, int32_t* cnt, int32_t* col,
+                              float* val, void* stream) {
+    return grl_rrs_expand_rows(rank, ld, lcnt, lidx, lval, N, k2, 0, N, row_ptr, cnt, col, val, stream);
+}
+
+extern "C" int grl_rrs_scan(const int32_t* cnt, int n, int64_t* ptr, void* stream) {
+    GRL_REQUIRE(ptr && n >= 0 && (cnt || n == 0), "rrs_scan: bad args");
+    hipLaunchKernelGGL(rrs_scan_kernel, dim3(1), dim3(RRS_SCAN_T), 0, (hipStream_t)stream, cnt, n, ptr);
+    return grl_check_launch("grl_rrs_scan");
+}
+
+extern "C" int grl_rrs_place(const int32_t* src_col, const float* src_val, int64_t cap, const int64_t* row_ptr, int row0,
+                             int row1, int32_t* col, float* val, void* stream) {
+    GRL_REQUIRE(row_ptr && col && val && cap >= 0 && row0 >= 0 && row1 >= row0, "rrs_place: bad args");
+    if (cap == 0 || row1 == row0) return GRL_OK;
+    GRL_REQUIRE(src_col && src_val, "rrs_place: null source");
+    const int blocks = (int)std::min<int64_t>((cap + 255) / 256, 65535);
+    hipLaunchKernelGGL(rrs_place_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src_col, src_val, cap,
+                       row_ptr, row0, row1, col, val);
+    return grl_check_launch("grl_rrs_place");
+}
+
+extern "C" int grl_rrs_transpose(const int64_t* row_ptr, const int32_t* col, const float* val, int nq, int N,
+                                 int32_t* ccnt, int32_t* tmp_row, float* tmp_val, int64_t* csc_ptr, int32_t* csc_row,
+                                 float* csc_val, void* stream) {
+    GRL_REQUIRE(row_ptr && col && val && ccnt && tmp_row && tmp_val && csc_ptr && csc_row && csc_val,
+                "rrs_transpose: null");
+    GRL_REQUIRE(nq >= 0 && N > nq, "rrs_transpose: needs 0 <= nq < N");
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(ccnt, 0, sizeof(int32_t) * (size_t)N, st) != hipSuccess)
+        return grl_fail(GRL_ELAUNCH, "rrs_transpose: hipMemsetAsync failed");
+    const int blocks = grl_ceil_div(N - nq, 4);
+    hipLaunchKernelGGL(rrs_csc_count_kernel, dim3(blocks), dim3(256), 0, st, row_ptr, col, nq, N, ccnt);
+    hipLaunchKernelGGL(rrs_scan_kernel, dim3(1), dim3(RRS_SCAN_T), 0, st, ccnt, N, csc_ptr);
+    hipLaunchKernelGGL(rrs_csc_scatter_kernel, dim3(blocks), dim3(256), 0, st, row_ptr, col, val, nq, N, csc_ptr, ccnt,
+                       tmp_row, tmp_val);
+    hipLaunchKernelGGL(rrs_csc_order_kernel, dim3(N), dim3(256), 0, st, csc_ptr, tmp_row, tmp_val, csc_row, csc_val);
+    return grl_check_launch("grl_rrs_transpose");
 }
 
 extern "C" int grl_rrs_final(float* d, int64_t ld, int nq, int col0, int ncols, const float* colmax,

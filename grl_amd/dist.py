@@ -217,6 +217,45 @@ def shard_rows(n, rank, world):
     return lo, lo + base + (1 if rank < extra else 0)
 
 
+def shard_bounds(n, world):
+    """[world + 1] offsets of shard_rows: rank r owns rows bounds[r] .. bounds[r + 1] - 1."""
+    return [shard_rows(n, r, world)[0] for r in range(world)] + [n]
+
+
+def all_gather_uneven(part, sizes, group=None):
+    """Rank-ordered all-gather of tensors whose first dimension differs from rank to rank: ``part`` holds
+    ``sizes[rank]`` rows, ``sizes`` (known to every rank) the row count of each rank.  The parts are padded to the
+    largest one, because gloo gathers equal shapes only (device tensors are staged through the host there, as in
+    every collective of this module); the result is the list of the ranks' parts, trimmed, on ``part``'s device.
+    A world in which nobody has a row exchanges nothing."""
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    sizes = [int(n) for n in sizes]
+    if len(sizes) != world or part.size(0) != sizes[rank]:
+        raise ValueError('all_gather_uneven: rank %d holds %d rows, sizes say %r' % (rank, part.size(0), sizes))
+    width = max(sizes)
+    if width == 0:
+        return [part.new_empty((0,) + tuple(part.shape[1:])) for _ in range(world)]
+    block = part.new_zeros((width,) + tuple(part.shape[1:]))
+    block[:sizes[rank]] = part
+    blocks = [torch.empty_like(block) for _ in range(world)]
+    _all_gather(blocks, block, group)
+    return [b[:n] for b, n in zip(blocks, sizes)]
+
+
+def gather_row_ranges(t, bounds, group=None):
+    """In place: ``t`` [n, ...] of which this rank has filled the rows bounds[rank] .. bounds[rank + 1] - 1
+    (``shard_bounds``) holds, afterwards, every rank's rows on every rank."""
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    if len(bounds) != world + 1 or bounds[0] != 0 or bounds[-1] != t.size(0):
+        raise ValueError('gather_row_ranges: %r does not split %d rows over %d ranks' % (bounds, t.size(0), world))
+    sizes = [bounds[r + 1] - bounds[r] for r in range(world)]
+    parts = all_gather_uneven(t[bounds[rank]:bounds[rank + 1]].contiguous(), sizes, group)
+    for r, p in enumerate(parts):
+        if r != rank:
+            t[bounds[r]:bounds[r + 1]] = p
+    return t
+
+
 def sharded_distmat(qf, gf, fn, group=None):
     """The evaluator's query x gallery matrix with the gallery rows sharded over the ranks
     (SURVEY.md 8(e)): every rank runs ``fn(qf, gf[lo:hi])`` -- an independent GEMM, e.g.

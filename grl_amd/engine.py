@@ -1586,17 +1586,19 @@ class _SampleBlocks(object):
     SEGMENTS on one side of the query/gallery boundary.  A query segment's lower rows are a row block of qg
     (gemm(qf[i0:i1], gf), read transposed), a gallery segment's come from a column block of gg; every entry has
     the full matrix's bits.  Without ``block_cols`` the width is the multiple of 32 samples whose three buffers
-    (upper, lower, D rows) fit ``block_bytes``."""
+    (upper, lower, D rows) fit ``block_bytes``.  ``lo`` / ``hi`` keep the spans to the samples [lo, hi) (a rank's
+    share); the width rule does not look at them, and no entry's bits depend on the spans."""
 
-    def __init__(self, qf, gf, block_cols=None, block_bytes=None):
+    def __init__(self, qf, gf, block_cols=None, block_bytes=None, lo=0, hi=None):
         nq, ng = qf.shape[0], gf.shape[0]
         self.nq, self.ng, self.N = nq, ng, nq + ng
+        hi = self.N if hi is None else hi
         if block_cols is None:
             budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
             block_cols = max(32, budget // (12 * self.N) // 32 * 32)
             block_cols = min(block_cols, max(32, -(-self.N // 64) * 32))          # never the whole N x N matrix
-        self.width = w = max(1, min(int(block_cols), self.N))
-        self.spans = [(i, min(i + w, self.N)) for i in range(0, self.N, w)]
+        self.width = w = max(1, min(int(block_cols), hi - lo))
+        self.spans = [(i, min(i + w, hi)) for i in range(lo, hi, w)]
         self.qq = _ColumnBlocks(qf, qf, 'euclidean', block_cols=min(w, nq))
         self.qg = _ColumnBlocks(qf, gf, 'cosine', block_cols=min(w, ng))
         self.gg = _ColumnBlocks(gf, gf, 'euclidean', block_cols=min(w, ng))
@@ -1633,9 +1635,16 @@ class _SampleBlocks(object):
 class _Rerank(object):
     """The sparse state of the k-reciprocal re-ranking of (qf, gf): colmax [N], the first K rank entries of every
     D row, the expansion lists with their weights ([N][256]), V2 as CSR over all samples and the gallery samples'
-    V2 as CSC.  Nothing of size N x N or nq x ng is allocated."""
+    V2 as CSC.  Nothing of size N x N or nq x ng is allocated.
+
+    Under torch.distributed (``grl_dist.is_distributed``) rank r of W owns the samples ``shard_rows(N, r, W)``: a
+    contiguous range, the first N % W ranks one sample longer.  The passes over the distance GEMM (A1, A2) and the
+    expansion run for the owned samples only; colmax, the rank lists, the weights, the row counts and the CSR
+    entries are all-gathered in between, each value exactly as its owner wrote it (nothing is reduced), so every
+    rank ends with the single-process state, bit for bit."""
 
     def __init__(self, qf, gf, k1, k2, lambda_value, block_cols=None, block_bytes=None):
+        from . import dist as grl_dist
         require_device(qf, 'qf'); require_device(gf, 'gf')
         nq, ng = qf.shape[0], gf.shape[0]
         N = nq + ng
@@ -1650,50 +1659,76 @@ class _Rerank(object):
         self.nq, self.ng, self.N = nq, ng, N
         self.k1, self.k2, self.K = int(k1), int(k2), max(int(k1) + 1, int(k2))
         self.lam, self.one_minus = float(lambda_value), 1 - lambda_value     # float32(1 - lambda), as rerank.py passes it
-        sb = _SampleBlocks(qf, gf, block_cols, block_bytes)
+        self.sharded = sharded = grl_dist.is_distributed()
+        rank, world = grl_dist._rank_world(None, None)
+        bounds = grl_dist.shard_bounds(N, world)
+        lo, hi = bounds[rank], bounds[rank + 1]
+        sb = _SampleBlocks(qf, gf, block_cols, block_bytes, lo, hi)
         dev, K = sb.qf.device, self.K
-        # pass A1: colmax and the first K entries of every D row (grl_row_argsort's order)
+        # pass A1, owned samples: colmax and the first K entries of every D row (grl_row_argsort's order).  A
+        # sample's colmax is the maximum over its whole column of S, which its owner holds: gathered, never reduced
         self.colmax = torch.empty(N, dtype=torch.float32, device=dev)
-        run_key = torch.full((N, K), -1, dtype=torch.int64, device=dev)
-        run_val = torch.full((N, K), float('inf'), dtype=torch.float32, device=dev)
+        run_key = torch.full((hi - lo, K), -1, dtype=torch.int64, device=dev)
+        run_val = torch.full((hi - lo, K), float('inf'), dtype=torch.float32, device=dev)
         for i0, i1 in sb.spans:
             dr = sb.d_rows(i0, i1, self.colmax)
-            _call('grl_topk_block', ptr(dr), N, None, 0, i1 - i0, N, 0, K, ptr(run_key[i0:]), ptr(run_val[i0:]))
+            _call('grl_topk_block', ptr(dr), N, None, 0, i1 - i0, N, 0, K, ptr(run_key[i0 - lo:]), ptr(run_val[i0 - lo:]))
         sb.drows = None
         del run_val
-        self.rank = (run_key & 0xffffffff).to(torch.int32)
+        self.rank = torch.empty((N, K), dtype=torch.int32, device=dev)
+        self.rank[lo:hi] = run_key & 0xffffffff
         del run_key
-        # expansion lists, then pass A2: their weights
+        if sharded:
+            grl_dist.gather_row_ranges(self.colmax, bounds)
+            grl_dist.gather_row_ranges(self.rank, bounds)
+        # expansion lists of ALL samples on every rank (a list reads the rank lists of arbitrary samples, so it comes
+        # after the gather; one wave per sample, no GEMM), then pass A2 for the owned samples: their weights
         self.lcnt = torch.empty(N, dtype=torch.int32, device=dev)
         self.lidx = torch.empty((N, RERANK_LMAX), dtype=torch.int32, device=dev)
         _call('grl_rrs_lists', ptr(self.rank), K, N, self.k1, ptr(self.lcnt), ptr(self.lidx))
         self.lval = torch.empty((N, RERANK_LMAX), dtype=torch.float32, device=dev)
         for i0, i1 in sb.spans:
-            for s0, s1, up, ldu, lo, lrs, lcs in sb.segments(i0, i1):
-                _call('grl_rrs_weights', ptr(up), ldu, ptr(lo), lrs, lcs, nq, ng, s1 - s0, s0, ptr(self.colmax),
+            for s0, s1, up, ldu, lo_, lrs, lcs in sb.segments(i0, i1):
+                _call('grl_rrs_weights', ptr(up), ldu, ptr(lo_), lrs, lcs, nq, ng, s1 - s0, s0, ptr(self.colmax),
                       ptr(self.lcnt), ptr(self.lidx), ptr(self.lval))
         del sb
-        # local query expansion: V2 as CSR (a counting launch sizes it)
+        if sharded:
+            grl_dist.gather_row_ranges(self.lval, bounds)
+        # local query expansion: V2 as CSR.  A counting launch over the owned rows, the counts of all ranks, their
+        # prefix sum; the fill then writes the owned rows at their final place and the other ranks' rows follow
         cnt = torch.empty(N, dtype=torch.int32, device=dev)
-        _call('grl_rrs_expand', ptr(self.rank), K, ptr(self.lcnt), ptr(self.lidx), ptr(self.lval), N, self.k2, None,
-              ptr(cnt), None, None)
-        self.row_ptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(cnt, 0, out=self.row_ptr[1:])
-        nnz = int(self.row_ptr[-1].item())
+        _call('grl_rrs_expand_rows', ptr(self.rank), K, ptr(self.lcnt), ptr(self.lidx), ptr(self.lval), N, self.k2, lo,
+              hi - lo, None, ptr(cnt), None, None)
+        if sharded:
+            grl_dist.gather_row_ranges(cnt, bounds)
+        self.row_ptr = torch.empty(N + 1, dtype=torch.int64, device=dev)
+        _call('grl_rrs_scan', ptr(cnt), N, ptr(self.row_ptr))
+        del cnt
+        at = self.row_ptr[torch.tensor(bounds + [nq], device=dev)].tolist()       # the one read-back: sizes to allocate
+        nnz, g0 = at[world], at[world + 1]
         self.col = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
         self.val = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)
-        _call('grl_rrs_expand', ptr(self.rank), K, ptr(self.lcnt), ptr(self.lidx), ptr(self.lval), N, self.k2,
-              ptr(self.row_ptr), None, ptr(self.col), ptr(self.val))
-        # inverted index of the gallery samples' rows: a stable sort by column keeps ascending j within a column
-        g0 = int(self.row_ptr[nq].item())
-        kcol = self.col[g0:nnz].long()
-        order = torch.sort(kcol, stable=True).indices
-        grow = torch.repeat_interleave(torch.arange(nq, N, dtype=torch.int32, device=dev), cnt[nq:].long(),
-                                       output_size=nnz - g0)
-        self.csc_row = grow[order].contiguous() if nnz > g0 else torch.zeros(1, dtype=torch.int32, device=dev)
-        self.csc_val = self.val[g0:nnz][order].contiguous() if nnz > g0 else torch.zeros(1, device=dev)
-        self.csc_ptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(torch.bincount(kcol, minlength=N), 0, out=self.csc_ptr[1:])
+        _call('grl_rrs_expand_rows', ptr(self.rank), K, ptr(self.lcnt), ptr(self.lidx), ptr(self.lval), N, self.k2, lo,
+              hi - lo, ptr(self.row_ptr), None, ptr(self.col), ptr(self.val))
+        if sharded:
+            sizes = [at[r + 1] - at[r] for r in range(world)]
+            cols = grl_dist.all_gather_uneven(self.col[at[rank]:at[rank + 1]], sizes)
+            vals = grl_dist.all_gather_uneven(self.val[at[rank]:at[rank + 1]], sizes)
+            for r in range(world):
+                if r != rank and sizes[r]:
+                    _call('grl_rrs_place', ptr(cols[r]), ptr(vals[r]), sizes[r], ptr(self.row_ptr), bounds[r],
+                          bounds[r + 1], ptr(self.col), ptr(self.val))
+            del cols, vals
+        # inverted index of the gallery samples' rows, ascending j within a column (grl_rrs_final's summation order)
+        n_g = max(nnz - g0, 1)
+        self.csc_ptr = torch.empty(N + 1, dtype=torch.int64, device=dev)
+        self.csc_row = torch.zeros(n_g, dtype=torch.int32, device=dev)
+        self.csc_val = torch.zeros(n_g, dtype=torch.float32, device=dev)
+        ccnt = torch.empty(N, dtype=torch.int32, device=dev)
+        tmp_row = torch.empty(n_g, dtype=torch.int32, device=dev)
+        tmp_val = torch.empty(n_g, dtype=torch.float32, device=dev)
+        _call('grl_rrs_transpose', ptr(self.row_ptr), ptr(self.col), ptr(self.val), nq, N, ptr(ccnt), ptr(tmp_row),
+              ptr(tmp_val), ptr(self.csc_ptr), ptr(self.csc_row), ptr(self.csc_val))
 
     def finish(self, d, col0, ncols):
         """d [nq][ncols] (cosin_dist of gallery entries col0 ..) becomes the re-ranked distances, in place."""
@@ -1711,7 +1746,8 @@ class _RerankBlocks(object):
             budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
             block_cols = max(256, budget // (4 * rr.nq) // 256 * 256)
             block_cols = min(block_cols, max(256, -(-rr.ng // 512) * 256))
-        self.cos = _ColumnBlocks(qf, gf, 'cosine', block_cols)
+        lo, hi, _ = _shard(rr.ng)                   # under torch.distributed: gallery columns sharded as in search
+        self.cos = _ColumnBlocks(qf, gf, 'cosine', block_cols, lo=lo, hi=hi)
         self.spans, self.qf, self.rr = self.cos.spans, self.cos.qf, rr
 
     def block(self, c0, c1):
@@ -1723,20 +1759,24 @@ def rerank_search(qf, gf, k, k1=20, k2=6, lambda_value=0.3, block_cols=None, blo
     qf, qf), pairwise_distance_tensor(gf, gf), k1, k2, lambda_value): ``(dist [nq, k] float32, idx [nq, k] int64)``,
     bit for bit ``rank_rows(F)[:, :k]`` and F at those indices (search's tie, NaN and padding rules), without F, the
     (q+g)^2 matrices or any nq x ng array.  k <= 1024, k1 <= 20, k2 <= 8; no limit on q + g.  Blocks follow
-    ``block_cols`` / ``block_bytes`` (GRL_SEARCH_BLOCK_BYTES).  Under torch.distributed every rank computes the full
-    result: nothing is sharded or exchanged."""
+    ``block_cols`` / ``block_bytes`` (GRL_SEARCH_BLOCK_BYTES).  Under torch.distributed the work is sharded over the
+    ranks: the sample passes by contiguous sample range with all-gathers of colmax, the rank lists,
+    the weights and the V2 rows in between, the final pass by gallery column with search's exchange of top-k
+    lists.  Every rank returns the full result, bit for bit the single-process one."""
     if not 1 <= int(k) <= SEARCH_K_MAX:
         raise ValueError('rerank_search: k must be in 1..%d (got %r)' % (SEARCH_K_MAX, k))
     rr = _Rerank(qf, gf, k1, k2, lambda_value, block_cols, block_bytes)
-    return _search_blocks(_RerankBlocks(qf, gf, rr, block_cols, block_bytes), rr.nq, int(k), False)
+    return _search_blocks(_RerankBlocks(qf, gf, rr, block_cols, block_bytes), rr.nq, int(k), rr.sharded)
 
 
 def rerank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, k1=20, k2=6, lambda_value=0.3, max_rank=100,
                              block_cols=None, block_bytes=None):
     """``rank_metrics(rank_rows(F), ...)`` for the re-ranked distances F of ``rerank_search``: (cmc[max_rank] float32,
     mAP float) with rank_metrics_streaming's contract (first hit and #matches exact, CMC equal, mAP within 1e-12,
-    at most 8192 gallery entries per query pid).  Under torch.distributed every rank computes the full result."""
+    at most 8192 gallery entries per query pid).  Under torch.distributed it is sharded as ``rerank_search`` is, the
+    final pass with rank_metrics_streaming's exchange (match keys and rank histograms); first hit, #matches and the
+    CMC are the single-process values on every rank, the mAP within the same 1e-12."""
     rr = _Rerank(qf, gf, k1, k2, lambda_value, block_cols, block_bytes)
     first, nhit, ap = _rank_blocks(_RerankBlocks(qf, gf, rr, block_cols, block_bytes), rr.nq, rr.ng, q_pids, g_pids,
-                                   q_camids, g_camids, False)
+                                   q_camids, g_camids, rr.sharded)
     return _cmc_map(first, nhit, ap, rr.ng, max_rank)

@@ -119,8 +119,8 @@ class ATTEvaluator(object):
         print("Computing distance matrix")
         if rerank_stream:
             # k-reciprocal re-ranking over column blocks (engine.rerank_metrics_streaming): the values of the device
-            # re_ranking below without its (q+g)^2 matrices, for any q + g.  Under torch.distributed every rank
-            # computes the whole result; nothing is sharded or exchanged.
+            # re_ranking below without its (q+g)^2 matrices, for any q + g.  Under torch.distributed the sample passes
+            # are sharded by sample range and the final pass by gallery column; every rank gets the full result.
             print('Applying person re-ranking ...')
             return _report(*engine.rerank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids))
         if stream:

@@ -39,7 +39,8 @@ const char* grl_last_error(void);
  * round 6: 9 with the grl_jpeg_* entry points; 10: GRL_MATH_MXFP8 and the grl_mx_* entry points, additive only).
  * The column-block search / ranking entry points grl_topk_block .. grl_rank_finish were added at 10: they change no
  * struct layout or argument list, and a library without them fails to bind in _lib.load.  So were the streaming
- * re-ranking entry points grl_rrs_*. */
+ * re-ranking entry points grl_rrs_*, the CSR / CSC assembly of its sharded form (grl_rrs_expand_rows, grl_rrs_scan,
+ * grl_rrs_place, grl_rrs_transpose) among them. */
 #define GRL_ABI_VERSION 10
 int grl_abi_version(void);
 /* `waiter` (a hipStream_t) waits for everything enqueued on `signaler` so far: hipEventRecord + hipStreamWaitEvent on a
@@ -648,6 +649,27 @@ int grl_rrs_weights(const float* up, int64_t ldu, const float* lo, int64_t lo_rs
  * filled. */
 int grl_rrs_expand(const int32_t* rank, int64_t ld, const int32_t* lcnt, const int32_t* lidx, const float* lval, int N,
                    int k2, const int64_t* row_ptr, int32_t* cnt, int32_t* col, float* val, void* stream);
+/* grl_rrs_expand for the samples row0 .. row0 + nrows - 1 only (a rank's share); cnt [N] and row_ptr [N+1] stay
+ * indexed by the sample, so a fill with the global row_ptr writes the rows at their final place in col / val */
+int grl_rrs_expand_rows(const int32_t* rank, int64_t ld, const int32_t* lcnt, const int32_t* lidx, const float* lval,
+                        int N, int k2, int row0, int nrows, const int64_t* row_ptr, int32_t* cnt, int32_t* col,
+                        float* val, void* stream);
+/* ptr [n+1] = exclusive prefix sum of cnt [n] (>= 0) in 64 bits, ptr[n] = the total: row_ptr from grl_rrs_expand's
+ * counts */
+int grl_rrs_scan(const int32_t* cnt, int n, int64_t* ptr, void* stream);
+/* the CSR entries of the rows row0 .. row1 - 1, packed from src_col[0] / src_val[0] on (a shard received from
+ * another rank, cap = entries the source buffers hold), are copied to col / val at row_ptr[row0]; at most cap and
+ * at most row_ptr[row1] - row_ptr[row0] entries move */
+int grl_rrs_place(const int32_t* src_col, const float* src_val, int64_t cap, const int64_t* row_ptr, int row0, int row1,
+                  int32_t* col, float* val, void* stream);
+/* The inverted index grl_rrs_final reads: the CSR rows nq .. N-1 transposed.  csc_ptr [N+1] (int64), and for every
+ * column k its samples j in ASCENDING order in csc_row with their values in csc_val (row_ptr[N] - row_ptr[nq]
+ * entries).  Integer atomics count the columns and hand out slots; the final place of an entry is the number of
+ * its column's samples below its own, so the result does not depend on the order of arrival.  Workspaces: ccnt [N]
+ * int32, tmp_row / tmp_val as large as csc_row / csc_val.  Column indices outside 0..N-1 are skipped. */
+int grl_rrs_transpose(const int64_t* row_ptr, const int32_t* col, const float* val, int nq, int N, int32_t* ccnt,
+                      int32_t* tmp_row, float* tmp_val, int64_t* csc_ptr, int32_t* csc_row, float* csc_val,
+                      void* stream);
 /* in place: d [nq][ld] holds cosin_dist for gallery entries col0 .. col0 + ncols; each becomes grl_rerank_jaccard's
  * out value.  q_ptr / q_col / q_val: the CSR of V2 (rows 0..nq-1 are read); csc_ptr [N+1] / csc_row / csc_val: for
  * every k, the gallery samples j >= nq with V2[j][k] != 0 in ascending j and those values. */

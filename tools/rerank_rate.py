@@ -5,7 +5,11 @@
   big:  10^4 queries x 10^5 gallery rows at 256-d, streaming only (the materialised path would need
         (q+g)^2 matrices of 48 GB each and refuses q + g > 16384)
 
-One JSON line per measurement.  Usage: python tools/rerank_rate.py [--case mars|big|all] [--reps R]"""
+One JSON line per measurement.  Usage: python tools/rerank_rate.py [--case mars|big|all] [--reps R] [--world W]
+
+--world W > 1 starts W ranks that share cuda:0 and talk over gloo (as `bench.py --gpus 2` under GRL_SINGLE_DEVICE=1)
+and times the sharded streaming paths only; every rank prints its own lines (`rank`, `world`).  On one device the
+ranks share the compute units: the wall time there says what the exchange costs, not what W devices would gain."""
 import argparse
 import contextlib
 import io
@@ -39,9 +43,12 @@ def measure(fn, reps):
     return best, peak
 
 
+_WHO = {}                         # rank / world of a --world run, added to every line
+
+
 def report(case, path, shape, sec, peak):
-    print(json.dumps({'case': case, 'path': path, 'nq': shape[0], 'ng': shape[1], 'dim': shape[2],
-                      'seconds': round(sec, 4), 'peak_gib': round(peak / 2 ** 30, 3)}), flush=True)
+    print(json.dumps(dict({'case': case, 'path': path, 'nq': shape[0], 'ng': shape[1], 'dim': shape[2],
+                           'seconds': round(sec, 4), 'peak_gib': round(peak / 2 ** 30, 3)}, **_WHO)), flush=True)
 
 
 def run(case, nq, ng, dim, reps, materialised):
@@ -63,15 +70,35 @@ def run(case, nq, ng, dim, reps, materialised):
     report(case, 'rerank_search k=100', shape, *measure(lambda: engine.rerank_search(qf, gf, 100), reps))
 
 
+def cases(a, materialised=True):
+    if a.case in ('mars', 'all'):
+        run('mars', 1980, 13290, 6144, a.reps, materialised)
+    if a.case in ('big', 'all'):
+        run('big', 10000, 100000, 256, 1, False)
+
+
+def rank_main(rank, a, port):
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
+    dist.init_process_group('gloo', rank=rank, world_size=a.world)
+    _WHO.update(rank=rank, world=a.world)
+    cases(a, materialised=False)
+    torch.cuda.synchronize()
+    dist.barrier()
+    dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--case', choices=['mars', 'big', 'all'], default='all')
     ap.add_argument('--reps', type=int, default=2)
+    ap.add_argument('--world', type=int, default=1)
     a = ap.parse_args()
-    if a.case in ('mars', 'all'):
-        run('mars', 1980, 13290, 6144, a.reps, True)
-    if a.case in ('big', 'all'):
-        run('big', 10000, 100000, 256, 1, False)
+    if a.world > 1:
+        import torch.multiprocessing as mp
+        mp.spawn(rank_main, args=(a, 41000 + os.getpid() % 1500), nprocs=a.world, join=True)
+    else:
+        cases(a)
 
 
 if __name__ == '__main__':
