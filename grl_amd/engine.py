@@ -86,6 +86,15 @@ def _new(shape, like):
     return torch.empty(shape, dtype=torch.float32, device=like.device)
 
 
+def _newl(shape, like):
+    return torch.empty(shape, dtype=like.dtype, device=like.device)
+
+
+def _k(name, t):
+    """Entry point for tensor ``t``'s storage type: the bf16 twin (train_bf16.hip / pointwise_bf16.hip) or the fp32 one."""
+    return name + '_bf16' if t.dtype == torch.bfloat16 else name
+
+
 # Raw uint8 clips are normalised on the device with the constants of the reference's loaders
 # (reid/data/dataloader.py:20,51: ToTensor + Normalize(mean, std)) -- inside the stem in eval
 # mode, by grl_normalize_u8 in train mode.  SURVEY.md 8(f) rank 4.
@@ -454,20 +463,49 @@ def _plan(module, cls):
 # ----------------------------------------------------------------------------
 # eval forward
 # ----------------------------------------------------------------------------
-def _conv_layer(x, c, n_img, H, W, stride=1, relu=True, res=None, **kw):
-    """x: [n_img*H*W][cin] channels-last.  Returns (y, Ho, Wo)."""
+def _newb(shape, like):
+    return torch.empty(shape, dtype=torch.bfloat16, device=like.device)
+
+
+FUSE_C64 = os.environ.get('GRL_CONV3X3_C64', '1') != '0'        # A/B and tests: 0 = layer 1's 3x3 convs on the generic kernel
+
+
+def conv3x3_c64_bf16(x, c, n_img, H, W, relu=True):
+    """Layer 1's 3x3 / stride 1, 64 -> 64 channels, W == 32 (resnets1.py:79-81): weights LDS-resident, each input pixel
+    staged once per tile (grl_conv3x3_c64_bf16)."""
+    y = _newb((n_img * H * W, 64), x)
+    _call('grl_conv3x3_c64_bf16', ptr(x), ptr(c.wb()), ptr(c.scale), ptr(c.shift), ptr(y), n_img, H, W, 1 if relu else 0)
+    return y
+
+
+def _gw(c, x, dp, K=None):
+    """(weight, math) of a generic conv / linear GEMM over the activation ``x``.  fp32 storage: the packed fp32 weight on
+    the mode's multiplier datapath (math None: gemm()'s default).  bf16 storage: the bf16 copy on MATH_BF16S or, with
+    ``dp`` = MATH_MXFP8, the MX-FP8 image of the weight's first ``K`` (default all) columns."""
+    if x.dtype != torch.bfloat16:
+        return c.w, None
+    return (c.wmx(K), MATH_MXFP8) if dp == MATH_MXFP8 else (c.wb(), MATH_BF16S)
+
+
+def _conv_layer(x, c, n_img, H, W, stride=1, relu=True, res=None, dp=MATH_BF16S, **kw):
+    """x: [n_img*H*W][cin] channels-last, fp32 or bf16 storage: the output follows it (``dp``: see _gw).
+    Returns (y, Ho, Wo)."""
+    if (x.dtype == torch.bfloat16 and FUSE_C64 and c.k == 3 and stride == 1 and c.cin == 64 and c.N == 64 and W == 32
+            and H % 8 == 0 and res is None and not kw and n_img * H * W * 128 < (1 << 32)):          # (32-bit byte offsets inside that kernel)
+        return conv3x3_c64_bf16(x, c, n_img, H, W, relu), H, W
+    wt, m = _gw(c, x, dp)
     if c.k == 1 and stride == 1:
         M = n_img * H * W
-        y = _new((M, c.N), x)
-        gemm(x, c.w, y, M, c.N, c.K, ldw=c.ldw, scale=c.scale, shift=c.shift, res=res, relu=relu, **kw)
+        y = _newl((M, c.N), x)
+        gemm(x, wt, y, M, c.N, c.K, ldw=c.ldw, scale=c.scale, shift=c.shift, res=res, relu=relu, math=m, **kw)
         return y, H, W
     pad = c.k // 2
     Ho = (H + 2 * pad - c.k) // stride + 1
     Wo = (W + 2 * pad - c.k) // stride + 1
     M = n_img * Ho * Wo
-    y = _new((M, c.N), x)
-    gemm(x, c.w, y, M, c.N, c.K, ldw=c.ldw, scale=c.scale, shift=c.shift, res=res, relu=relu,
-         conv=(H, W, c.cin, Ho, Wo, c.k, c.k, stride, pad), **kw)
+    y = _newl((M, c.N), x)
+    gemm(x, wt, y, M, c.N, c.K, ldw=c.ldw, scale=c.scale, shift=c.shift, res=res, relu=relu,
+         conv=(H, W, c.cin, Ho, Wo, c.k, c.k, stride, pad), math=m, **kw)
     return y, Ho, Wo
 
 
@@ -487,322 +525,6 @@ def _stem_pool_ok(x, n):
     """what grl_stem_pool_{f32,bf16} require beyond the frame geometry (one grid row per frame; 2-byte loads of u8
     rows, 8-byte loads of fp32 rows): otherwise the two-launch stem + max-pool path takes the batch"""
     return n <= 65535 and x.data_ptr() % (2 if x.dtype == torch.uint8 else 8) == 0
-
-
-def trunk_eval(plan, x, taps=None):
-    """x [n,3,H,W] NCHW -> channels-last [n*16*8][2048] (for 256x128 input)."""
-    n, _, H, W = x.shape
-    Hs, Ws = H // 2, W // 2
-    Hp, Wp = (Hs + 1) // 2, (Ws + 1) // 2
-    cur = _new((n * Hp * Wp, 64), x)
-    _stage('stem')
-    if FUSE_STEM_POOL_F32 and taps is None and W == 128 and H % 4 == 0 and _stem_pool_ok(x, n):
-        # stem + max-pool in one launch: the stem map never reaches HBM (grl_stem_pool_f32)
-        u8 = x.dtype == torch.uint8
-        _call('grl_stem_pool_f32', ptr(x), 1 if u8 else 0, ptr(input_mean_std(x.device)) if u8 else None,
-              ptr(plan.stem_scale), ptr(plan.stem_shift), ptr(cur), n, H, W, ptr(plan.stem_wq))
-    else:
-        stem = _new((n * Hs * Ws, 64), x)
-        if x.dtype == torch.uint8:           # raw pixels: normalised while the stem stages its patch
-            _call('grl_stem_conv7x7_u8', ptr(x), ptr(input_mean_std(x.device)), ptr(plan.stem_w),
-                  ptr(plan.stem_scale), ptr(plan.stem_shift), ptr(stem), n, H, W, 1, ptr(plan.stem_wp))
-        else:
-            _call('grl_stem_conv7x7', ptr(x), ptr(plan.stem_w), ptr(plan.stem_scale), ptr(plan.stem_shift),
-                  ptr(stem), n, H, W, 1, ptr(plan.stem_wp))
-        _call('grl_maxpool3x3s2', ptr(stem), ptr(cur), n, Hs, Ws, 64)
-        if taps is not None:
-            taps['stem'] = _to_nchw(stem, n, Hs, Ws)
-            taps['pool'] = _to_nchw(cur, n, Hp, Wp)
-        del stem
-    H, W = Hp, Wp
-    counts = (3, 4, 6, 3)
-    bi = 0
-    o1 = None
-    for li, nb in enumerate(counts):
-        _stage('layer%d' % (li + 1))       # (a fused tail computes the NEXT block's conv1: the first conv1 of layers 2 / 3 is booked here)
-        for _ in range(nb):
-            e = plan.blocks[bi]
-            bi += 1
-            s = e['stride']
-            if o1 is None:
-                o1, _, _ = _conv_layer(cur, e['c1'], n, H, W)
-            o2, Ho, Wo = _conv_layer(o1, e['c2'], n, H, W, stride=s)
-            if e['down'] is not None:
-                res, _, _ = _conv_layer(cur, e['down'], n, H, W, stride=s, relu=False)
-            else:
-                res = cur
-            nxt = plan.blocks[bi]['c1'] if bi < len(plan.blocks) else None
-            o1 = None
-            if FUSE_BNECK and nxt is not None and _bneck_tail_f32_ok(e['c3'], nxt, n * Ho * Wo):
-                # layers 1-2: conv3 + residual + ReLU AND the next block's conv1 in one launch, bit-identical to the two
-                # GEMM launches (fuse_f32.hip) -- the 4P-wide output is written once and never re-read
-                cur, o1 = bneck_tail_f32(o2, e['c3'], res, nxt, n * Ho * Wo)
-            else:
-                cur, _, _ = _conv_layer(o2, e['c3'], n, Ho, Wo, res=res)
-            H, W = Ho, Wo
-        if taps is not None:
-            taps['layer%d' % (li + 1)] = _to_nchw(cur, n, H, W)
-    return cur, H, W
-
-
-def gce_eval(plan, x4, b, t, taps=None):
-    """x4 [b*t*128][2048] -> (x_uncorr, x_corr) same shape, corr_map [b*t*128]."""
-    M = x4.shape[0]
-    _stage('gce')
-    x_glo = _new((b, 2048), x4)
-    _call('grl_group_mean', ptr(x4), ptr(x_glo), b, t * PIX, 2048, 2048, C.c_float(1.0), 0)
-    g = plan.glo_fc
-    glo = _new((b, 1024), x4)
-    gemm(x_glo, g.w, glo, b, 1024, 2048, scale=g.scale, shift=g.shift, relu=True, kblock=_kb())
-    # W.[x; g] = Wx.x + Wg.g : the broadcast-concat of basebranch.py:59-61 becomes a
-    # per-clip bias added inside the accumulator epilogue.
-    c0 = plan.corr0
-    gb = _new((b, 1024), x4)
-    gemm(glo, c0.w[:, 2048:], gb, b, 1024, 1024, ldw=3072, kblock=_kb())
-    h1 = _new((M, 1024), x4)
-    gemm(x4, c0.w, h1, M, 1024, 2048, ldw=3072, gbias=gb, rows_per_group=t * PIX,
-         scale=c0.scale, shift=c0.shift, relu=False)
-    c2 = plan.corr2
-    h2 = _new((M, 256), x4)
-    gemm(h1, c2.w, h2, M, 256, 1024, scale=c2.scale, shift=c2.shift, relu=True)
-    cmap = _new((M,), x4)
-    xc = _new((M, 2048), x4)
-    xu = _new((M, 2048), x4)
-    _call('grl_gce_gate', ptr(h2), ptr(plan.corr5_w), ptr(plan.corr6_scale), ptr(plan.corr6_shift),
-          ptr(x4), ptr(cmap), ptr(xc), ptr(xu), M, 256, 2048)
-    if taps is not None:
-        taps['x_glo'], taps['glo'] = x_glo, glo
-        taps['corr_map'] = cmap.view(b * t, 1, 16, 8)
-    return xu, xc, cmap
-
-
-# The two TRL directions (forward / backward in time, grl_model.py:170-208) are independent recurrences over
-# their own weights: each step's GEMMs have M = B*128 rows -- 128..256 tiles, half a chip -- and six small
-# latency-bound kernels.  They are issued on two HIP streams (fork after the shared inputs, join before the
-# pooled outputs) so the chip runs one direction's GEMM next to the other's small kernels.  Same kernels,
-# same per-direction order, per-direction scratch: bit-identical to the single-stream order
-# (GRL_TRL_STREAMS=0, or taps requested).
-TRL_STREAMS = os.environ.get('GRL_TRL_STREAMS', '1') != '0'
-TRL_GROUP = os.environ.get('GRL_TRL_GROUP', '0') != '0'       # bf16 storage: conv1 / conv2 of both directions as grouped launches (measured slower: see below)
-# Round 5 (eval): each direction's ATTENTION branch of a step -- the f1 GEMM with its squared-difference epilogue and the
-# three latency-bound kernels behind it (partial-sum GAP, the two channel-attention layers) -- only reads the step's memo
-# and feeds f_corr, never the recurrence; in stream order it still sat in front of the step's add / conv1 / conv2 / conv3.
-# It goes to a stream of its own (one per direction), forked from the direction's stream where the memo is ready, so the
-# recurrence's GEMMs run next to it (knock-out bound: the small kernels cost 0.27 ms of configs[2] although nothing waits
-# for their results before the join; measured configs[2] 10.03 -> 9.93-9.97 ms).  bf16 storage only: the exact-fp32 step
-# LOSES 1 % to it (14.47 -> 14.63 ms; with only the small kernels moved 14.60) -- its f1 GEMMs are four times longer and
-# sharing CUs costs them more than the bubbles they fill.  Same kernels on the same operands: bit-identical.
-# GRL_TRL_ATT_STREAMS=0: the attention branch stays on its direction's stream.
-TRL_ATT_STREAMS = os.environ.get('GRL_TRL_ATT_STREAMS', '1') != '0'
-_side_streams = {}
-_att_streams = {}
-
-
-class _TrlFork(object):
-    """streams[di] for the two TRL directions; ``with fork.on(di):`` routes launches and allocations;
-    ``with fork.att_on(di):`` routes to the direction's attention stream (ordered after everything issued so far on
-    the direction's own stream)."""
-
-    def __init__(self, dev, enable, att=False):
-        self.main = torch.cuda.current_stream(dev)
-        self.two = bool(enable and TRL_STREAMS)
-        self.att = None
-        self.held = []          # tensors an attention stream reads: kept alive until the join
-        if self.two:
-            key = (dev.index if dev.index is not None else torch.cuda.current_device())
-            if key not in _side_streams:
-                _side_streams[key] = torch.cuda.Stream(dev)
-            self.side = _side_streams[key]
-            if att and TRL_ATT_STREAMS:
-                if key not in _att_streams:
-                    _att_streams[key] = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
-                self.att = _att_streams[key]
-        else:
-            self.side = self.main
-
-    def att_on(self, di, *reads):
-        """``reads``: tensors of the direction's stream the branch reads (held until the join)."""
-        if self.att is None:
-            return self.on(di)
-        ev = torch.cuda.Event()
-        ev.record(self.side if di == 1 else self.main)
-        self.att[di].wait_event(ev)
-        self.held.extend(r for r in reads if r is not None)
-        return torch.cuda.stream(self.att[di])
-
-    def fork(self):
-        if self.two:
-            ev = torch.cuda.Event()
-            ev.record(self.main)
-            self.side.wait_event(ev)
-
-    def on(self, di):
-        return torch.cuda.stream(self.side if di == 1 else self.main)
-
-    def side_to_main(self):
-        """main waits for everything issued on the side stream so far"""
-        if self.two:
-            ev = torch.cuda.Event()
-            ev.record(self.side)
-            self.main.wait_event(ev)
-
-    def main_to_side(self):
-        """the side stream waits for everything issued on the main stream so far"""
-        if self.two:
-            ev = torch.cuda.Event()
-            ev.record(self.main)
-            self.side.wait_event(ev)
-
-    def join(self, *side_tensors):
-        if self.two:
-            for st in (self.side,) + (tuple(self.att) if self.att is not None else ()):
-                ev = torch.cuda.Event()
-                ev.record(st)
-                self.main.wait_event(ev)
-                if st is not self.side:
-                    # blocks the attention streams read / write were allocated on the DIRECTION streams: once `held`
-                    # is dropped the allocator may hand a side-stream block to the side stream's next launch, so the
-                    # side stream is ordered behind the attention streams as well (main already is)
-                    self.side.wait_event(ev)
-            for x in side_tensors:
-                x.record_stream(self.main)
-            self.held = []
-
-
-def trl_eval(plan, xu, xc, b, t, taps=None):
-    """xu, xc [b][t][128][2048] (flat) -> f_uncorr [b][2048], f_corr [b][t][2048]."""
-    Cc = 2048
-    frame = PIX * Cc
-    Mb = b * PIX
-    _stage('trl')
-    memo0 = _new((Mb, Cc), xu)
-    _call('grl_temporal_mean', ptr(xu), ptr(memo0), b, t, frame)
-    gapc = _new((b * t, Cc), xu)
-    _call('grl_group_mean', ptr(xc), ptr(gapc), b * t, PIX, Cc, Cc, C.c_float(1.0), 0)
-    # conv_f2(x_corr_i) does not depend on the recurrence: one GEMM over all T per direction
-    fk = _TrlFork(xu.device, taps is None and len(plan.dirs) == 2)
-    fk.fork()
-    f2, fc, scr = [], [], []
-    for di, d in enumerate(plan.dirs):
-        with fk.on(di):
-            y = _new((b * t * PIX, Cc), xu)
-            gemm(xc, d['f2'].w, y, b * t * PIX, Cc, Cc, shift=d['f2'].shift, relu=True)
-            f2.append(y)
-            # per-direction accumulators / scratch (a + b == b + a: summing the two directions' f_corr
-            # contributions at the join gives the bits the shared accumulator got in either arrival order)
-            # (two streams: each direction has its own accumulator and writes every (clip, frame) row exactly once -- no
-            #  zero fill, the attention kernel stores instead of accumulating)
-            fc.append(_new((b, t, Cc), xu) if fk.two else (torch.zeros((b, t, Cc), dtype=torch.float32, device=xu.device) if di == 0 else fc[0]))
-            scr.append((_new((b, Cc), xu), _new((Mb // 32, Cc), xu), _new((b, 128), xu)))
-    memo = [memo0, memo0]
-    catte = _new((b, Cc), xu) if taps is not None else None
-    for i in range(t):
-        for di, d in enumerate(plan.dirs):
-            ti = i if di == 0 else t - 1 - i
-            with fk.on(di):
-                dvec, dpart, hid = scr[di]
-                fcorr = fc[di]
-                # d = GAP((ReLU(conv_f1(memo)) - f2_t)^2): the squared difference is reduced in the GEMM
-                # epilogue (32-row partial sums), conv_f1's output never reaches HBM (grl_model.py:146-149)
-                if FUSE_TRL_SQDIFF:
-                    gemm(memo[di], d['f1'].w, dpart, Mb, Cc, Cc, shift=d['f1'].shift, epilogue=EPI_SQDIFF,
-                         res=f2[di][ti * PIX:], res_rows=PIX, res_gstride=t * PIX)
-                    _call('grl_group_mean', ptr(dpart), ptr(dvec), b, PIX // 32, Cc, Cc, C.c_float(1.0 / 32.0), 0)
-                else:
-                    f1 = _new((Mb, Cc), xu)
-                    gemm(memo[di], d['f1'].w, f1, Mb, Cc, Cc, shift=d['f1'].shift, relu=True)
-                    _call('grl_sqdiff_mean', ptr(f1), ptr(f2[di][ti * PIX:]), ptr(dvec), b, PIX, Cc, t * frame)
-                _call('grl_channel_atte', ptr(dvec), ptr(d['w1']), ptr(d['w2t']), ptr(gapc[ti:]), t * Cc,
-                      ptr(catte), ptr(fcorr.view(b * t, Cc)[ti:]), t * Cc, 0 if fk.two else 1, b, Cc, d['w1'].shape[0], ptr(hid))
-                if taps is not None:
-                    taps.setdefault(('fwd', 'bwd')[di] + '_catte', []).append(catte.clone())
-            with fk.on(di):                                     # the recurrence
-                s = _new((Mb, Cc), xu)
-                _call('grl_add_strided', ptr(memo[di]), ptr(xu.view(-1)[ti * frame:]), ptr(s), b, frame, t * frame)
-                o = _new((Mb, 512), xu)
-                c1, c2, c3 = d['c1'], d['c2'], d['c3']
-                gemm(s, c1.w, o, Mb, 512, Cc, scale=c1.scale, shift=c1.shift, relu=True)
-                o2 = _new((Mb, 512), xu)
-                gemm(o, c2.w, o2, Mb, 512, 512, scale=c2.scale, shift=c2.shift, relu=True)
-                nm = _new((Mb, Cc), xu)
-                gemm(o2, c3.w, nm, Mb, Cc, 512, scale=c3.scale, shift=c3.shift, res=s, relu=True)
-                memo[di] = nm
-    fk.join(memo[1], fc[1])
-    fcorr = fc[0]
-    if fk.two:
-        fcorr = _new((b, t, Cc), xu)
-        _call('grl_add_strided', ptr(fc[0]), ptr(fc[1]), ptr(fcorr), 1, b * t * Cc, 0)
-    f_uncorr = _new((b, Cc), xu)
-    _call('grl_group_mean', ptr(memo[0]), ptr(f_uncorr), b, PIX, Cc, Cc, C.c_float(1.0), 0)
-    _call('grl_group_mean', ptr(memo[1]), ptr(f_uncorr), b, PIX, Cc, Cc, C.c_float(1.0), 1)
-    if taps is not None:
-        taps['f_uncorr'], taps['f_corr'] = f_uncorr, fcorr
-    return f_uncorr, fcorr
-
-
-def _grl_eval(model, inputs, taps=None, out_uncorr=None, ld_uncorr=2048):
-    if _math[0] in (MATH_BF16S, MATH_MXFP8):
-        return _grl_eval_bf16s(model, inputs, taps, out_uncorr, ld_uncorr, dp=_math[0])
-    plan = _plan(model, GrlEvalPlan)
-    b, t, c, h, w = inputs.shape
-    if (c, h, w) != (3, 256, 128):
-        raise ValueError('GRL expects clips of [B,T,3,256,128] (got %s)' % (tuple(inputs.shape),))
-    x = inputs.contiguous().view(b * t, c, h, w)
-    x4, _, _ = trunk_eval(plan, x, taps)
-    xu, xc, _ = gce_eval(plan, x4, b, t, taps)
-    del x4
-    f_uncorr, f_corr = trl_eval(plan, xu, xc, b, t, taps)
-    _stage('tail')
-    x_corr = _new((b, t, 2048), inputs)
-    _call('grl_affine_l2norm', ptr(f_corr), ptr(plan.corr_bn[0]), ptr(plan.corr_bn[1]), ptr(x_corr),
-          b * t, 2048, 2048)
-    x_uncorr = out_uncorr if out_uncorr is not None else _new((b, 2048), inputs)
-    _call('grl_affine_l2norm', ptr(f_uncorr), ptr(plan.uncorr_bn[0]), ptr(plan.uncorr_bn[1]),
-          ptr(x_uncorr), b, 2048, ld_uncorr)
-    return x_uncorr, x_corr
-
-
-# ----------------------------------------------------------------------------
-# bf16-storage eval forward (BASELINE configs[2])
-# ----------------------------------------------------------------------------
-def _newb(shape, like):
-    return torch.empty(shape, dtype=torch.bfloat16, device=like.device)
-
-
-FUSE_C64 = os.environ.get('GRL_CONV3X3_C64', '1') != '0'        # A/B and tests: 0 = layer 1's 3x3 convs on the generic kernel
-
-
-def conv3x3_c64_bf16(x, c, n_img, H, W, relu=True):
-    """Layer 1's 3x3 / stride 1, 64 -> 64 channels, W == 32 (resnets1.py:79-81): weights LDS-resident, each input pixel
-    staged once per tile (grl_conv3x3_c64_bf16)."""
-    y = _newb((n_img * H * W, 64), x)
-    _call('grl_conv3x3_c64_bf16', ptr(x), ptr(c.wb()), ptr(c.scale), ptr(c.shift), ptr(y), n_img, H, W, 1 if relu else 0)
-    return y
-
-
-def _gw(c, dp, K=None):
-    """(weight, math) of a generic bf16-storage GEMM on datapath ``dp`` (MATH_BF16S or MATH_MXFP8)"""
-    return (c.wmx(K), MATH_MXFP8) if dp == MATH_MXFP8 else (c.wb(), MATH_BF16S)
-
-
-def _conv_b16(x, c, n_img, H, W, stride=1, relu=True, res=None, dp=MATH_BF16S, **kw):
-    if (FUSE_C64 and c.k == 3 and stride == 1 and c.cin == 64 and c.N == 64 and W == 32 and H % 8 == 0 and res is None
-            and not kw and n_img * H * W * 128 < (1 << 32)):          # (32-bit byte offsets inside that kernel)
-        return conv3x3_c64_bf16(x, c, n_img, H, W, relu), H, W
-    wt, m = _gw(c, dp)
-    if c.k == 1 and stride == 1:
-        M = n_img * H * W
-        y = _newb((M, c.N), x)
-        gemm(x, wt, y, M, c.N, c.K, ldw=c.ldw, scale=c.scale, shift=c.shift, res=res, relu=relu,
-             math=m, **kw)
-        return y, H, W
-    pad = c.k // 2
-    Ho, Wo = (H + 2 * pad - c.k) // stride + 1, (W + 2 * pad - c.k) // stride + 1
-    M = n_img * Ho * Wo
-    y = _newb((M, c.N), x)
-    gemm(x, wt, y, M, c.N, c.K, ldw=c.ldw, scale=c.scale, shift=c.shift, res=res, relu=relu,
-         conv=(H, W, c.cin, Ho, Wo, c.k, c.k, stride, pad), math=m, **kw)
-    return y, Ho, Wo
 
 
 FUSE_TAIL_L23 = os.environ.get('GRL_FUSE_TAIL_L23', '0') != '0'   # the layer 2 -> 3 tail (P 128, 4P 512, P' 256) fused too: measured slower
@@ -870,197 +592,279 @@ def bneck_tail_f32(t2, c3, res, c1n, M):
     return y, u
 
 
-def _grl_eval_bf16s(model, inputs, taps=None, out_uncorr=None, ld_uncorr=2048, dp=MATH_BF16S):
-    """Same launch order as _grl_eval with bf16 activations in HBM: stem -> trunk -> GCE ->
-    TRL memo are bf16 tensors, every GEMM is the bf16-storage datapath, reductions land in
-    fp32 vectors, the BN1d + L2 tail is the fp32 one.  ``dp`` = MATH_MXFP8: the generic conv / linear GEMMs
-    (those issued through gemm() with a bf16-storage weight) run on MX-FP8 operands instead; the fused kernels and
-    the fp32 per-clip linears do not change, and the TRL f1 GEMM takes the unfused squared-difference route."""
+def trunk_eval(plan, x, dp, taps=None):
+    """x [n,3,H,W] NCHW, float32 or raw uint8 -> channels-last [n*16*8][2048] (for 256x128 input): fp32, or bf16 on the
+    bf16-storage datapaths (``dp`` = MATH_BF16S / MATH_MXFP8)."""
+    n, _, H, W = x.shape
+    Hs, Ws = H // 2, W // 2
+    Hp, Wp = (Hs + 1) // 2, (Ws + 1) // 2
+    b16 = dp in (MATH_BF16S, MATH_MXFP8)
+    # (the stem's entry points follow the _bf16 suffix rule of _k; its one-launch form, its switch and its packed weights do not)
+    fuse_stem, pool, wpool, wstem = ((FUSE_STEM_POOL, 'grl_stem_pool_bf16', plan.stem_wpb, plan.stem_wpb) if b16 else
+                                     (FUSE_STEM_POOL_F32, 'grl_stem_pool_f32', plan.stem_wq, plan.stem_wp))
+    cur = (_newb if b16 else _new)((n * Hp * Wp, 64), x)
+    _stage('stem')
+    if fuse_stem and taps is None and W == 128 and H % 4 == 0 and _stem_pool_ok(x, n):
+        # stem + max-pool in one launch: the stem map never reaches HBM (grl_stem_pool_f32 / grl_stem_pool_bf16)
+        u8 = x.dtype == torch.uint8
+        _call(pool, ptr(x), 1 if u8 else 0, ptr(input_mean_std(x.device)) if u8 else None,
+              ptr(plan.stem_scale), ptr(plan.stem_shift), ptr(cur), n, H, W, ptr(wpool))
+    else:
+        stem = _newl((n * Hs * Ws, 64), cur)
+        if x.dtype == torch.uint8:           # raw pixels: normalised while the stem stages its patch
+            _call(_k('grl_stem_conv7x7_u8', stem), ptr(x), ptr(input_mean_std(x.device)), ptr(plan.stem_w),
+                  ptr(plan.stem_scale), ptr(plan.stem_shift), ptr(stem), n, H, W, 1, ptr(wstem))
+        else:
+            _call(_k('grl_stem_conv7x7', stem), ptr(x), ptr(plan.stem_w), ptr(plan.stem_scale), ptr(plan.stem_shift),
+                  ptr(stem), n, H, W, 1, ptr(wstem))
+        _call(_k('grl_maxpool3x3s2', stem), ptr(stem), ptr(cur), n, Hs, Ws, 64)
+        if taps is not None:
+            taps['stem'] = _to_nchw(stem, n, Hs, Ws)
+            taps['pool'] = _to_nchw(cur, n, Hp, Wp)
+        del stem
+    H, W = Hp, Wp
+    counts = (3, 4, 6, 3)
+    bi = 0
+    o1 = None
+    for li, nb in enumerate(counts):
+        _stage('layer%d' % (li + 1))       # (a fused tail computes the NEXT block's conv1: the first conv1 of layers 2 / 3 is booked here)
+        for _ in range(nb):
+            e = plan.blocks[bi]
+            bi += 1
+            s = e['stride']
+            if o1 is None:
+                o1, _, _ = _conv_layer(cur, e['c1'], n, H, W, dp=dp)
+            o2, Ho, Wo = _conv_layer(o1, e['c2'], n, H, W, stride=s, dp=dp)
+            nxt = plan.blocks[bi]['c1'] if bi < len(plan.blocks) else None
+            M = n * Ho * Wo
+            fuse = FUSE_BNECK and nxt is not None and (_bneck_tail_ok if b16 else _bneck_tail_f32_ok)(e['c3'], nxt, M)
+            o1 = None
+            if fuse and b16 and FUSE_DOWN and _bneck_down_ok(e['c3'], nxt, e['down'], s):
+                # layer 1's first block: the downsample branch too -- its 4P-wide output is neither written nor re-read
+                cur, o1 = bneck_tail_bf16(o2, e['c3'], None, nxt, M, down=e['down'], x0=cur)
+            else:
+                res = _conv_layer(cur, e['down'], n, H, W, stride=s, relu=False, dp=dp)[0] if e['down'] is not None else cur
+                if fuse:
+                    # layers 1-2: conv3 + residual + ReLU AND the next block's conv1 in one launch -- the 4P-wide output is
+                    # written once (the next block's residual) and never re-read (fuse_bf16.hip; fuse_f32.hip: bit-identical
+                    # to the two GEMM launches)
+                    cur, o1 = (bneck_tail_bf16 if b16 else bneck_tail_f32)(o2, e['c3'], res, nxt, M)
+                else:
+                    cur, _, _ = _conv_layer(o2, e['c3'], n, Ho, Wo, res=res, dp=dp)
+            H, W = Ho, Wo
+        if taps is not None:
+            taps['layer%d' % (li + 1)] = _to_nchw(cur, n, H, W)
+    return cur, H, W
+
+
+def gce_eval(plan, x4, b, t, dp, taps=None):
+    """x4 [b*t*128][2048] -> (x_uncorr, x_corr) same shape and storage, corr_map [b*t*128] (fp32, as every per-clip
+    vector)."""
+    M = x4.shape[0]
+    _stage('gce')
+    x_glo = _new((b, 2048), x4)
+    _call(_k('grl_group_mean', x4), ptr(x4), ptr(x_glo), b, t * PIX, 2048, 2048, C.c_float(1.0), 0)
+    # (the per-clip linears: fp32 operands on every datapath -- gemm()'s default math is MATH_F32 on bf16 storage)
+    g = plan.glo_fc
+    glo = _new((b, 1024), x4)
+    gemm(x_glo, g.w, glo, b, 1024, 2048, scale=g.scale, shift=g.shift, relu=True, kblock=_kb())
+    # W.[x; g] = Wx.x + Wg.g : the broadcast-concat of basebranch.py:59-61 becomes a
+    # per-clip bias added inside the accumulator epilogue.
+    c0 = plan.corr0
+    gb = _new((b, 1024), x4)
+    gemm(glo, c0.w[:, 2048:], gb, b, 1024, 1024, ldw=3072, kblock=_kb())
+    h1 = _newl((M, 1024), x4)
+    w0, m0 = _gw(c0, x4, dp, 2048)              # (the x4 half of corr0's [1024][3072] weight)
+    gemm(x4, w0, h1, M, 1024, 2048, ldw=3072, gbias=gb, rows_per_group=t * PIX,
+         scale=c0.scale, shift=c0.shift, relu=False, math=m0)
+    c2 = plan.corr2
+    h2 = _newl((M, 256), x4)
+    w2, m2 = _gw(c2, x4, dp)
+    gemm(h1, w2, h2, M, 256, 1024, scale=c2.scale, shift=c2.shift, relu=True, math=m2)
+    cmap = _new((M,), x4)
+    xc = _newl((M, 2048), x4)
+    xu = _newl((M, 2048), x4)
+    _call(_k('grl_gce_gate', x4), ptr(h2), ptr(plan.corr5_w), ptr(plan.corr6_scale), ptr(plan.corr6_shift),
+          ptr(x4), ptr(cmap), ptr(xc), ptr(xu), M, 256, 2048)
+    if taps is not None:
+        taps['x_glo'], taps['glo'] = x_glo, glo
+        taps['corr_map'] = cmap.view(b * t, 1, 16, 8)
+    return xu, xc, cmap
+
+
+# The two TRL directions (forward / backward in time, grl_model.py:170-208) are independent recurrences over
+# their own weights: each step's GEMMs have M = B*128 rows -- 128..256 tiles, half a chip -- and six small
+# latency-bound kernels.  They are issued on two HIP streams (fork after the shared inputs, join before the
+# pooled outputs) so the chip runs one direction's GEMM next to the other's small kernels.  Same kernels,
+# same per-direction order, per-direction scratch: bit-identical to the single-stream order
+# (GRL_TRL_STREAMS=0, or taps requested).
+TRL_STREAMS = os.environ.get('GRL_TRL_STREAMS', '1') != '0'
+# Round 5 (eval): each direction's ATTENTION branch of a step -- the f1 GEMM with its squared-difference epilogue and the
+# three latency-bound kernels behind it (partial-sum GAP, the two channel-attention layers) -- only reads the step's memo
+# and feeds f_corr, never the recurrence; in stream order it still sat in front of the step's add / conv1 / conv2 / conv3.
+# It goes to a stream of its own (one per direction), forked from the direction's stream where the memo is ready, so the
+# recurrence's GEMMs run next to it (knock-out bound: the small kernels cost 0.27 ms of configs[2] although nothing waits
+# for their results before the join; measured configs[2] 10.03 -> 9.93-9.97 ms).  bf16 storage only: the exact-fp32 step
+# LOSES 1 % to it (14.47 -> 14.63 ms; with only the small kernels moved 14.60) -- its f1 GEMMs are four times longer and
+# sharing CUs costs them more than the bubbles they fill.  Same kernels on the same operands: bit-identical.
+# GRL_TRL_ATT_STREAMS=0: the attention branch stays on its direction's stream.
+TRL_ATT_STREAMS = os.environ.get('GRL_TRL_ATT_STREAMS', '1') != '0'
+_side_streams = {}
+_att_streams = {}
+
+
+class _TrlFork(object):
+    """streams[di] for the two TRL directions; ``with fork.on(di):`` routes launches and allocations;
+    ``with fork.att_on(di):`` routes to the direction's attention stream (ordered after everything issued so far on
+    the direction's own stream)."""
+
+    def __init__(self, dev, enable, att=False):
+        self.main = torch.cuda.current_stream(dev)
+        self.two = bool(enable and TRL_STREAMS)
+        self.att = None
+        self.held = []          # tensors an attention stream reads: kept alive until the join
+        if self.two:
+            key = (dev.index if dev.index is not None else torch.cuda.current_device())
+            if key not in _side_streams:
+                _side_streams[key] = torch.cuda.Stream(dev)
+            self.side = _side_streams[key]
+            if att and TRL_ATT_STREAMS:
+                if key not in _att_streams:
+                    _att_streams[key] = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
+                self.att = _att_streams[key]
+        else:
+            self.side = self.main
+
+    def att_on(self, di, *reads):
+        """``reads``: tensors of the direction's stream the branch reads (held until the join)."""
+        if self.att is None:
+            return self.on(di)
+        ev = torch.cuda.Event()
+        ev.record(self.side if di == 1 else self.main)
+        self.att[di].wait_event(ev)
+        self.held.extend(r for r in reads if r is not None)
+        return torch.cuda.stream(self.att[di])
+
+    def fork(self):
+        if self.two:
+            ev = torch.cuda.Event()
+            ev.record(self.main)
+            self.side.wait_event(ev)
+
+    def on(self, di):
+        return torch.cuda.stream(self.side if di == 1 else self.main)
+
+    def join(self, *side_tensors):
+        if self.two:
+            for st in (self.side,) + (tuple(self.att) if self.att is not None else ()):
+                ev = torch.cuda.Event()
+                ev.record(st)
+                self.main.wait_event(ev)
+                if st is not self.side:
+                    # blocks the attention streams read / write were allocated on the DIRECTION streams: once `held`
+                    # is dropped the allocator may hand a side-stream block to the side stream's next launch, so the
+                    # side stream is ordered behind the attention streams as well (main already is)
+                    self.side.wait_event(ev)
+            for x in side_tensors:
+                x.record_stream(self.main)
+            self.held = []
+
+
+def trl_eval(plan, xu, xc, b, t, dp, taps=None):
+    """xu, xc [b][t][128][2048] (flat, fp32 or bf16 storage) -> f_uncorr [b][2048], f_corr [b][t][2048] (fp32)."""
+    Cc = 2048
+    frame = PIX * Cc
+    Mb = b * PIX
+    b16 = xu.dtype == torch.bfloat16
+    _stage('trl')
+    memo0 = _newl((Mb, Cc), xu)
+    _call(_k('grl_temporal_mean', xu), ptr(xu), ptr(memo0), b, t, frame)
+    gapc = _new((b * t, Cc), xu)
+    _call(_k('grl_group_mean', xc), ptr(xc), ptr(gapc), b * t, PIX, Cc, Cc, C.c_float(1.0), 0)
+    # (attention streams on bf16 storage only: the exact-fp32 step loses 1 % to them, see TRL_ATT_STREAMS)
+    fk = _TrlFork(xu.device, taps is None and len(plan.dirs) == 2, att=b16)
+    fk.fork()
+    # conv_f2(x_corr_i) does not depend on the recurrence: one GEMM over all T per direction
+    f2, fc, scr = [], [], []
+    for di, d in enumerate(plan.dirs):
+        with fk.on(di):
+            y = _newl((b * t * PIX, Cc), xu)
+            wf2, mf2 = _gw(d['f2'], xu, dp)
+            gemm(xc, wf2, y, b * t * PIX, Cc, Cc, shift=d['f2'].shift, relu=True, math=mf2)
+            f2.append(y)
+            # per-direction accumulators / scratch (a + b == b + a: summing the two directions' f_corr
+            # contributions at the join gives the bits the shared accumulator got in either arrival order)
+            # (two streams: each direction has its own accumulator and writes every (clip, frame) row exactly once -- no
+            #  zero fill, the attention kernel stores instead of accumulating)
+            fc.append(_new((b, t, Cc), xu) if fk.two else (torch.zeros((b, t, Cc), dtype=torch.float32, device=xu.device) if di == 0 else fc[0]))
+            scr.append((_new((b, Cc), xu), _new((b, 128), xu)))
+    memo = [memo0, memo0]
+    catte = _new((b, Cc), xu) if taps is not None else None
+    # d = GAP((ReLU(conv_f1(memo)) - f2_t)^2): the squared difference is reduced in the f1 GEMM's epilogue (32-row
+    # partial sums), conv_f1's output never reaches HBM (grl_model.py:146-149).  On bf16 storage the 256 x 256 kernel
+    # has that epilogue (round 3): it takes the step when Mb is a multiple of 256 on MATH_BF16S; MX-FP8 has none.
+    sqdiff = FUSE_TRL_SQDIFF and (not b16 or (Mb % 256 == 0 and dp == MATH_BF16S))
+    for i in range(t):
+        for di, d in enumerate(plan.dirs):
+            ti = i if di == 0 else t - 1 - i
+            with fk.att_on(di, memo[di]):                       # the attention branch (its own stream where the fork has one)
+                dvec, hid = scr[di]
+                wf1, mf1 = _gw(d['f1'], xu, dp)
+                if sqdiff:
+                    dpart = _new((Mb // 32, Cc), xu)
+                    gemm(memo[di], wf1, dpart, Mb, Cc, Cc, shift=d['f1'].shift, epilogue=EPI_SQDIFF,
+                         res=f2[di][ti * PIX:], res_rows=PIX, res_gstride=t * PIX, math=mf1)
+                    _call('grl_group_mean', ptr(dpart), ptr(dvec), b, PIX // 32, Cc, Cc, C.c_float(1.0 / 32.0), 0)      # (fp32 partial sums on either storage)
+                else:
+                    f1 = _newl((Mb, Cc), xu)
+                    gemm(memo[di], wf1, f1, Mb, Cc, Cc, shift=d['f1'].shift, relu=True, math=mf1)
+                    _call(_k('grl_sqdiff_mean', f1), ptr(f1), ptr(f2[di][ti * PIX:]), ptr(dvec), b, PIX, Cc, t * frame)
+                _call('grl_channel_atte', ptr(dvec), ptr(d['w1']), ptr(d['w2t']), ptr(gapc[ti:]), t * Cc,
+                      ptr(catte), ptr(fc[di].view(b * t, Cc)[ti:]), t * Cc, 0 if fk.two else 1, b, Cc, d['w1'].shape[0], ptr(hid))
+                if taps is not None:
+                    taps.setdefault(('fwd', 'bwd')[di] + '_catte', []).append(catte.clone())
+            with fk.on(di):                                     # the recurrence
+                s = _newl((Mb, Cc), xu)
+                _call(_k('grl_add_strided', xu), ptr(memo[di]), ptr(xu.view(-1)[ti * frame:]), ptr(s), b, frame, t * frame)
+                c1, c2, c3 = d['c1'], d['c2'], d['c3']
+                (w1, m1), (w2, m2), (w3, m3) = _gw(c1, xu, dp), _gw(c2, xu, dp), _gw(c3, xu, dp)
+                o = _newl((Mb, 512), xu)
+                gemm(s, w1, o, Mb, 512, Cc, scale=c1.scale, shift=c1.shift, relu=True, math=m1)
+                o2 = _newl((Mb, 512), xu)
+                gemm(o, w2, o2, Mb, 512, 512, scale=c2.scale, shift=c2.shift, relu=True, math=m2)
+                nm = _newl((Mb, Cc), xu)
+                gemm(o2, w3, nm, Mb, Cc, 512, scale=c3.scale, shift=c3.shift, res=s, relu=True, math=m3)
+                memo[di] = nm
+    fk.join(memo[1], fc[1])
+    fcorr = fc[0]
+    if fk.two:
+        fcorr = _new((b, t, Cc), xu)
+        _call('grl_add_strided', ptr(fc[0]), ptr(fc[1]), ptr(fcorr), 1, b * t * Cc, 0)
+    f_uncorr = _new((b, Cc), xu)
+    _call(_k('grl_group_mean', memo[0]), ptr(memo[0]), ptr(f_uncorr), b, PIX, Cc, Cc, C.c_float(1.0), 0)
+    _call(_k('grl_group_mean', memo[1]), ptr(memo[1]), ptr(f_uncorr), b, PIX, Cc, Cc, C.c_float(1.0), 1)
+    if taps is not None:
+        taps['f_uncorr'], taps['f_corr'] = f_uncorr, fcorr
+    return f_uncorr, fcorr
+
+
+def _grl_eval(model, inputs, taps=None, out_uncorr=None, ld_uncorr=2048):
+    """The eval forward on the current datapath: MATH_BF16S / MATH_MXFP8 keep the activations bf16 in HBM from the stem
+    to the TRL memo (and, MX-FP8, run the generic conv / linear GEMMs on MX operands: _gw); per-clip vectors and the
+    BN1d + L2 tail are fp32 on every datapath."""
+    dp = _math[0]
     plan = _plan(model, GrlEvalPlan)
     b, t, c, h, w = inputs.shape
     if (c, h, w) != (3, 256, 128):
         raise ValueError('GRL expects clips of [B,T,3,256,128] (got %s)' % (tuple(inputs.shape),))
     x = inputs.contiguous().view(b * t, c, h, w)
-    n = b * t
-    Hs, Ws = h // 2, w // 2
-    H, W = (Hs + 1) // 2, (Ws + 1) // 2
-    cur = _newb((n * H * W, 64), x)
-    _stage('stem')
-    if FUSE_STEM_POOL and taps is None and w == 128 and h % 4 == 0 and _stem_pool_ok(x, n):
-        # stem + max-pool in one launch: the stem map never reaches HBM (grl_stem_pool_bf16)
-        u8 = x.dtype == torch.uint8
-        _call('grl_stem_pool_bf16', ptr(x), 1 if u8 else 0, ptr(input_mean_std(x.device)) if u8 else None,
-              ptr(plan.stem_scale), ptr(plan.stem_shift), ptr(cur), n, h, w, ptr(plan.stem_wpb))
-    else:
-        stem = _newb((n * Hs * Ws, 64), x)
-        if x.dtype == torch.uint8:
-            _call('grl_stem_conv7x7_u8_bf16', ptr(x), ptr(input_mean_std(x.device)), ptr(plan.stem_w),
-                  ptr(plan.stem_scale), ptr(plan.stem_shift), ptr(stem), n, h, w, 1, ptr(plan.stem_wpb))
-        else:
-            _call('grl_stem_conv7x7_bf16', ptr(x), ptr(plan.stem_w), ptr(plan.stem_scale), ptr(plan.stem_shift),
-                  ptr(stem), n, h, w, 1, ptr(plan.stem_wpb))
-        _call('grl_maxpool3x3s2_bf16', ptr(stem), ptr(cur), n, Hs, Ws, 64)
-        del stem
-    o1 = None
-    for bi, e in enumerate(plan.blocks):
-        if bi in (0, 3, 7, 13):
-            _stage('layer%d' % ((0, 3, 7, 13).index(bi) + 1))
-        s = e['stride']
-        if o1 is None:
-            o1, _, _ = _conv_b16(cur, e['c1'], n, H, W, dp=dp)
-        o2, Ho, Wo = _conv_b16(o1, e['c2'], n, H, W, stride=s, dp=dp)
-        nxt = plan.blocks[bi + 1]['c1'] if bi + 1 < len(plan.blocks) else None
-        fuse = FUSE_BNECK and nxt is not None and _bneck_tail_ok(e['c3'], nxt, n * Ho * Wo)
-        o1 = None
-        if fuse and FUSE_DOWN and _bneck_down_ok(e['c3'], nxt, e['down'], s):
-            # layer 1's first block: the downsample branch too -- its 4P-wide output is neither written nor re-read
-            cur, o1 = bneck_tail_bf16(o2, e['c3'], None, nxt, n * Ho * Wo, down=e['down'], x0=cur)
-        else:
-            res = _conv_b16(cur, e['down'], n, H, W, stride=s, relu=False, dp=dp)[0] if e['down'] is not None else cur
-            if fuse:
-                # layers 1-2: conv3 + residual + ReLU AND the next block's conv1 in one launch -- the 4P-wide output is
-                # written once (the next block's residual) and never re-read (fuse_bf16.hip)
-                cur, o1 = bneck_tail_bf16(o2, e['c3'], res, nxt, n * Ho * Wo)
-            else:
-                cur, _, _ = _conv_b16(o2, e['c3'], n, Ho, Wo, res=res, dp=dp)
-        H, W = Ho, Wo
-    x4 = cur
-    M = x4.shape[0]
-    # GCE
-    _stage('gce')
-    x_glo = _new((b, 2048), x)
-    _call('grl_group_mean_bf16', ptr(x4), ptr(x_glo), b, t * PIX, 2048, 2048, C.c_float(1.0), 0)
-    g = plan.glo_fc
-    glo = _new((b, 1024), x)
-    gemm(x_glo, g.w, glo, b, 1024, 2048, scale=g.scale, shift=g.shift, relu=True, math=MATH_F32, kblock=True)
-    c0 = plan.corr0
-    gb = _new((b, 1024), x)
-    gemm(glo, c0.w[:, 2048:], gb, b, 1024, 1024, ldw=3072, math=MATH_F32, kblock=True)
-    h1 = _newb((M, 1024), x)
-    w0, m0 = _gw(c0, dp, 2048)                  # (the x4 half of corr0's [1024][3072] weight)
-    gemm(x4, w0, h1, M, 1024, 2048, ldw=3072, gbias=gb, rows_per_group=t * PIX,
-         scale=c0.scale, shift=c0.shift, relu=False, math=m0)
-    c2 = plan.corr2
-    h2 = _newb((M, 256), x)
-    w2, m2 = _gw(c2, dp)
-    gemm(h1, w2, h2, M, 256, 1024, scale=c2.scale, shift=c2.shift, relu=True, math=m2)
-    cmap = _new((M,), x)
-    xc, xu = _newb((M, 2048), x), _newb((M, 2048), x)
-    _call('grl_gce_gate_bf16', ptr(h2), ptr(plan.corr5_w), ptr(plan.corr6_scale), ptr(plan.corr6_shift),
-          ptr(x4), ptr(cmap), ptr(xc), ptr(xu), M, 256, 2048)
-    del x4, h1, h2
-    if taps is not None:
-        taps['corr_map'] = cmap.view(b * t, 1, 16, 8)
-    # TRL
-    _stage('trl')
-    Cc, frame, Mb = 2048, PIX * 2048, b * PIX
-    memo0 = _newb((Mb, Cc), x)
-    _call('grl_temporal_mean_bf16', ptr(xu), ptr(memo0), b, t, frame)
-    gapc = _new((b * t, Cc), x)
-    _call('grl_group_mean_bf16', ptr(xc), ptr(gapc), b * t, PIX, Cc, Cc, C.c_float(1.0), 0)
-    # bf16 storage: the large bf16 tiles own a CU's LDS, so the two directions' M = b * 128 GEMMs cannot share a CU and
-    # each leaves half the chip idle.  Round 5: the two directions' conv1 / conv2 of a step (same shape, different
-    # operands) go out as ONE grouped launch (grl_conv_gemm_f32_group: 256 x 128 tiles over both problems, bit-identical
-    # to the separate launches) on the main stream, between two event hand-offs; everything else of a direction stays on
-    # its own stream.  Every buffer that crosses streams is allocated on the main stream before the fork and lives until
-    # the join.  MEASURED SLOWER in the pipeline (configs[2] same box 10.48 -> 10.68 ms; on ONE stream 10.78): alone the
-    # grouped launch beats two launches (44 vs 2 x 35 us), but the 128 x 64 ring kernel the separate launches run on keeps
-    # two workgroups per CU, so the two streams' launches already share every CU -- and the hand-offs cost their bubbles.
-    # Off by default (GRL_TRL_GROUP=1 switches it on; kept tested: test_trl_grouped_launches_equal_two_stream_form).
-    grouped = TRL_GROUP and len(plan.dirs) == 2 and dp == MATH_BF16S
-    fk = _TrlFork(x.device, taps is None and len(plan.dirs) == 2, att=not grouped)
-    bufs = None
-    if grouped:
-        bufs = [dict(s=_newb((Mb, Cc), x), o=_newb((Mb, 512), x), o2=_newb((Mb, 512), x),
-                     m=(_newb((Mb, Cc), x), _newb((Mb, Cc), x))) for _ in plan.dirs]
-    fk.fork()
-    f2, fc, scr = [], [], []
-    for di, d in enumerate(plan.dirs):
-        with fk.on(di):
-            y = _newb((b * t * PIX, Cc), x)
-            wf2, mf2 = _gw(d['f2'], dp)
-            gemm(xc, wf2, y, b * t * PIX, Cc, Cc, shift=d['f2'].shift, relu=True, math=mf2)
-            f2.append(y)
-            fc.append(_new((b, t, Cc), x) if fk.two else (torch.zeros((b, t, Cc), dtype=torch.float32, device=x.device) if di == 0 else fc[0]))
-            scr.append((_new((b, Cc), x), _new((b, 128), x)))
-    memo = [memo0, memo0]
-
-    def f1_gemm(di, d, ti):
-        if FUSE_TRL_SQDIFF and Mb % 256 == 0 and dp == MATH_BF16S:
-            # the squared difference reduced in the f1 GEMM's epilogue (32-row partial sums): conv_f1's output
-            # never reaches HBM -- round 3: the bf16 256 x 256 kernel has the epilogue too
-            dpart = _new((Mb // 32, Cc), x)
-            gemm(memo[di], d['f1'].wb(), dpart, Mb, Cc, Cc, shift=d['f1'].shift, epilogue=EPI_SQDIFF,
-                 res=f2[di][ti * PIX:], res_rows=PIX, res_gstride=t * PIX, math=MATH_BF16S)
-            return dpart, None
-        f1 = _newb((Mb, Cc), x)
-        wf1, mf1 = _gw(d['f1'], dp)
-        gemm(memo[di], wf1, f1, Mb, Cc, Cc, shift=d['f1'].shift, relu=True, math=mf1)
-        return None, f1
-
-    def f1_tail(di, d, ti, dpart, f1):
-        dvec, hid = scr[di]
-        if dpart is not None:
-            _call('grl_group_mean', ptr(dpart), ptr(dvec), b, PIX // 32, Cc, Cc, C.c_float(1.0 / 32.0), 0)
-        else:
-            _call('grl_sqdiff_mean_bf16', ptr(f1), ptr(f2[di][ti * PIX:]), ptr(dvec), b, PIX, Cc, t * frame)
-        _call('grl_channel_atte', ptr(dvec), ptr(d['w1']), ptr(d['w2t']), ptr(gapc[ti:]), t * Cc,
-              None, ptr(fc[di].view(b * t, Cc)[ti:]), t * Cc, 0 if fk.two else 1, b, Cc, d['w1'].shape[0], ptr(hid))
-
-    def f1_branch(di, d, ti):
-        f1_tail(di, d, ti, *f1_gemm(di, d, ti))
-
-    for i in range(t):
-        tis = [i, t - 1 - i]
-        if grouped:
-            for di, d in enumerate(plan.dirs):
-                with fk.on(di):
-                    f1_branch(di, d, tis[di])
-                    _call('grl_add_strided_bf16', ptr(memo[di]), ptr(xu.view(-1)[tis[di] * frame:]), ptr(bufs[di]['s']),
-                          b, frame, t * frame)
-            fk.side_to_main()
-            gemm_group([dict(a=bufs[di]['s'], w=d['c1'].wb(), y=bufs[di]['o'], M=Mb, N=512, K=Cc, scale=d['c1'].scale,
-                             shift=d['c1'].shift, relu=True, math=MATH_BF16S) for di, d in enumerate(plan.dirs)])
-            gemm_group([dict(a=bufs[di]['o'], w=d['c2'].wb(), y=bufs[di]['o2'], M=Mb, N=512, K=512, scale=d['c2'].scale,
-                             shift=d['c2'].shift, relu=True, math=MATH_BF16S) for di, d in enumerate(plan.dirs)])
-            fk.main_to_side()
-            for di, d in enumerate(plan.dirs):
-                with fk.on(di):
-                    c3 = d['c3']
-                    nm = bufs[di]['m'][i & 1]
-                    gemm(bufs[di]['o2'], c3.wb(), nm, Mb, Cc, 512, scale=c3.scale, shift=c3.shift, res=bufs[di]['s'], relu=True,
-                         math=MATH_BF16S)
-                    memo[di] = nm
-            continue
-        for di, d in enumerate(plan.dirs):
-            ti = tis[di]
-            with fk.att_on(di, memo[di]):                       # the attention branch (its own stream: see _TrlFork)
-                f1_branch(di, d, ti)
-            with fk.on(di):
-                s_ = _newb((Mb, Cc), x)
-                _call('grl_add_strided_bf16', ptr(memo[di]), ptr(xu.view(-1)[ti * frame:]), ptr(s_), b, frame, t * frame)
-                c1, c2_, c3 = d['c1'], d['c2'], d['c3']
-                o = _newb((Mb, 512), x)
-                (w1, mm1), (w2_, mm2), (w3, mm3) = _gw(c1, dp), _gw(c2_, dp), _gw(c3, dp)
-                gemm(s_, w1, o, Mb, 512, Cc, scale=c1.scale, shift=c1.shift, relu=True, math=mm1)
-                o2 = _newb((Mb, 512), x)
-                gemm(o, w2_, o2, Mb, 512, 512, scale=c2_.scale, shift=c2_.shift, relu=True, math=mm2)
-                nm = _newb((Mb, Cc), x)
-                gemm(o2, w3, nm, Mb, Cc, 512, scale=c3.scale, shift=c3.shift, res=s_, relu=True, math=mm3)
-                memo[di] = nm
-    fk.join(memo[1], fc[1])
-    fcorr = fc[0]
-    if fk.two:
-        fcorr = _new((b, t, Cc), x)
-        _call('grl_add_strided', ptr(fc[0]), ptr(fc[1]), ptr(fcorr), 1, b * t * Cc, 0)
-    f_uncorr = _new((b, Cc), x)
-    _call('grl_group_mean_bf16', ptr(memo[0]), ptr(f_uncorr), b, PIX, Cc, Cc, C.c_float(1.0), 0)
-    _call('grl_group_mean_bf16', ptr(memo[1]), ptr(f_uncorr), b, PIX, Cc, Cc, C.c_float(1.0), 1)
-    if taps is not None:
-        taps['f_uncorr'], taps['f_corr'] = f_uncorr, fcorr
+    x4, _, _ = trunk_eval(plan, x, dp, taps)
+    xu, xc, _ = gce_eval(plan, x4, b, t, dp, taps)
+    del x4
+    f_uncorr, f_corr = trl_eval(plan, xu, xc, b, t, dp, taps)
     _stage('tail')
     x_corr = _new((b, t, 2048), inputs)
-    _call('grl_affine_l2norm', ptr(fcorr), ptr(plan.corr_bn[0]), ptr(plan.corr_bn[1]), ptr(x_corr),
+    _call('grl_affine_l2norm', ptr(f_corr), ptr(plan.corr_bn[0]), ptr(plan.corr_bn[1]), ptr(x_corr),
           b * t, 2048, 2048)
     x_uncorr = out_uncorr if out_uncorr is not None else _new((b, 2048), inputs)
     _call('grl_affine_l2norm', ptr(f_uncorr), ptr(plan.uncorr_bn[0]), ptr(plan.uncorr_bn[1]),

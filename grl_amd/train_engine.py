@@ -20,7 +20,7 @@ import torch
 from . import _lib, engine
 from ._lib import GrlWgrad, check, ptr
 from ._lib import MATH_F32
-from .engine import _call, _new, EvalPlan, PIX
+from .engine import _call, _k, _new, _newl, EvalPlan, PIX
 
 
 # Multiplier datapath of the TRAINING forward and data-gradient GEMMs (operands stay fp32 in HBM,
@@ -83,15 +83,6 @@ def gemm(a, w, *args, **kw):
 
 def _b16(t):
     return t is not None and t.dtype == BF16
-
-
-def _k(name, t):
-    """Entry point for tensor ``t``'s storage type: the bf16 twin (train_bf16.hip / pointwise_bf16.hip) or the fp32 one."""
-    return name + '_bf16' if t.dtype == BF16 else name
-
-
-def _newl(shape, like):
-    return torch.empty(shape, dtype=like.dtype, device=like.device)
 
 
 def cast16(t):

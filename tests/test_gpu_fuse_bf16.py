@@ -189,9 +189,9 @@ def test_conv3x3_c64_matches_the_generic_kernel_and_torch(dev, n, H):
     x = torch.randn(n * H * W, 64, generator=g).to(dev).to(BF)
     old, engine.FUSE_C64 = engine.FUSE_C64, True
     try:
-        y, _, _ = engine._conv_b16(x, c, n, H, W)
+        y, _, _ = engine._conv_layer(x, c, n, H, W)
         engine.FUSE_C64 = False
-        y0, _, _ = engine._conv_b16(x, c, n, H, W)
+        y0, _, _ = engine._conv_layer(x, c, n, H, W)
     finally:
         engine.FUSE_C64 = old
     xr = x.float().view(n, H, W, 64).permute(0, 3, 1, 2)
