@@ -159,6 +159,8 @@ _SIGNATURES = {
     'grl_scale_dev': ([_fp, _fp, C.c_float, _fp, _i64, _fp], C.c_int),
     'grl_rank_metrics': ([_fp, _i64, _fp, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
     'grl_topk_block': ([_fp, _i64, _fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp], C.c_int),
+    'grl_topk_block_filtered': ([_fp, _i64, _fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp,
+                                 _fp], C.c_int),
     'grl_match_gather': ([_fp, _i64, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp], C.c_int),
     'grl_match_sort': ([C.c_int] + [_fp] * 7 + [C.c_int, _fp, _fp, _fp], C.c_int),
     'grl_rank_count_block': ([_fp, _i64, C.c_int, C.c_int, C.c_int] + [_fp] * 5 + [C.c_int, _fp, _fp], C.c_int),

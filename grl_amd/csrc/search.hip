@@ -63,11 +63,23 @@ __device__ __forceinline__ int lower_bound_i32(const int32_t* a, int lo, int hi,
 // before the current k-th entry; when the buffer cannot take another 256-column chunk, the 2P entries are
 // sorted and the best P stay in front.  The result is the first k entries of the union under the total
 // order, whatever order the buffer was filled in.
+//
+// FILTER (grl_topk_block_filtered): a column whose gallery entry shares pid AND camera with the query is junk
+// (eva_functions.py:151-155) and never enters the buffer.  The predicate sits behind the threshold test, so only
+// the columns that would have been admitted read g_pids / g_cams: every column while the list is still filling
+// (thr is padding, junk must not take a slot and set the threshold), a few per chunk afterwards.  The query's
+// own pid and camera are wave-uniform: one load before the loop, held in scalar registers for the whole row.
+// Without FILTER the branch does not exist and the four pointers are never read.
+template <bool FILTER>
 __global__ __launch_bounds__(SEARCH_THREADS) void topk_block_kernel(const float* __restrict__ d, int64_t ld,
                                                                     const int32_t* __restrict__ cidx, int64_t ldc,
                                                                     int ncols, int col0, int k, int P,
                                                                     uint64_t* __restrict__ run_key,
-                                                                    float* __restrict__ run_val) {
+                                                                    float* __restrict__ run_val,
+                                                                    const int32_t* __restrict__ q_pids,
+                                                                    const int32_t* __restrict__ q_cams,
+                                                                    const int32_t* __restrict__ g_pids,
+                                                                    const int32_t* __restrict__ g_cams) {
     extern __shared__ __attribute__((aligned(16))) uint64_t sm_topk[];
     uint64_t* c = sm_topk;                                  // [2P]
     float* v = reinterpret_cast<float*>(sm_topk + 2 * P);   // [2P]
@@ -81,6 +93,8 @@ __global__ __launch_bounds__(SEARCH_THREADS) void topk_block_kernel(const float*
         v[i] = i < k ? rv[i] : __int_as_float(0x7f800000);
     }
     if (tid == 0) cnt = 0;
+    int qp = 0, qc = 0;
+    if constexpr (FILTER) { qp = q_pids[q]; qc = q_cams[q]; }
     __syncthreads();
     for (int base = 0; base < ncols; base += SEARCH_THREADS) {
         const uint64_t thr = c[k - 1];
@@ -90,7 +104,9 @@ __global__ __launch_bounds__(SEARCH_THREADS) void topk_block_kernel(const float*
             if (g >= 0) {
                 const float x = dr[j];
                 const uint64_t cc = composite(search_key(x), g);
-                if (cc < thr) {
+                bool take = cc < thr;
+                if constexpr (FILTER) take = take && !(g_pids[g] == qp && g_cams[g] == qc);
+                if (take) {
                     const int pos = atomicAdd(&cnt, 1);         // < P: the buffer had room for a whole chunk
                     c[P + pos] = cc;
                     v[P + pos] = x;
@@ -258,9 +274,25 @@ extern "C" int grl_topk_block(const float* d, int64_t ld, const int32_t* cidx, i
     if (k < 1 || k > TOPK_MAX) return grl_fail(GRL_EUNSUPPORTED, "topk_block: k = %d (1..%d)", k, TOPK_MAX);
     const int P = max(SEARCH_THREADS, pow2_at_least(k));
     const size_t lds = (size_t)2 * P * (sizeof(uint64_t) + sizeof(float));
-    hipLaunchKernelGGL(topk_block_kernel, dim3(nq), dim3(SEARCH_THREADS), lds, (hipStream_t)stream, d, ld, cidx, ldc,
-                       ncols, col0, k, P, run_key, run_val);
+    hipLaunchKernelGGL(topk_block_kernel<false>, dim3(nq), dim3(SEARCH_THREADS), lds, (hipStream_t)stream, d, ld, cidx,
+                       ldc, ncols, col0, k, P, run_key, run_val, (const int32_t*)nullptr, (const int32_t*)nullptr,
+                       (const int32_t*)nullptr, (const int32_t*)nullptr);
     return grl_check_launch("grl_topk_block");
+}
+
+extern "C" int grl_topk_block_filtered(const float* d, int64_t ld, const int32_t* cidx, int64_t ldc, int nq, int ncols,
+                                       int col0, int k, uint64_t* run_key, float* run_val, const int32_t* q_pids,
+                                       const int32_t* q_cams, const int32_t* g_pids, const int32_t* g_cams,
+                                       void* stream) {
+    GRL_REQUIRE(d && run_key && run_val && q_pids && q_cams && g_pids && g_cams, "topk_block_filtered: null");
+    GRL_REQUIRE(nq > 0 && ncols > 0 && ld >= ncols && col0 >= 0 && (!cidx || ldc >= ncols),
+                "topk_block_filtered: bad shape");
+    if (k < 1 || k > TOPK_MAX) return grl_fail(GRL_EUNSUPPORTED, "topk_block_filtered: k = %d (1..%d)", k, TOPK_MAX);
+    const int P = max(SEARCH_THREADS, pow2_at_least(k));
+    const size_t lds = (size_t)2 * P * (sizeof(uint64_t) + sizeof(float));
+    hipLaunchKernelGGL(topk_block_kernel<true>, dim3(nq), dim3(SEARCH_THREADS), lds, (hipStream_t)stream, d, ld, cidx,
+                       ldc, ncols, col0, k, P, run_key, run_val, q_pids, q_cams, g_pids, g_cams);
+    return grl_check_launch("grl_topk_block_filtered");
 }
 
 extern "C" int grl_match_gather(const float* d, int64_t ld, int nq, int col0, int ncols, const int32_t* q_slot,

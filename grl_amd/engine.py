@@ -1159,19 +1159,27 @@ def rank_metrics(indices, q_pids, g_pids, q_camids, g_camids, max_rank=100):
     nq, ng = indices.shape
     dev = indices.device
 
-    def ids(a, n, what):
-        a = np.asarray(a).reshape(-1)
-        if a.size != n:
-            raise ValueError('%s: expected %d entries, got %d' % (what, n, a.size))
-        return torch.from_numpy(a.astype(np.int32)).to(dev)
-    qp, qc = ids(q_pids, nq, 'q_pids'), ids(q_camids, nq, 'q_camids')
-    gp, gc = ids(g_pids, ng, 'g_pids'), ids(g_camids, ng, 'g_camids')
+    qp, qc = _ids(q_pids, nq, 'q_pids', dev), _ids(q_camids, nq, 'q_camids', dev)
+    gp, gc = _ids(g_pids, ng, 'g_pids', dev), _ids(g_camids, ng, 'g_camids', dev)
     first = torch.empty(nq, dtype=torch.int32, device=dev)
     nhit = torch.empty(nq, dtype=torch.int32, device=dev)
     ap = torch.empty(nq, dtype=torch.float64, device=dev)
     _call('grl_rank_metrics', ptr(indices), ng, ptr(qp), ptr(qc), ptr(gp), ptr(gc), nq, ng, ptr(first), ptr(nhit),
           ptr(ap))
     return _cmc_map(first, nhit, ap, ng, max_rank)
+
+
+def _ids(a, n, what, dev=None):
+    """A pid / camera id list as int32 [n]: a numpy array, or a tensor on ``dev``.  The kernels compare ids as
+    int32, so a value outside that range is refused rather than wrapped."""
+    import numpy as np
+    a = np.asarray(a).reshape(-1)
+    if a.size != n:
+        raise ValueError('%s: expected %d entries, got %d' % (what, n, a.size))
+    if a.size and (a.min() < -2 ** 31 or a.max() > 2 ** 31 - 1):
+        raise ValueError('%s: ids must fit int32' % what)
+    a = a.astype(np.int32)
+    return a if dev is None else torch.from_numpy(a).to(dev)
 
 
 def _cmc_map(first, nhit, ap, ng, max_rank):
@@ -1246,7 +1254,19 @@ def _shard(ng):
     return lo, hi, True
 
 
-def search(qf, gf, k, metric='cosine', block_cols=None, block_bytes=None):
+def _junk_ids(exclude, nq, ng, dev):
+    """``exclude = (q_pids, g_pids, q_camids, g_camids)`` (rank_metrics' order) as the int32 device arrays
+    (q_pids, q_cams, g_pids, g_cams) of grl_topk_block_filtered; None stays None."""
+    if exclude is None:
+        return None
+    if len(exclude) != 4:
+        raise ValueError('exclude must be (q_pids, g_pids, q_camids, g_camids)')
+    q_pids, g_pids, q_camids, g_camids = exclude
+    return (_ids(q_pids, nq, 'q_pids', dev), _ids(q_camids, nq, 'q_camids', dev), _ids(g_pids, ng, 'g_pids', dev),
+            _ids(g_camids, ng, 'g_camids', dev))
+
+
+def search(qf, gf, k, metric='cosine', exclude=None, block_cols=None, block_bytes=None):
     """Each query's ``k`` nearest gallery entries: ``(dist [nq, k] float32, idx [nq, k] int64)`` on the device,
     without the query x gallery matrix.  Exactly ``rank_rows(D)[:, :k]`` and ``D`` at those indices, bit for
     bit, for D = cosin_dist(qf, gf) ('cosine') or pairwise_distance_tensor(qf, gf) ('euclidean'): canonical
@@ -1254,18 +1274,28 @@ def search(qf, gf, k, metric='cosine', block_cols=None, block_bytes=None):
     row is padding: index -1, distance +inf.  k <= 1024.  The distances are computed in column blocks of
     ``block_cols`` (default: as many as fit ``block_bytes``, GRL_SEARCH_BLOCK_BYTES, 256 MiB).  Under
     torch.distributed the gallery rows are sharded over the ranks and only the per-rank top-k lists are
-    exchanged."""
+    exchanged.
+
+    ``exclude = (q_pids, g_pids, q_camids, g_camids)`` (the order of ``rank_metrics``) drops, for every query, the
+    gallery entries that share its pid AND its camera: the junk rule of eva_functions.evaluate, which CMC / mAP and
+    visualize_ranked_results apply.  Row q is then ``rank_rows(D)[q]`` with the junk entries of query q deleted,
+    truncated to ``k`` (padded as above when fewer are left), and ``D`` at those indices, bit for bit.  The rule is
+    applied on the device while the blocks are ranked (grl_topk_block_filtered); no nq x ng mask is built.
+    ``exclude=None`` makes the calls it made before the argument existed."""
     if not 1 <= int(k) <= SEARCH_K_MAX:
         raise ValueError('search: k must be in 1..%d (got %r)' % (SEARCH_K_MAX, k))
     k = int(k)
     nq, ng = qf.shape[0], gf.shape[0]
+    junk = _junk_ids(exclude, nq, ng, qf.device)
     lo, hi, sharded = _shard(ng)
     blocks = _ColumnBlocks(qf, gf, metric, block_cols, block_bytes, lo, hi)
-    return _search_blocks(blocks, nq, k, sharded)
+    return _search_blocks(blocks, nq, k, sharded, junk)
 
 
-def _search_blocks(blocks, nq, k, sharded):
-    """The running top-k of search over a block source (``spans``, ``block(c0, c1)``, ``qf``)."""
+def _search_blocks(blocks, nq, k, sharded, junk=None):
+    """The running top-k of search over a block source (``spans``, ``block(c0, c1)``, ``qf``).  ``junk``: the
+    device arrays of _junk_ids; every distance block then goes through grl_topk_block_filtered.  The merge of the
+    ranks' lists stays unfiltered: its inputs are clean already."""
     dev = blocks.qf.device
     run_key = torch.full((nq, k), -1, dtype=torch.int64, device=dev)          # all-ones composite = empty slot
     run_val = torch.full((nq, k), float('inf'), dtype=torch.float32, device=dev)
@@ -1273,7 +1303,11 @@ def _search_blocks(blocks, nq, k, sharded):
         return run_val, run_key
     for c0, c1 in blocks.spans:
         d = blocks.block(c0, c1)
-        _call('grl_topk_block', ptr(d), c1 - c0, None, 0, nq, c1 - c0, c0, k, ptr(run_key), ptr(run_val))
+        if junk is None:
+            _call('grl_topk_block', ptr(d), c1 - c0, None, 0, nq, c1 - c0, c0, k, ptr(run_key), ptr(run_val))
+        else:
+            _call('grl_topk_block_filtered', ptr(d), c1 - c0, None, 0, nq, c1 - c0, c0, k, ptr(run_key), ptr(run_val),
+                  ptr(junk[0]), ptr(junk[1]), ptr(junk[2]), ptr(junk[3]))
     if sharded:
         import torch.distributed as tdist
         from . import dist as grl_dist
@@ -1323,13 +1357,8 @@ def _rank_blocks(blocks, nq, ng, q_pids, g_pids, q_camids, g_camids, sharded):
     from . import dist as grl_dist
     dev = blocks.qf.device
 
-    def ids(a, n, what):
-        a = np.asarray(a).reshape(-1)
-        if a.size != n:
-            raise ValueError('%s: expected %d entries, got %d' % (what, n, a.size))
-        return a.astype(np.int32)
-    qp, qc = ids(q_pids, nq, 'q_pids'), ids(q_camids, nq, 'q_camids')
-    gp, gc = ids(g_pids, ng, 'g_pids'), ids(g_camids, ng, 'g_camids')
+    qp, qc = _ids(q_pids, nq, 'q_pids'), _ids(q_camids, nq, 'q_camids')
+    gp, gc = _ids(g_pids, ng, 'g_pids'), _ids(g_camids, ng, 'g_camids')
     # pid -> ascending gallery indices (CSR); a query's candidates are its pid's list
     order = np.argsort(gp, kind='stable').astype(np.int32)
     uniq, starts = np.unique(gp[order], return_index=True)
@@ -1558,7 +1587,7 @@ class _RerankBlocks(object):
         return self.rr.finish(self.cos.block(c0, c1), c0, c1 - c0)
 
 
-def rerank_search(qf, gf, k, k1=20, k2=6, lambda_value=0.3, block_cols=None, block_bytes=None):
+def rerank_search(qf, gf, k, k1=20, k2=6, lambda_value=0.3, exclude=None, block_cols=None, block_bytes=None):
     """``search`` on the k-reciprocal re-ranked distances F = re_ranking(cosin_dist(qf, gf), pairwise_distance_tensor(
     qf, qf), pairwise_distance_tensor(gf, gf), k1, k2, lambda_value): ``(dist [nq, k] float32, idx [nq, k] int64)``,
     bit for bit ``rank_rows(F)[:, :k]`` and F at those indices (search's tie, NaN and padding rules), without F, the
@@ -1566,11 +1595,17 @@ def rerank_search(qf, gf, k, k1=20, k2=6, lambda_value=0.3, block_cols=None, blo
     ``block_cols`` / ``block_bytes`` (GRL_SEARCH_BLOCK_BYTES).  Under torch.distributed the work is sharded over the
     ranks: the sample passes by contiguous sample range with all-gathers of colmax, the rank lists,
     the weights and the V2 rows in between, the final pass by gallery column with search's exchange of top-k
-    lists.  Every rank returns the full result, bit for bit the single-process one."""
+    lists.  Every rank returns the full result, bit for bit the single-process one.
+
+    ``exclude = (q_pids, g_pids, q_camids, g_camids)`` is ``search``'s: row q is ``rank_rows(F)[q]`` with the
+    gallery entries of query q's pid AND camera deleted, truncated to ``k``, and F at those indices, bit for bit.
+    Only the ranking of the re-ranked blocks is filtered; the K-nearest lists behind the k-reciprocal sets are
+    not, as the reference's re_ranking knows nothing of junk, so F itself does not depend on ``exclude``."""
     if not 1 <= int(k) <= SEARCH_K_MAX:
         raise ValueError('rerank_search: k must be in 1..%d (got %r)' % (SEARCH_K_MAX, k))
+    junk = _junk_ids(exclude, qf.shape[0], gf.shape[0], qf.device)
     rr = _Rerank(qf, gf, k1, k2, lambda_value, block_cols, block_bytes)
-    return _search_blocks(_RerankBlocks(qf, gf, rr, block_cols, block_bytes), rr.nq, int(k), rr.sharded)
+    return _search_blocks(_RerankBlocks(qf, gf, rr, block_cols, block_bytes), rr.nq, int(k), rr.sharded, junk)
 
 
 def rerank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, k1=20, k2=6, lambda_value=0.3, max_rank=100,

@@ -12,8 +12,9 @@ from grl_amd import engine
 from grl_amd import dist as grl_dist
 from .eva_functions import evaluate
 from .rerank import re_ranking
+from .visualize import visualize_ranked_results
 
-__all__ = ['ATTEvaluator', 'evaluate_seq', 'cosin_dist', 'pairwise_distance_tensor']
+__all__ = ['ATTEvaluator', 'evaluate_seq', 'cosin_dist', 'pairwise_distance_tensor', 'visualize_ranked_results']
 
 
 def evaluate_seq(distmat, query_pids, query_camids, gallery_pids, gallery_camids, path,
@@ -101,9 +102,49 @@ class ATTEvaluator(object):
         feat, pids_all, cams_all = grl_dist.gather_feature_batches(mine, len(data_loader))
         return feat, np.asarray(pids_all), np.asarray(cams_all)
 
+    def _visualize(self, query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, rerank, topk=10):
+        """``visual=1``: the ranked-results folders of visualize_ranked_results in ``path + 'visual'`` for the query
+        positions of GRL_VISUAL_QUERIES (comma list; default 4, the reference's visual_id), and ``ranked.json`` in
+        the same folder: {query position: [[gallery position, pid, camid, distance], ...]} (a non-finite distance is
+        null; a position the query list does not have is skipped with a printed note).  ``gf`` / ``g_pids`` /
+        ``g_camids`` carry the prepended queries, so gallery positions below nq are queries.  The lists are the
+        junk-filtered top-k of engine.search / engine.rerank_search (``exclude=``): no matrix, no argsort.  Those
+        calls are collective under torch.distributed; rank 0 alone writes."""
+        import json
+        if query is None or gallery is None:
+            raise ValueError('visual=1 needs the query and gallery tuple lists (img_path(s), pid, camid)')
+        nq = qf.size(0)
+        if len(query) != nq or len(query) + len(gallery) != gf.size(0):
+            raise ValueError('visual=1: %d query / %d gallery tuples for %d / %d feature rows'
+                             % (len(query), len(gallery), nq, gf.size(0) - nq))
+        spec = os.environ.get('GRL_VISUAL_QUERIES', '4')
+        try:
+            asked = sorted(set(int(v) for v in spec.split(',') if v.strip()))
+        except ValueError:
+            raise ValueError('GRL_VISUAL_QUERIES must be a comma list of query positions (got %r)' % spec)
+        wanted = [q for q in asked if 0 <= q < nq]
+        ids = (q_pids, g_pids, q_camids, g_camids)
+        if rerank:
+            dist, idx = engine.rerank_search(qf, gf, topk, exclude=ids)
+        else:
+            dist, idx = engine.search(qf, gf, topk, exclude=ids)
+        if grl_dist._rank_world(None, None)[0] != 0:
+            return
+        dist, idx = dist.cpu().numpy(), idx.cpu().numpy()
+        if len(wanted) < len(asked):
+            print('GRL_VISUAL_QUERIES: no query at position(s) %s (there are %d queries), skipped'
+                  % (', '.join(str(q) for q in asked if q not in wanted), nq))
+        save_dir = path + 'visual'
+        visualize_ranked_results(None, list(query), list(query) + list(gallery), save_dir, visual_id=wanted,
+                                 topk=topk, indices=idx)
+        ranked = {}
+        for q in wanted:                      # strict JSON: a distance that is not finite (NaN feature) becomes null
+            ranked[str(q)] = [[int(g), int(g_pids[g]), int(g_camids[g]), float(d) if np.isfinite(d) else None]
+                              for g, d in zip(idx[q], dist[q]) if g >= 0]
+        with open(os.path.join(save_dir, 'ranked.json'), 'w') as fh:
+            json.dump(ranked, fh, indent=1, allow_nan=False)
+
     def evaluate(self, query, gallery, query_loader, gallery_loader, path, visual, rerank):
-        if visual:
-            raise NotImplementedError('ranked-result visualisation is outside the GRL hot path')
         stream = os.environ.get('GRL_EVAL_STREAM') == '1'
         rerank_stream = rerank and os.environ.get('GRL_EVAL_RERANK') == 'stream'
         if stream and rerank and not rerank_stream:
@@ -117,6 +158,8 @@ class ATTEvaluator(object):
         g_camids = np.append(q_camids, g_camids)
         print('Done, obtained {}-by-{} matrix'.format(gf.size(0), gf.size(1)))
         print("Computing distance matrix")
+        if visual:
+            self._visualize(query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, rerank)
         if rerank_stream:
             # k-reciprocal re-ranking over column blocks (engine.rerank_metrics_streaming): the values of the device
             # re_ranking below without its (q+g)^2 matrices, for any q + g.  Under torch.distributed the sample passes

@@ -40,7 +40,7 @@ const char* grl_last_error(void);
  * The column-block search / ranking entry points grl_topk_block .. grl_rank_finish were added at 10: they change no
  * struct layout or argument list, and a library without them fails to bind in _lib.load.  So were the streaming
  * re-ranking entry points grl_rrs_*, the CSR / CSC assembly of its sharded form (grl_rrs_expand_rows, grl_rrs_scan,
- * grl_rrs_place, grl_rrs_transpose) among them. */
+ * grl_rrs_place, grl_rrs_transpose) among them, and grl_topk_block_filtered. */
 #define GRL_ABI_VERSION 10
 int grl_abi_version(void);
 /* `waiter` (a hipStream_t) waits for everything enqueued on `signaler` so far: hipEventRecord + hipStreamWaitEvent on a
@@ -586,6 +586,13 @@ int grl_rank_metrics(const int32_t* idx, int64_t ld, const int32_t* q_pids, cons
  * k <= 1024 (GRL_EUNSUPPORTED beyond). */
 int grl_topk_block(const float* d, int64_t ld, const int32_t* cidx, int64_t ldc, int nq, int ncols, int col0, int k,
                    uint64_t* run_key, float* run_val, void* stream);
+/* grl_topk_block that skips junk as eva_functions.evaluate does: a column whose gallery index g (col0 + column, or
+ * cidx[q][column]) has g_pids[g] == q_pids[q] && g_cams[g] == q_cams[q] is skipped as cidx < 0 is.  q_pids / q_cams
+ * [nq]; g_pids / g_cams are indexed by the gallery index, so they cover the whole gallery, not the block.  Order,
+ * padding and the limit on k are grl_topk_block's. */
+int grl_topk_block_filtered(const float* d, int64_t ld, const int32_t* cidx, int64_t ldc, int nq, int ncols, int col0,
+                            int k, uint64_t* run_key, float* run_val, const int32_t* q_pids, const int32_t* q_cams,
+                            const int32_t* g_pids, const int32_t* g_cams, void* stream);
 /* candidates of query q = gallery entries with its pid: q_slot[q] indexes the CSR pid_ptr / pid_list (ascending
  * gallery indices per pid; -1 = the pid is not in the gallery).  The keys of those inside the block go to
  * cand_key[cand_off[q] + j] (j = position in the pid's list). */

@@ -3,7 +3,7 @@
 materialised path (cosin_dist + rank_rows + rank_metrics), in one process, with warm-ups:
 
   1. MARS size (1980 x 13290 x 6144): materialised vs streaming (default block = one pass; block_cols=2048);
-  2. search(k=100) alone at MARS size;
+  2. search(k=100) alone at MARS size, without and with the junk filter (exclude=);
   3. a large synthetic case (default 10^4 x 10^6 x 256, random unit rows on the device), run only where the
      materialised path would need more than the block budget: streaming metrics and search(k=100), with the
      peak torch.cuda.max_memory_allocated over the inputs.
@@ -81,6 +81,10 @@ def main():
         res['mars_cosin_dist_ms'] = timed(lambda: engine.cosin_dist(qf, gf), a.reps)
         res['mars_search_k100_ms'] = timed(lambda: engine.search(qf, gf, 100), a.reps)
         res['mars_search_k100_2048_ms'] = timed(lambda: engine.search(qf, gf, 100, block_cols=2048), a.reps)
+        ex = (qp, gp, qc, gc)                 # junk-filtered lists (same pid AND camera dropped), same process
+        res['mars_search_k100_exclude_ms'] = timed(lambda: engine.search(qf, gf, 100, exclude=ex), a.reps)
+        res['mars_search_k100_2048_exclude_ms'] = timed(
+            lambda: engine.search(qf, gf, 100, exclude=ex, block_cols=2048), a.reps)
         res['mars_peak_materialised_bytes'] = peak_over_inputs(materialised)
         res['mars_peak_streaming_bytes'] = peak_over_inputs(streaming())
         res['mars_peak_streaming_2048_bytes'] = peak_over_inputs(streaming(2048))
