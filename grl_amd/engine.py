@@ -1327,6 +1327,81 @@ def _search_blocks(blocks, nq, k, sharded, junk=None):
     return run_val, idx
 
 
+# ----------------------------------------------------------------------------
+# query expansion and database-side augmentation (expand.hip)
+# ----------------------------------------------------------------------------
+EXPAND_ALPHA_MAX = 8
+
+
+def _expand_args(m, alpha, m_max, what):
+    """(m, alpha) as ints, or ValueError: 1 <= m <= m_max, 0 <= alpha <= 8, both integers."""
+    import numbers
+    for name, v in (('m', m), ('alpha', alpha)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError('%s: %s must be an integer (got %r)' % (what, name, v))
+    if not 1 <= m <= m_max:
+        raise ValueError('%s: m must be in 1..%d (got %r)' % (what, m_max, m))
+    if not 0 <= alpha <= EXPAND_ALPHA_MAX:
+        raise ValueError('%s: alpha must be in 0..%d (got %r)' % (what, EXPAND_ALPHA_MAX, alpha))
+    return int(m), int(alpha)
+
+
+def expand_from_lists(xf, bank, dist, idx, m, alpha=0, skip_self=False):
+    """A new [n, d] float32 tensor: row i is the weighted mean of ``xf[i]`` (weight 1) and its first ``m`` kept
+    neighbours ``bank[idx[i, t]]`` of the lists ``(dist, idx)`` [n, L] (``search``'s return values: float32 distances,
+    int64 indices, -1 = padding; with ``skip_self`` the entry idx == i is skipped, which needs xf and bank to have the
+    same rows).  Weight of a neighbour: 1 for ``alpha`` == 0, else max(-dist, 0) ** alpha by alpha - 1 products
+    (for 'cosine' lists -dist is the dot product).  One grl_expand_rows launch: the n x m x d gather ``bank[idx]`` is
+    never built, and the summation order is fixed (tests/expand_ref.py reproduces it bit for bit)."""
+    if idx.dim() != 2 or tuple(dist.shape) != tuple(idx.shape) or idx.shape[0] != xf.shape[0]:
+        raise ValueError('expand_from_lists: dist and idx must both be [%d, L] (got %s, %s)'
+                         % (xf.shape[0], tuple(dist.shape), tuple(idx.shape)))
+    m, alpha = _expand_args(m, alpha, idx.shape[1], 'expand_from_lists')
+    if skip_self and xf.shape[0] != bank.shape[0]:
+        raise ValueError('expand_from_lists: skip_self needs xf and bank to have the same rows (got %d, %d)'
+                         % (xf.shape[0], bank.shape[0]))
+    require_device(xf, 'xf'); require_device(bank, 'bank'); require_device(dist, 'dist')
+    if not (idx.is_cuda and idx.dtype == torch.int64):
+        raise _lib.GrlHipError('expand_from_lists needs the int64 device index lists of search')
+    n, nb = xf.shape[0], bank.shape[0]
+    xf, bank = xf.contiguous().view(n, -1), bank.contiguous().view(nb, -1)
+    if xf.shape[1] != bank.shape[1]:
+        raise ValueError('xf and bank have different feature sizes (%d, %d)' % (xf.shape[1], bank.shape[1]))
+    d, L = xf.shape[1], idx.shape[1]
+    out = _new((n, d), xf)
+    if n == 0:
+        return out
+    dist, idx = dist.contiguous(), idx.contiguous()
+    _call('grl_expand_rows', ptr(xf), d, ptr(bank), d, ptr(idx), ptr(dist), L, n, nb, d, L, m, alpha,
+          1 if skip_self else 0, ptr(out), d)
+    return out
+
+
+def expand_features(xf, bank, m, alpha=0, metric='cosine', exclude=None, skip_self=False, block_cols=None,
+                    block_bytes=None):
+    """Query expansion (AQE, alpha-QE) / database-side augmentation of feature rows, on the device: ``search(xf, bank,
+    m + (1 if skip_self else 0), metric, exclude, ...)`` and ``expand_from_lists`` on its lists.  Row i of the result is
+    (xf[i] + sum_p w_p bank[j_p]) / (1 + sum_p w_p) over its ``m`` nearest bank rows j_p; w_p = 1 (``alpha`` = 0) or
+    (xf[i] . bank[j_p]) ** alpha clamped at 0 (``alpha`` in 1..8, 'cosine' only: 'euclidean' lists carry no similarity
+    and take alpha = 0).  1 <= m <= SEARCH_K_MAX - 1.  ``skip_self``: xf IS bank (DBA), row i does not expand with
+    itself -- the search asks for one more neighbour and the kernel drops the entry idx == i.  ``exclude`` has
+    ``search``'s meaning (the evaluator's junk rule: same pid AND camera).  The result is a new tensor; xf and bank are
+    only read.  Under torch.distributed ``search`` is collective and returns identical lists on every rank; every rank
+    then expands all rows itself, so the result is identical on every rank with no further exchange."""
+    m, alpha = _expand_args(m, alpha, SEARCH_K_MAX - 1, 'expand_features')
+    if metric not in ('cosine', 'euclidean'):
+        raise ValueError("metric must be 'cosine' or 'euclidean' (got %r)" % (metric,))
+    if alpha > 0 and metric != 'cosine':
+        raise ValueError("expand_features: alpha > 0 weights by the cosine similarity and needs metric='cosine' "
+                         "(got alpha = %d with %r)" % (alpha, metric))
+    if skip_self and xf.shape[0] != bank.shape[0]:
+        raise ValueError('expand_features: skip_self needs xf and bank to have the same rows (got %d, %d)'
+                         % (xf.shape[0], bank.shape[0]))
+    dist, idx = search(xf, bank, m + (1 if skip_self else 0), metric=metric, exclude=exclude, block_cols=block_cols,
+                       block_bytes=block_bytes)
+    return expand_from_lists(xf, bank, dist, idx, m, alpha, skip_self)
+
+
 def rank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, metric='cosine', max_rank=100,
                            block_cols=None, block_bytes=None):
     """``rank_metrics(rank_rows(D), ...)`` without D or its argsort: (cmc[max_rank] float32, mAP float) of

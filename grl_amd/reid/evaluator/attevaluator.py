@@ -42,6 +42,24 @@ def pairwise_distance_tensor(query_x, gallery_x):
     return engine.pairwise_distance_tensor(query_x, gallery_x)
 
 
+def parse_expand_knob(name, value):
+    """``GRL_EVAL_QE`` / ``GRL_EVAL_DBA``: "m" or "m,alpha" -> (m, alpha); unset or empty -> None.  Anything else is a
+    ValueError that names the variable (the ranges are engine.expand_features')."""
+    if value is None or not value.strip():
+        return None
+    parts = [p.strip() for p in value.split(',')]
+    try:
+        if len(parts) > 2:
+            raise ValueError
+        m, alpha = int(parts[0]), (int(parts[1]) if len(parts) == 2 else 0)
+    except ValueError:
+        raise ValueError('%s must be "m" or "m,alpha" with integer m and alpha (got %r)' % (name, value))
+    if not 1 <= m <= engine.SEARCH_K_MAX - 1 or not 0 <= alpha <= engine.EXPAND_ALPHA_MAX:
+        raise ValueError('%s: m must be in 1..%d and alpha in 0..%d (got %r)'
+                         % (name, engine.SEARCH_K_MAX - 1, engine.EXPAND_ALPHA_MAX, value))
+    return m, alpha
+
+
 class ATTEvaluator(object):
     def __init__(self, cnn_model, Siamese_model, only_eval):
         self.cnn_model = cnn_model
@@ -150,6 +168,8 @@ class ATTEvaluator(object):
         if stream and rerank and not rerank_stream:
             raise ValueError('GRL_EVAL_STREAM=1 cannot re-rank: k-reciprocal re-ranking needs the full query/gallery '
                              'distance matrices, which the streaming evaluator never builds (unset GRL_EVAL_STREAM)')
+        dba = parse_expand_knob('GRL_EVAL_DBA', os.environ.get('GRL_EVAL_DBA'))
+        qe = parse_expand_knob('GRL_EVAL_QE', os.environ.get('GRL_EVAL_QE'))
         qf, q_pids, q_camids = self.extract_feature(query_loader)
         print('Done, obtained {}-by-{} matrix'.format(qf.size(0), qf.size(1)))
         gf, g_pids, g_camids = self.extract_feature(gallery_loader)
@@ -157,6 +177,16 @@ class ATTEvaluator(object):
         g_pids = np.append(q_pids, g_pids)
         g_camids = np.append(q_camids, g_camids)
         print('Done, obtained {}-by-{} matrix'.format(gf.size(0), gf.size(1)))
+        # feature-side post-processing, off by default (engine.expand_features): database-side augmentation replaces every
+        # gallery row by the weighted mean of itself and its m nearest other rows, query expansion then does the same
+        # for the queries against the (augmented) gallery, under the junk rule CMC / mAP apply.  Everything below runs
+        # on the new tensors unchanged.
+        if dba is not None:
+            print('Database-side augmentation: m = {}, alpha = {}'.format(*dba))
+            gf = engine.expand_features(gf, gf, dba[0], dba[1], skip_self=True)
+        if qe is not None:
+            print('Query expansion: m = {}, alpha = {}'.format(*qe))
+            qf = engine.expand_features(qf, gf, qe[0], qe[1], exclude=(q_pids, g_pids, q_camids, g_camids))
         print("Computing distance matrix")
         if visual:
             self._visualize(query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, rerank)

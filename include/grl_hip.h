@@ -40,7 +40,7 @@ const char* grl_last_error(void);
  * The column-block search / ranking entry points grl_topk_block .. grl_rank_finish were added at 10: they change no
  * struct layout or argument list, and a library without them fails to bind in _lib.load.  So were the streaming
  * re-ranking entry points grl_rrs_*, the CSR / CSC assembly of its sharded form (grl_rrs_expand_rows, grl_rrs_scan,
- * grl_rrs_place, grl_rrs_transpose) among them, and grl_topk_block_filtered. */
+ * grl_rrs_place, grl_rrs_transpose) among them, grl_topk_block_filtered and grl_expand_rows. */
 #define GRL_ABI_VERSION 10
 int grl_abi_version(void);
 /* `waiter` (a hipStream_t) waits for everything enqueued on `signaler` so far: hipEventRecord + hipStreamWaitEvent on a
@@ -613,6 +613,23 @@ int grl_rank_count_block(const float* d, int64_t ld, int nq, int col0, int ncols
  * ascending i, fp64) */
 int grl_rank_finish(int nq, const int64_t* cand_off, const int32_t* n_match, const int32_t* hist,
                     int32_t* first_hit, int32_t* n_hits, double* ap, void* stream);
+
+/* ---- query expansion / database-side augmentation (expand.hip, engine.expand_from_lists / expand_features) ----
+ * out[i] = (x[i] + sum_p w_p * bank[j_p]) / (1 + sum_p w_p): a gather and a weighted sum over feature rows, without
+ * the n x m x d tensor of bank[idx].  x [n][ldx], bank [nb][ldb], out [n][ldo] fp32 (d used); idx int64 / dist fp32
+ * [n][ldl] (L used) are the neighbour lists of grl_topk_block as engine.search returns them (index -1 = padding).
+ * Kept neighbours of row i: walk the list left to right, skip idx < 0 (and idx >= nb), with skip_self skip idx == i
+ * (n == nb then), keep the first m that remain -- fewer may.  Weight: s = dist < 0 ? -dist : 0 (NaN -> 0; for the
+ * 'cosine' lists dist = -dot); alpha == 0: w = 1; alpha in 1..8: w = s, then alpha - 1 times w = w * s.  Per element,
+ * in exactly this order: acc = x[i][e], wsum = 1; per kept neighbour in list order acc = acc + (w * bank[j][e])
+ * (product rounded, then the sum: no fma) and wsum = wsum + w; out[i][e] = acc / wsum, correctly rounded.  A NaN
+ * result is stored as 0x7fc00000.  tests/expand_ref.py is this paragraph in numpy float32, bit for bit.
+ * Any d, leading dimensions >= d; 16-byte accesses when every pointer and leading dimension allows them.
+ * GRL_EINVAL: m < 1, m > L, alpha outside 0..8, out overlapping x or bank (DBA reads the bank it replaces), skip_self
+ * with n != nb; GRL_EUNSUPPORTED: m > 4096. */
+int grl_expand_rows(const float* x, int64_t ldx, const float* bank, int64_t ldb, const int64_t* idx, const float* dist,
+                    int64_t ldl, int n, int nb, int d, int L, int m, int alpha, int skip_self, float* out, int64_t ldo,
+                    void* stream);
 
 /* ---- k-reciprocal re-ranking on the device (reid/evaluator/rerank.py:37-104) ----
  * N = nq + ng samples (<= 16384).  All matrices fp32 row-major, caller-owned:
