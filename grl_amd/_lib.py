@@ -166,6 +166,10 @@ _SIGNATURES = {
     'grl_rank_count_block': ([_fp, _i64, C.c_int, C.c_int, C.c_int] + [_fp] * 5 + [C.c_int, _fp, _fp], C.c_int),
     'grl_rank_finish': ([C.c_int] + [_fp] * 6 + [_fp], C.c_int),
     'grl_expand_rows': ([_fp, _i64, _fp, _i64, _fp, _fp, _i64] + [C.c_int] * 7 + [_fp, _i64, _fp], C.c_int),
+    'grl_verify_fold': ([_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
+    'grl_verify_rows': ([_fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, _fp],
+                        C.c_int),
+    'grl_verify_finish': ([_fp, _i64, C.c_int, C.c_int, _fp, _fp, _i64, _fp], C.c_int),
     'grl_rerank_build': ([_fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp], C.c_int),
     'grl_rerank_krecip': ([_fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
     'grl_rerank_expand': ([_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp], C.c_int),

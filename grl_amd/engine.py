@@ -1197,6 +1197,110 @@ def _cmc_map(first, nhit, ap, ng, max_rank):
 
 
 # ----------------------------------------------------------------------------
+# ranking by the Siamese verification head (verify.hip)
+# ----------------------------------------------------------------------------
+class VerifyFoldPlan(EvalPlan):
+    """classifierBN -> classifierlinear of a Siamese in eval mode, folded to the weights ``w`` [D] (fp32) and the
+    constant ``c`` (fp64 and fp32 copies, on the device) of the logit difference s(p, g) = sum_d w_d (p_d - g_d)^2 + c
+    (grl_verify_fold).  Cached by ``_plan``: rebuilt when a parameter or a running statistic of the module changes."""
+
+    def __init__(self, siam):
+        super().__init__(siam)
+        bn, lin = siam.classifierBN, siam.classifierlinear
+        self.D = D = bn.num_features
+        self.w = torch.empty(D, dtype=torch.float32, device=self.dev)
+        self.c64 = torch.empty(1, dtype=torch.float64, device=self.dev)
+        self.c32 = torch.empty(1, dtype=torch.float32, device=self.dev)
+        W, b = lin.weight.detach().contiguous(), lin.bias.detach().contiguous()
+        _call('grl_verify_fold', ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var),
+              C.byref(C.c_double(bn.eps)), ptr(W), ptr(b), D, ptr(self.w), ptr(self.c64), ptr(self.c32))
+
+
+class VerifyMetric(object):
+    """The ranking distance F(q, g) = (1 - beta) (-q . g) - beta s(p, g) of ``verify_metric``: what ``_ColumnBlocks``,
+    ``search``, ``rank_metrics_streaming`` and ``verify_dist`` take as ``metric``.  It holds the module, not the folded
+    numbers: ``folded()`` goes through the plan cache, so a weight update is picked up by the next call."""
+
+    def __init__(self, siam, col0, beta):
+        self.siam, self.col0, self.beta = siam, col0, beta
+        self.Dv = siam.classifierBN.num_features
+
+    def folded(self):
+        """(w [Dv] fp32, c fp64 [1], c fp32 [1]) on the device."""
+        p = _plan(self.siam, VerifyFoldPlan)
+        return p.w, p.c64, p.c32
+
+    @property
+    def full(self):
+        """beta < 1: the GEMM runs over the whole row; beta == 1: over the head's slice only."""
+        return self.beta < 1.0
+
+    def check_rows(self, d):
+        """ValueError unless rows of ``d`` columns hold the slice and the NEGDOT GEMM takes the resulting K."""
+        if self.col0 + self.Dv > d:
+            raise ValueError('verify metric: the slice [%d, %d) does not fit rows of %d columns'
+                             % (self.col0, self.col0 + self.Dv, d))
+        if d % 4 or (self.full and d % 32):
+            raise ValueError('verify metric: feature rows of %d columns (the distance GEMM needs a multiple of %d)'
+                             % (d, 32 if self.full else 4))
+
+    def __repr__(self):
+        return 'verify(col0=%d, Dv=%d, beta=%r)' % (self.col0, self.Dv, self.beta)
+
+
+def verify_metric(siam, col0, beta=1.0):
+    """Rank by the trained pair-verification head of ``siam`` (classifierBN + classifierlinear, eval mode) instead of
+    the cosine distance.  With p, g = columns [col0, col0 + input_num) of a query / gallery row, the head's class-1
+    minus class-0 logit is s(p, g) = sum_d w_d (p_d - g_d)^2 + c and sigmoid(s) is the trainer's pair probability; the
+    returned metric is F(q, g) = (1 - beta) (-q . g) + beta (-s(p, g)), 0 < beta <= 1 (beta = 1: the head alone).  It is
+    accepted as ``metric`` by ``search``, ``rank_metrics_streaming`` (and their sharded forms) and ``verify_dist``; the
+    pairs x d tensor of (p - g)^2 is never built.  ValueError: a head with class_num != 2, beta outside
+    (0, 1], a negative or unaligned col0, a head width the kernels or the GEMM cannot take."""
+    import numbers
+    ncls = siam.classifierlinear.out_features
+    if ncls != 2:
+        raise ValueError('verify_metric: the head has class_num = %d; the logit difference needs 2' % ncls)
+    if isinstance(beta, bool) or not isinstance(beta, numbers.Real) or not 0.0 < float(beta) <= 1.0:
+        raise ValueError('verify_metric: beta must be a number in (0, 1] (got %r)' % (beta,))
+    if isinstance(col0, bool) or not isinstance(col0, numbers.Integral) or col0 < 0 or col0 % 4:
+        raise ValueError('verify_metric: col0 must be a non-negative multiple of 4 (got %r)' % (col0,))
+    Dv = siam.classifierBN.num_features
+    if siam.classifierlinear.in_features != Dv:
+        raise ValueError('verify_metric: classifierBN has %d features, classifierlinear takes %d'
+                         % (Dv, siam.classifierlinear.in_features))
+    if Dv % 32:           # beta = 1 runs the GEMM over K = Dv; the row kernel reads 16 bytes at a time
+        raise ValueError('verify_metric: a head of width %d (the distance GEMM needs K %% 32 == 0)' % Dv)
+    if siam.training:
+        raise RuntimeError('verify_metric needs siamese.eval(): the fold uses the running statistics')
+    return VerifyMetric(siam, int(col0), float(beta))
+
+
+def verify_dist(qf, gf, metric):
+    """The materialised [nq, ng] matrix of ``metric`` (a ``verify_metric``): one column block of ``_ColumnBlocks``,
+    so every entry has the bits ``search`` and ``rank_metrics_streaming`` see.  Not collective: under
+    torch.distributed shard the gallery rows with grl_amd.dist.sharded_distmat, as for cosin_dist."""
+    if not isinstance(metric, VerifyMetric):
+        raise ValueError('verify_dist: metric must come from verify_metric (got %r)' % (metric,))
+    nq, ng = qf.shape[0], gf.shape[0]
+    blocks = _ColumnBlocks(qf, gf, metric, block_cols=max(ng, 1))
+    if nq == 0 or ng == 0:
+        return _new((nq, ng), blocks.qf)
+    return blocks.block(0, ng)
+
+
+def verify_prob(dist):
+    """sigmoid(-dist): the head's probability that a pair shows the same person, for the distances of a pure-head
+    metric (beta = 1; a blend has no such reading) -- a matrix of ``verify_dist`` or the lists of ``search``.  A
+    convenience for thresholding; padding (+inf) becomes 0."""
+    if torch.is_tensor(dist):
+        return torch.sigmoid(-dist)
+    import numpy as np
+    d = np.asarray(dist, dtype=np.float64)
+    with np.errstate(over='ignore'):
+        return 1.0 / (1.0 + np.exp(d))
+
+
+# ----------------------------------------------------------------------------
 # gallery search and ranking metrics over column blocks (search.hip, DESIGN.md 4n)
 # ----------------------------------------------------------------------------
 SEARCH_BLOCK_BYTES = int(os.environ.get('GRL_SEARCH_BLOCK_BYTES', str(256 << 20)))   # distance block budget
@@ -1208,11 +1312,16 @@ class _ColumnBlocks(object):
     ('cosine' = cosin_dist, 'euclidean' = pairwise_distance_tensor), one GEMM per block into one reused
     buffer.  Every entry is computed by the same fma chain as in the full matrix (the GEMM's order does not
     depend on N; no split-K scratch is handed over), so a block holds the full matrix's bits.  Without
-    ``block_cols`` the width is the largest multiple of 256 columns whose block fits ``block_bytes``."""
+    ``block_cols`` the width is the largest multiple of 256 columns whose block fits ``block_bytes``.
+    ``metric`` may also be a ``verify_metric``: the constructor prepares the modified queries q' and the row terms
+    rq, rg (for the gallery rows [lo, hi) only), a block is the NEGDOT GEMM of q' and grl_verify_finish on it."""
 
     def __init__(self, qf, gf, metric='cosine', block_cols=None, block_bytes=None, lo=0, hi=None):
-        if metric not in ('cosine', 'euclidean'):
-            raise ValueError("metric must be 'cosine' or 'euclidean' (got %r)" % (metric,))
+        vm = metric if isinstance(metric, VerifyMetric) else None
+        if vm is None and metric not in ('cosine', 'euclidean'):
+            raise ValueError("metric must be 'cosine', 'euclidean' or a verify_metric (got %r)" % (metric,))
+        if vm is not None:
+            vm.check_rows(int(torch.Size(qf.shape[1:]).numel()))
         require_device(qf, 'qf'); require_device(gf, 'gf')
         nq, ng = qf.shape[0], gf.shape[0]
         self.qf = qf.contiguous().view(nq, -1)
@@ -1235,10 +1344,31 @@ class _ColumnBlocks(object):
             _call('grl_row_sqnorm', ptr(self.qf), ptr(self.rn), nq, k, k)
             _call('grl_row_sqnorm', ptr(self.gf[lo:hi]), ptr(self.cn), hi - lo, k, k)
         self.lo = lo
+        self.qv = self.rq = self.rg = None
+        if vm is not None:
+            d = self.qf.shape[1]
+            if self.spans and nq:
+                w, c64, _ = vm.folded()
+                beta, full = C.byref(C.c_double(vm.beta)), vm.full     # (a host double, read during the call)
+                self.qv = _new((nq, d if full else vm.Dv), self.qf)
+                self.rq, self.rg = _new((nq,), self.qf), _new((hi - lo,), self.qf)
+                _call('grl_verify_rows', ptr(self.qf), d, nq, d, vm.col0, vm.Dv, ptr(w), beta, ptr(c64), ptr(self.rq),
+                      ptr(self.qv), self.qv.shape[1], 1 if full else 0)
+                _call('grl_verify_rows', ptr(self.gf[lo:hi]), d, hi - lo, d, vm.col0, vm.Dv, ptr(w), beta, None,
+                      ptr(self.rg), None, 0, 0)
 
     def block(self, c0, c1):
         n, k = c1 - c0, self.qf.shape[1]
         out = self.buf[:self.nq * n].view(self.nq, n)
+        if self.qv is not None:
+            vm = self.metric
+            if vm.full:
+                gemm(self.qv, self.gf[c0:c1], out, self.nq, n, k, epilogue=EPI_NEGDOT, math=MATH_F32)
+            else:               # beta = 1: K = the head's width, the gallery slice read in place through ldw
+                gemm(self.qv, self.gf[c0:c1, vm.col0:], out, self.nq, n, vm.Dv, ldw=k, epilogue=EPI_NEGDOT,
+                     math=MATH_F32)
+            _call('grl_verify_finish', ptr(out), n, self.nq, n, ptr(self.rq), ptr(self.rg), c0 - self.lo)
+            return out
         if self.metric == 'cosine':
             return gemm(self.qf, self.gf[c0:c1], out, self.nq, n, k, epilogue=EPI_NEGDOT, math=MATH_F32)
         return gemm(self.qf, self.gf[c0:c1], out, self.nq, n, k, epilogue=EPI_EUCLID, rnorm=self.rn,

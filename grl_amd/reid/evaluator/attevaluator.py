@@ -60,6 +60,24 @@ def parse_expand_knob(name, value):
     return m, alpha
 
 
+def parse_metric_knob(name, value):
+    """``GRL_EVAL_METRIC``: unset, empty or "cosine" -> None (the cosine ranking); "verify" or "verify,beta" ->
+    ('verify', beta) with a float beta in (0, 1] (default 1: the verification head alone; engine.verify_metric).
+    Anything else is a ValueError that names the variable."""
+    if value is None or not value.strip() or value.strip() == 'cosine':
+        return None
+    parts = [p.strip() for p in value.split(',')]
+    try:
+        if parts[0] != 'verify' or len(parts) > 2:
+            raise ValueError
+        beta = float(parts[1]) if len(parts) == 2 else 1.0
+    except ValueError:
+        raise ValueError('%s must be "cosine", "verify" or "verify,beta" with a float beta (got %r)' % (name, value))
+    if not 0.0 < beta <= 1.0:              # (NaN fails both comparisons)
+        raise ValueError('%s: beta must be in (0, 1] (got %r)' % (name, value))
+    return 'verify', beta
+
+
 class ATTEvaluator(object):
     def __init__(self, cnn_model, Siamese_model, only_eval):
         self.cnn_model = cnn_model
@@ -120,14 +138,16 @@ class ATTEvaluator(object):
         feat, pids_all, cams_all = grl_dist.gather_feature_batches(mine, len(data_loader))
         return feat, np.asarray(pids_all), np.asarray(cams_all)
 
-    def _visualize(self, query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, rerank, topk=10):
+    def _visualize(self, query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, rerank, topk=10,
+                   metric='cosine'):
         """``visual=1``: the ranked-results folders of visualize_ranked_results in ``path + 'visual'`` for the query
         positions of GRL_VISUAL_QUERIES (comma list; default 4, the reference's visual_id), and ``ranked.json`` in
         the same folder: {query position: [[gallery position, pid, camid, distance], ...]} (a non-finite distance is
         null; a position the query list does not have is skipped with a printed note).  ``gf`` / ``g_pids`` /
         ``g_camids`` carry the prepended queries, so gallery positions below nq are queries.  The lists are the
         junk-filtered top-k of engine.search / engine.rerank_search (``exclude=``): no matrix, no argsort.  Those
-        calls are collective under torch.distributed; rank 0 alone writes."""
+        calls are collective under torch.distributed; rank 0 alone writes.  ``metric``: engine.search's (the
+        distances of ranked.json are that metric's)."""
         import json
         if query is None or gallery is None:
             raise ValueError('visual=1 needs the query and gallery tuple lists (img_path(s), pid, camid)')
@@ -145,7 +165,7 @@ class ATTEvaluator(object):
         if rerank:
             dist, idx = engine.rerank_search(qf, gf, topk, exclude=ids)
         else:
-            dist, idx = engine.search(qf, gf, topk, exclude=ids)
+            dist, idx = engine.search(qf, gf, topk, metric=metric, exclude=ids)
         if grl_dist._rank_world(None, None)[0] != 0:
             return
         dist, idx = dist.cpu().numpy(), idx.cpu().numpy()
@@ -168,6 +188,11 @@ class ATTEvaluator(object):
         if stream and rerank and not rerank_stream:
             raise ValueError('GRL_EVAL_STREAM=1 cannot re-rank: k-reciprocal re-ranking needs the full query/gallery '
                              'distance matrices, which the streaming evaluator never builds (unset GRL_EVAL_STREAM)')
+        knob = parse_metric_knob('GRL_EVAL_METRIC', os.environ.get('GRL_EVAL_METRIC'))
+        if knob is not None and rerank:
+            raise ValueError('GRL_EVAL_METRIC=%s cannot re-rank: k-reciprocal re-ranking is defined on Euclidean and '
+                             'cosine distance matrices, and the verification head\'s distance is a signed logit '
+                             '(unset GRL_EVAL_METRIC or evaluate with rerank=0)' % os.environ['GRL_EVAL_METRIC'].strip())
         dba = parse_expand_knob('GRL_EVAL_DBA', os.environ.get('GRL_EVAL_DBA'))
         qe = parse_expand_knob('GRL_EVAL_QE', os.environ.get('GRL_EVAL_QE'))
         qf, q_pids, q_camids = self.extract_feature(query_loader)
@@ -188,6 +213,11 @@ class ATTEvaluator(object):
             print('Query expansion: m = {}, alpha = {}'.format(*qe))
             qf = engine.expand_features(qf, gf, qe[0], qe[1], exclude=(q_pids, g_pids, q_camids, g_camids))
         print("Computing distance matrix")
+        if knob is not None:
+            # rank by the trained pair-verification head, blended with the cosine distance (engine.verify_metric); the
+            # head reads the out_frame slice of the rows [x_uncorr | out_frame | mean].  QE / DBA above ran by cosine.
+            return self._evaluate_verify(knob[1], query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path,
+                                         visual, stream)
         if visual:
             self._visualize(query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, rerank)
         if rerank_stream:
@@ -219,3 +249,15 @@ class ATTEvaluator(object):
             distmat_gg = pairwise_distance_tensor(gf, gf).cpu().numpy()
             distmat = re_ranking(distmat, distmat_qq, distmat_gg)
         return evaluate_seq(distmat, q_pids, q_camids, g_pids, g_camids, path)
+
+    def _evaluate_verify(self, beta, query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, visual, stream):
+        """The three routes of ``evaluate`` (no re-ranking) under GRL_EVAL_METRIC=verify[,beta]."""
+        siam = self.siamese_model
+        vm = engine.verify_metric(siam, qf.size(1) - 2 * siam.input_num, beta)
+        print('Ranking metric: verification head, beta = {:g}'.format(beta))
+        if visual:
+            self._visualize(query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, 0, metric=vm)
+        if stream:
+            return _report(*engine.rank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, metric=vm))
+        dist_dev = grl_dist.sharded_distmat(qf, gf, lambda q, g: engine.verify_dist(q, g, vm))
+        return evaluate_seq(None, q_pids, q_camids, g_pids, g_camids, path, indices=engine.rank_rows(dist_dev))

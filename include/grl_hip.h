@@ -40,7 +40,7 @@ const char* grl_last_error(void);
  * The column-block search / ranking entry points grl_topk_block .. grl_rank_finish were added at 10: they change no
  * struct layout or argument list, and a library without them fails to bind in _lib.load.  So were the streaming
  * re-ranking entry points grl_rrs_*, the CSR / CSC assembly of its sharded form (grl_rrs_expand_rows, grl_rrs_scan,
- * grl_rrs_place, grl_rrs_transpose) among them, grl_topk_block_filtered and grl_expand_rows. */
+ * grl_rrs_place, grl_rrs_transpose) among them, grl_topk_block_filtered, grl_expand_rows and the grl_verify_* entry points. */
 #define GRL_ABI_VERSION 10
 int grl_abi_version(void);
 /* `waiter` (a hipStream_t) waits for everything enqueued on `signaler` so far: hipEventRecord + hipStreamWaitEvent on a
@@ -630,6 +630,36 @@ int grl_rank_finish(int nq, const int64_t* cand_off, const int32_t* n_match, con
 int grl_expand_rows(const float* x, int64_t ldx, const float* bank, int64_t ldb, const int64_t* idx, const float* dist,
                     int64_t ldl, int n, int nb, int d, int L, int m, int alpha, int skip_self, float* out, int64_t ldo,
                     void* stream);
+
+/* ---- ranking by the Siamese verification head (verify.hip, engine.verify_metric / verify_dist) ----
+ * In eval mode classifierBN -> classifierlinear on (p - g)^2 is affine in (p - g)^2; the class-1 minus class-0 logit is
+ * s(p, g) = sum_d w_d (p_d - g_d)^2 + c.  The ranking distance F = (1 - beta)(-q.g) + beta(-s), p / g = columns
+ * [col0, col0 + Dv) of the rows q / g, is  F = -q'.g - (rq + rg):  one NEGDOT GEMM (grl_conv_gemm_f32, unchanged) on
+ * the modified queries q' and the pass grl_verify_finish, with rq = beta (a_q + c), rg = beta a_g,
+ * a_x = sum_d w_d x_d^2 over the slice.
+ *
+ * grl_verify_fold: w[d] = fp32((W[1][d] - W[0][d]) * gamma[d] / sqrt(var[d] + eps)), c = sum_d (W[1][d] - W[0][d]) *
+ *   (beta[d] - gamma[d] * mean[d] / sqrt(var[d] + eps)) + b[1] - b[0], all in fp64 in exactly this operation order
+ *   (tests/verify_ref.py); c is stored as fp64 (*c64) and rounded to fp32 (*c32).  One workgroup: thread t adds its
+ *   d = t, t + 256, ... in ascending order, the 256 sums meet in a binary tree.  W is [2][D], D % 4 == 0.
+ * grl_verify_rows: r[i] = fp32(beta * (sum_d w[d] * x[i][col0 + d]^2 + (c64 ? *c64 : 0))) for n rows x [n][ldx] of d
+ *   columns.  fp64; one wave per row, lane l adds elements 4 (l + 64 j) .. + 3 for j = 0, 1, ... in ascending order, the
+ *   64 sums meet in an xor tree: no dependence on the launch.  With qout, the modified query rows, every element
+ *   computed in fp64 and rounded once: full != 0: qout [n][ldq] has d columns, ((1 - beta) - 2 beta w[e]) x inside the
+ *   slice and (1 - beta) x outside; full == 0: qout has Dv columns, column e = ((1 - beta) - 2 beta w[e]) x[col0 + e]
+ *   (beta = 1: -2 w x; the GEMM then runs over K = Dv against the gallery slice in place, ldw = the gallery's ld).
+ *   d, col0, Dv, ldx, ldq % 4 == 0, 16-byte aligned pointers, 0 < beta <= 1, qout must not overlap x.
+ *   `eps` (fold) and `beta` (rows) point to one double in HOST memory, read during the call: the two scalars keep
+ *   their fp64 value across the ABI.  Every other pointer is device memory.
+ * grl_verify_finish: in place on a distance block D [nq][ld] (n columns used, any ld >= n):
+ *   D[q][j] = D[q][j] - (rq[q] + rg[c0 + j]), the fp32 sum first, then the fp32 difference.  An entry depends on
+ *   nothing but itself, so a column block holds the full matrix's bits.  16-byte accesses from a row's first 16-byte
+ *   boundary on, element by element before it and at the ragged end. */
+int grl_verify_fold(const float* bn_weight, const float* bn_bias, const float* bn_mean, const float* bn_var,
+                    const double* eps, const float* W, const float* b, int D, float* w, double* c64, float* c32, void* stream);
+int grl_verify_rows(const float* x, int64_t ldx, int n, int d, int col0, int Dv, const float* w, const double* beta,
+                    const double* c64, float* r, float* qout, int64_t ldq, int full, void* stream);
+int grl_verify_finish(float* D, int64_t ld, int nq, int n, const float* rq, const float* rg, int64_t c0, void* stream);
 
 /* ---- k-reciprocal re-ranking on the device (reid/evaluator/rerank.py:37-104) ----
  * N = nq + ng samples (<= 16384).  All matrices fp32 row-major, caller-owned:
