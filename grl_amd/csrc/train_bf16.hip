@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void col_stats_b16_kernel(const __bf16* __rest
     const int chunk = blockIdx.y, sub = threadIdx.x % LPR, part = threadIdx.x / LPR, parts = 256 / LPR;
     const int c = blockIdx.x * 256 + sub * 8;
     f32x8 s = zero8(), q = zero8();
-    if (c < C) {
+    if (c < C && part < parts) {
         const int r1 = min(M, (chunk + 1) * CHUNK);
         const f32x8 pv = pivot ? ld8f(pivot + c) : zero8();
 #pragma unroll 4
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_b16_kernel(
     const int chunk = blockIdx.y, sub = threadIdx.x % LPR, part = threadIdx.x / LPR, parts = 256 / LPR;
     const int c = blockIdx.x * 256 + sub * 8;
     f32x8 s = zero8(), q = zero8();
-    if (c < C) {
+    if (c < C && part < parts) {
         const f32x8 mu = ld8f(mean + c), is = ld8f(invstd + c);
         const f32x8 ms = mscale ? ld8f(mscale + c) : zero8(), mb = mbeta ? ld8f(mbeta + c) : zero8();
         const int r1 = min(M, (chunk + 1) * CHUNK);
@@ -572,12 +572,11 @@ __global__ void cast_f32_b16_kernel(const __bf16* __restrict__ x, float* __restr
         st8f(y + i * 8, ld8(x + i * 8));
 }
 
-inline int lpr_for(int C) {         // lanes per row of the column reductions: 8 channels per lane, at most 32 lanes
-    int l = C / 8;
-    if (l > 32) l = 32;
-    int p = 1;
-    while (p * 2 <= l) p *= 2;
-    return p;
+// lanes per row of the column reductions: one lane per 8 channels of a row's (at most 256-channel) column block, so
+// min(32, C / 8), a power of two or not; the 256 % LPR threads that form no whole lane group stay idle (`part < parts`)
+inline int lpr_for(int C) {
+    const int l = C / 8;
+    return l > 32 ? 32 : l;
 }
 
 }  // namespace
