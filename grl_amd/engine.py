@@ -1611,6 +1611,172 @@ def _rank_blocks(blocks, nq, ng, q_pids, g_pids, q_camids, g_camids, sharded):
     return first, nhit, ap
 
 
+# ----------------------------------------------------------------------------
+# pair-level (verification) metrics: ROC, AUC, EER, TPR@FPR over column blocks (roc.hip)
+# ----------------------------------------------------------------------------
+ROC_BITS_MIN, ROC_BITS_MAX, ROC_BITS_DEFAULT = 8, 20, 16
+ROC_FPR_TARGETS = (1e-4, 1e-3, 1e-2, 1e-1)
+
+
+def _roc_bits(bits, what):
+    import numbers
+    if isinstance(bits, bool) or not isinstance(bits, numbers.Integral) or not ROC_BITS_MIN <= bits <= ROC_BITS_MAX:
+        raise ValueError('%s: bits must be an integer in %d..%d (got %r)' % (what, ROC_BITS_MIN, ROC_BITS_MAX, bits))
+    return int(bits)
+
+
+class PairRoc(object):
+    """The verification metrics of a set of (query, gallery) pair distances (lower = more alike), from two histograms
+    over the order-preserving uint32 key of the float32 distance, bin = key >> (32 - bits):
+
+      pos, neg     int64 device tensors [2^bits]: same pid from another camera / another pid (same pid AND camera is
+                   dropped, the junk rule of eva_functions.evaluate).  Integer counts: independent of block width,
+                   summation order and sharding.
+      n_pos, n_neg their sums (ValueError at construction if either is 0, saying which)
+      auc          Mann-Whitney: P(a positive's bin < a negative's bin) + 0.5 P(same bin), float64
+      auc_slack    0.5 sum_b pos_b neg_b / (n_pos n_neg): |auc - AUC of the unquantised distances| is at most this,
+                   because only pairs that share a bin can be ordered differently
+      eer          bins are accepted in ascending order; at the first bin boundary where FPR >= 1 - TPR, the FPR
+                   linearly interpolated (in FPR + TPR - 1) between that boundary and the one before it
+      tpr_at_fpr(f)  TPR at the last boundary whose FPR <= f
+      curve()      (fpr, tpr, threshold) float64 / float64 / float32 numpy arrays over the non-empty bins: the rates
+                   after accepting the bin, and the bin's upper edge (accept d <= threshold).  The bin that holds
+                   +inf ends at +inf; a bin above it holds NaN keys only (the last bin, for bits >= 9) and its
+                   threshold is NaN: NaN distances are accepted last
+
+    For a ``verify_metric`` with beta = 1 the distance is the head's negated logit difference, so
+    ``verify_prob(threshold)`` is the pair probability P(same) at which a threshold accepts."""
+
+    def __init__(self, pos, neg, bits):
+        self.pos, self.neg, self.bits = pos, neg, bits
+        self.n_pos, self.n_neg = (int(v) for v in torch.stack((pos.sum(), neg.sum())).tolist())
+        if self.n_pos == 0 or self.n_neg == 0:
+            raise ValueError('pair ROC: no %s pairs (n_pos = %d, n_neg = %d): %s'
+                             % ('positive' if self.n_pos == 0 else 'negative', self.n_pos, self.n_neg,
+                                'no query has a gallery entry of its pid from another camera' if self.n_pos == 0
+                                else 'every gallery entry shares the pid of every query'))
+        self._pts = None
+
+    def _points(self):
+        """(bin ids, pos, neg, tpr, fpr) over the non-empty bins; the rates are those after accepting the bin."""
+        if self._pts is None:
+            import numpy as np
+            p, n = self.pos.cpu().numpy(), self.neg.cpu().numpy()
+            b = np.flatnonzero((p != 0) | (n != 0))
+            p, n = p[b], n[b]
+            self._pts = (b, p, n, np.cumsum(p) / float(self.n_pos), np.cumsum(n) / float(self.n_neg))
+        return self._pts
+
+    @property
+    def auc(self):
+        import numpy as np
+        _, p, n, _, _ = self._points()
+        above = self.n_neg - np.cumsum(n)                  # negatives in higher bins
+        return float((p.astype(np.float64) * (above + 0.5 * n)).sum() / (float(self.n_pos) * float(self.n_neg)))
+
+    @property
+    def auc_slack(self):
+        import numpy as np
+        _, p, n, _, _ = self._points()
+        return float(0.5 * (p.astype(np.float64) * n).sum() / (float(self.n_pos) * float(self.n_neg)))
+
+    @property
+    def eer(self):
+        import numpy as np
+        _, _, _, tpr, fpr = self._points()
+        f = fpr + tpr - 1.0                                # < 0 at the boundary before the first bin, 1 after the last
+        k = int(np.argmax(f >= 0.0))
+        f0, fpr0 = (f[k - 1], fpr[k - 1]) if k > 0 else (-1.0, 0.0)
+        return float(fpr0 + (0.0 - f0) / (f[k] - f0) * (fpr[k] - fpr0))
+
+    def tpr_at_fpr(self, target):
+        import numpy as np
+        _, _, _, tpr, fpr = self._points()
+        k = int(np.searchsorted(fpr, float(target), side='right'))
+        return float(tpr[k - 1]) if k > 0 else 0.0
+
+    def curve(self):
+        import numpy as np
+        b, _, _, tpr, fpr = self._points()
+        shift = np.uint64(32 - self.bits)
+        lower, key = b.astype(np.uint64) << shift, ((b.astype(np.uint64) + 1) << shift) - 1
+        inf_key = np.uint64(0xff800000)                # the keys above +inf are NaN patterns: the bin that holds +inf
+        key = np.where((key > inf_key) & (lower <= inf_key), inf_key, key).astype(np.uint32)       # ends at +inf
+        u = np.where(key & np.uint32(0x80000000), key ^ np.uint32(0x80000000), ~key).astype(np.uint32)
+        return fpr, tpr, u.view(np.float32)
+
+    def summary(self):
+        """The scalar figures as a dict of plain Python numbers (what the evaluator prints and stores)."""
+        return {'bits': self.bits, 'n_pos': self.n_pos, 'n_neg': self.n_neg, 'auc': self.auc,
+                'auc_slack': self.auc_slack, 'eer': self.eer,
+                'tpr_at_fpr': {'%g' % f: self.tpr_at_fpr(f) for f in ROC_FPR_TARGETS}}
+
+
+def _pair_hist_block(d, c0, ids, bits, pos, neg):
+    """One grl_pair_hist_block launch: the block d [nq, ncols] (rows strided by d.stride(0), gallery entries c0 ..)
+    added to pos / neg."""
+    nq, ncols = d.shape
+    _call('grl_pair_hist_block', ptr(d), d.stride(0), nq, c0, ncols, ptr(ids[0]), ptr(ids[1]), ptr(ids[2]),
+          ptr(ids[3]), bits, ptr(pos), ptr(neg))
+
+
+def _roc_blocks(blocks, nq, ng, q_pids, g_pids, q_camids, g_camids, bits, sharded):
+    """The histogram pass of pair_roc over a block source (``spans``, ``block(c0, c1)``, ``qf``): one block, one
+    launch.  Under sharding every rank has counted its own gallery columns; the sum is the whole."""
+    bits = _roc_bits(bits, 'pair ROC')
+    dev = blocks.qf.device
+    ids = (_ids(q_pids, nq, 'q_pids', dev), _ids(q_camids, nq, 'q_camids', dev), _ids(g_pids, ng, 'g_pids', dev),
+           _ids(g_camids, ng, 'g_camids', dev))
+    hist = torch.zeros((2, 1 << bits), dtype=torch.int64, device=dev)
+    if nq:
+        for c0, c1 in blocks.spans:
+            _pair_hist_block(blocks.block(c0, c1), c0, ids, bits, hist[0], hist[1])
+    if sharded:
+        from . import dist as grl_dist
+        grl_dist._all_reduce_sum(hist)
+    return PairRoc(hist[0], hist[1], bits)
+
+
+def pair_roc(qf, gf, q_pids, g_pids, q_camids, g_camids, metric='cosine', bits=ROC_BITS_DEFAULT, block_cols=None,
+             block_bytes=None):
+    """ROC / AUC / EER / TPR@FPR of all (query, gallery) pairs under ``metric`` ('cosine', 'euclidean' or a
+    ``verify_metric``) as a ``PairRoc``, without the query x gallery matrix: CMC and mAP look at the order inside a
+    query's row, this asks whether ONE threshold separates same-identity from different-identity pairs.  The column
+    blocks are those of ``search`` and ``rank_metrics_streaming`` (same bits as the full matrix); each is read once by
+    grl_pair_hist_block, which classifies the entries by the id arrays (no nq x ng mask) and counts them in two
+    int64 histograms of 2^bits bins (8 <= bits <= 20).  The host receives those two arrays, whatever nq x ng is.
+    Under torch.distributed the gallery rows are sharded over the ranks and the histograms are all-reduced (integer
+    sums: bit-equal to one process); every rank returns the full result.  ValueError: bad ``bits``, id lists of the
+    wrong length, no positive or no negative pair."""
+    bits = _roc_bits(bits, 'pair_roc')
+    nq, ng = qf.shape[0], gf.shape[0]
+    lo, hi, sharded = _shard(ng)
+    blocks = _ColumnBlocks(qf, gf, metric, block_cols, block_bytes, lo, hi)
+    return _roc_blocks(blocks, nq, ng, q_pids, g_pids, q_camids, g_camids, bits, sharded)
+
+
+def pair_roc_matrix(distmat, q_pids, g_pids, q_camids, g_camids, bits=ROC_BITS_DEFAULT):
+    """``pair_roc`` of a [nq, ng] float32 distance matrix that already lives on the device (cosin_dist, verify_dist,
+    the device re_ranking's result); rows may be strided (a column slice of a wider matrix is read in place).  Not
+    collective: every rank that holds the matrix gets the result from it."""
+    bits = _roc_bits(bits, 'pair_roc_matrix')
+    require_device(distmat, 'distmat')
+    if distmat.dim() != 2:
+        raise ValueError('pair_roc_matrix: distmat must be [nq, ng] (got %s)' % (tuple(distmat.shape),))
+    nq, ng = distmat.shape
+    if nq and ng and (distmat.stride(1) != 1 or distmat.stride(0) < ng):
+        distmat = distmat.contiguous()
+
+
+    class _Whole(object):                           # a block source of one block: the matrix itself
+        spans = [(0, ng)] if ng else []
+        qf = distmat
+
+        @staticmethod
+        def block(c0, c1):
+            return distmat
+    return _roc_blocks(_Whole, nq, ng, q_pids, g_pids, q_camids, g_camids, bits, False)
+
 
 # ----------------------------------------------------------------------------
 # streaming k-reciprocal re-ranking (rerank_stream.hip, DESIGN.md 4o)
@@ -1824,3 +1990,14 @@ def rerank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, k1=20, 
     first, nhit, ap = _rank_blocks(_RerankBlocks(qf, gf, rr, block_cols, block_bytes), rr.nq, rr.ng, q_pids, g_pids,
                                    q_camids, g_camids, rr.sharded)
     return _cmc_map(first, nhit, ap, rr.ng, max_rank)
+
+
+def rerank_pair_roc(qf, gf, q_pids, g_pids, q_camids, g_camids, k1=20, k2=6, lambda_value=0.3, bits=ROC_BITS_DEFAULT,
+                    block_cols=None, block_bytes=None):
+    """``pair_roc`` on the k-reciprocal re-ranked distances F of ``rerank_search``: the ``PairRoc`` of
+    ``pair_roc_matrix(F, ...)``, bin for bin, without F.  Sharded under torch.distributed as
+    ``rerank_metrics_streaming`` is, the final pass with pair_roc's all-reduce of the two histograms."""
+    bits = _roc_bits(bits, 'rerank_pair_roc')
+    rr = _Rerank(qf, gf, k1, k2, lambda_value, block_cols, block_bytes)
+    return _roc_blocks(_RerankBlocks(qf, gf, rr, block_cols, block_bytes), rr.nq, rr.ng, q_pids, g_pids, q_camids,
+                       g_camids, bits, rr.sharded)

@@ -18,20 +18,43 @@ __all__ = ['ATTEvaluator', 'evaluate_seq', 'cosin_dist', 'pairwise_distance_tens
 
 
 def evaluate_seq(distmat, query_pids, query_camids, gallery_pids, gallery_camids, path,
-                 cmc_topk=(1, 5, 10, 20), indices=None):
+                 cmc_topk=(1, 5, 10, 20), indices=None, roc_lines=()):
     """Prints mAP / Rank-k in the reference's format and returns Rank-1
     (attevaluator.py:15-30)."""
     cmc_scores, mAP = evaluate(distmat, np.array(query_pids), np.array(gallery_pids),
                                np.array(query_camids), np.array(gallery_camids), indices=indices)
-    return _report(cmc_scores, mAP, cmc_topk)
+    return _report(cmc_scores, mAP, cmc_topk, roc_lines)
 
 
-def _report(cmc_scores, mAP, cmc_topk=(1, 5, 10, 20)):
+def _report(cmc_scores, mAP, cmc_topk=(1, 5, 10, 20), roc_lines=()):
     print('Mean AP: {:4.1%}'.format(mAP))
     for r in cmc_topk:
         print("Rank-{:<3}: {:.1%}".format(r, cmc_scores[r - 1]))
+    for line in roc_lines:                    # GRL_EVAL_ROC: the pair-level figures (_roc_report); none by default
+        print(line)
     print("------------------")
     return cmc_scores[0]
+
+
+def _roc_report(roc, metric_name, path):
+    """GRL_EVAL_ROC: the lines ``_report`` prints after the CMC for a ``engine.PairRoc``, and ``path + 'roc.json'``
+    (rank 0 alone writes): the scalar figures, ``bits``, the metric's name and the curve over the non-empty bins.
+    Strict JSON: a threshold that is not finite (the +inf bin, the NaN bin) is null."""
+    import json
+    s = roc.summary()
+    lines = ['ROC AUC: {:.2%} (+/- {:.1e} from binning; n_pos = {}, n_neg = {})'.format(s['auc'], s['auc_slack'],
+                                                                                     s['n_pos'], s['n_neg']),
+             'EER: {:.2%}'.format(s['eer']),
+             'TPR@FPR=1e-3: {:.2%}'.format(s['tpr_at_fpr']['0.001']),
+             'TPR@FPR=1e-2: {:.2%}'.format(s['tpr_at_fpr']['0.01'])]
+    if grl_dist._rank_world(None, None)[0] == 0:
+        fpr, tpr, thr = roc.curve()
+        s['metric'] = metric_name
+        s['curve'] = {'fpr': fpr.tolist(), 'tpr': tpr.tolist(),
+                      'threshold': [float(t) if np.isfinite(t) else None for t in thr]}
+        with open((path or '') + 'roc.json', 'w') as fh:
+            json.dump(s, fh, allow_nan=False)
+    return lines
 
 
 def cosin_dist(qf, gf):
@@ -76,6 +99,23 @@ def parse_metric_knob(name, value):
     if not 0.0 < beta <= 1.0:              # (NaN fails both comparisons)
         raise ValueError('%s: beta must be in (0, 1] (got %r)' % (name, value))
     return 'verify', beta
+
+
+def parse_roc_knob(name, value):
+    """``GRL_EVAL_ROC``: unset or empty -> None (off); "1" -> engine.ROC_BITS_DEFAULT (16); an integer in 8..20 -> that
+    many histogram bits (engine.pair_roc).  Anything else is a ValueError that names the variable."""
+    if value is None or not value.strip():
+        return None
+    try:
+        bits = int(value.strip())
+    except ValueError:
+        raise ValueError('%s must be "1" or an integer number of histogram bits (got %r)' % (name, value))
+    if bits == 1:
+        return engine.ROC_BITS_DEFAULT
+    if not engine.ROC_BITS_MIN <= bits <= engine.ROC_BITS_MAX:
+        raise ValueError('%s: bits must be 1 (the default, %d) or in %d..%d (got %r)'
+                         % (name, engine.ROC_BITS_DEFAULT, engine.ROC_BITS_MIN, engine.ROC_BITS_MAX, value))
+    return bits
 
 
 class ATTEvaluator(object):
@@ -195,6 +235,9 @@ class ATTEvaluator(object):
                              '(unset GRL_EVAL_METRIC or evaluate with rerank=0)' % os.environ['GRL_EVAL_METRIC'].strip())
         dba = parse_expand_knob('GRL_EVAL_DBA', os.environ.get('GRL_EVAL_DBA'))
         qe = parse_expand_knob('GRL_EVAL_QE', os.environ.get('GRL_EVAL_QE'))
+        # pair-level metrics, off by default: ROC AUC / EER / TPR@FPR of the distances the route ranks by
+        # (engine.pair_roc and its forms), printed after the CMC and stored in path + 'roc.json'
+        roc_bits = parse_roc_knob('GRL_EVAL_ROC', os.environ.get('GRL_EVAL_ROC'))
         qf, q_pids, q_camids = self.extract_feature(query_loader)
         print('Done, obtained {}-by-{} matrix'.format(qf.size(0), qf.size(1)))
         gf, g_pids, g_camids = self.extract_feature(gallery_loader)
@@ -217,7 +260,9 @@ class ATTEvaluator(object):
             # rank by the trained pair-verification head, blended with the cosine distance (engine.verify_metric); the
             # head reads the out_frame slice of the rows [x_uncorr | out_frame | mean].  QE / DBA above ran by cosine.
             return self._evaluate_verify(knob[1], query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path,
-                                         visual, stream)
+                                         visual, stream, roc_bits)
+        ids = (q_pids, g_pids, q_camids, g_camids)
+        roc_lines = ()
         if visual:
             self._visualize(query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, rerank)
         if rerank_stream:
@@ -225,23 +270,36 @@ class ATTEvaluator(object):
             # re_ranking below without its (q+g)^2 matrices, for any q + g.  Under torch.distributed the sample passes
             # are sharded by sample range and the final pass by gallery column; every rank gets the full result.
             print('Applying person re-ranking ...')
-            return _report(*engine.rerank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids))
+            if roc_bits:                          # (a second pass over the re-ranking state: the knob's cost here)
+                roc_lines = _roc_report(engine.rerank_pair_roc(qf, gf, *ids, bits=roc_bits), 'rerank(cosine)', path)
+            return _report(*engine.rerank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids),
+                           roc_lines=roc_lines)
         if stream:
             # column blocks of the distance GEMM and exact CMC / mAP without a sort (engine.rank_metrics_streaming); under
             # torch.distributed the gallery columns are sharded and only match keys and rank histograms travel
-            return _report(*engine.rank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids))
+            if roc_bits:
+                roc_lines = _roc_report(engine.pair_roc(qf, gf, *ids, bits=roc_bits), 'cosine', path)
+            return _report(*engine.rank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids),
+                           roc_lines=roc_lines)
+        if roc_bits and rerank and qf.size(0) + gf.size(0) > 16384:
+            raise ValueError('GRL_EVAL_ROC: %d samples re-rank on the host (more than 16384), where no device matrix '
+                             'exists to measure; set GRL_EVAL_RERANK=stream' % (qf.size(0) + gf.size(0)))
         dist_dev = grl_dist.sharded_distmat(qf, gf, cosin_dist)     # gallery rows sharded over the ranks
         # ranking AND the per-query CMC / AP work on the device (one LDS sort network per row up to
         # 16384 gallery entries -- MARS: 11310 -- the chunked network beyond): neither the distance nor
         # the index matrix leaves HBM
         if not rerank:
+            if roc_bits:
+                roc_lines = _roc_report(engine.pair_roc_matrix(dist_dev, *ids, bits=roc_bits), 'cosine', path)
             return evaluate_seq(None, q_pids, q_camids, g_pids, g_camids, path,
-                                indices=engine.rank_rows(dist_dev))
+                                indices=engine.rank_rows(dist_dev), roc_lines=roc_lines)
         if rerank and qf.size(0) + gf.size(0) <= 16384:
             print('Applying person re-ranking ...')            # entirely on the device
             dist_dev = re_ranking(dist_dev, pairwise_distance_tensor(qf, qf), pairwise_distance_tensor(gf, gf))
+            if roc_bits:
+                roc_lines = _roc_report(engine.pair_roc_matrix(dist_dev, *ids, bits=roc_bits), 'rerank(cosine)', path)
             return evaluate_seq(None, q_pids, q_camids, g_pids, g_camids, path,
-                                indices=engine.rank_rows(dist_dev))
+                                indices=engine.rank_rows(dist_dev), roc_lines=roc_lines)
         distmat = dist_dev.cpu().numpy()
         if rerank:                                             # beyond one LDS sort network: host numpy
             print('Applying person re-ranking ...')
@@ -250,14 +308,24 @@ class ATTEvaluator(object):
             distmat = re_ranking(distmat, distmat_qq, distmat_gg)
         return evaluate_seq(distmat, q_pids, q_camids, g_pids, g_camids, path)
 
-    def _evaluate_verify(self, beta, query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, visual, stream):
-        """The three routes of ``evaluate`` (no re-ranking) under GRL_EVAL_METRIC=verify[,beta]."""
+    def _evaluate_verify(self, beta, query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, visual, stream,
+                         roc_bits=None):
+        """The three routes of ``evaluate`` (no re-ranking) under GRL_EVAL_METRIC=verify[,beta].  ``roc_bits``
+        (GRL_EVAL_ROC): the pair-level figures of the same distances; for beta = 1 ``engine.verify_prob`` maps a
+        threshold of roc.json's curve to the head's P(same)."""
         siam = self.siamese_model
         vm = engine.verify_metric(siam, qf.size(1) - 2 * siam.input_num, beta)
         print('Ranking metric: verification head, beta = {:g}'.format(beta))
         if visual:
             self._visualize(query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, 0, metric=vm)
+        ids, roc_lines = (q_pids, g_pids, q_camids, g_camids), ()
         if stream:
-            return _report(*engine.rank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, metric=vm))
+            if roc_bits:
+                roc_lines = _roc_report(engine.pair_roc(qf, gf, *ids, metric=vm, bits=roc_bits), repr(vm), path)
+            return _report(*engine.rank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, metric=vm),
+                           roc_lines=roc_lines)
         dist_dev = grl_dist.sharded_distmat(qf, gf, lambda q, g: engine.verify_dist(q, g, vm))
-        return evaluate_seq(None, q_pids, q_camids, g_pids, g_camids, path, indices=engine.rank_rows(dist_dev))
+        if roc_bits:
+            roc_lines = _roc_report(engine.pair_roc_matrix(dist_dev, *ids, bits=roc_bits), repr(vm), path)
+        return evaluate_seq(None, q_pids, q_camids, g_pids, g_camids, path, indices=engine.rank_rows(dist_dev),
+                            roc_lines=roc_lines)

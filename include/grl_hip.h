@@ -614,6 +614,19 @@ int grl_rank_count_block(const float* d, int64_t ld, int nq, int col0, int ncols
 int grl_rank_finish(int nq, const int64_t* cand_off, const int32_t* n_match, const int32_t* hist,
                     int32_t* first_hit, int32_t* n_hits, double* ap, void* stream);
 
+/* ---- pair-level (verification) histograms of a distance block (roc.hip, engine.pair_roc) ----
+ * ``d`` [nq][ld] (ncols used) is a column block as above.  Entry (q, j), gallery index g = col0 + j: dropped when
+ * g_pids[g] == q_pids[q] && g_cams[g] == q_cams[q] (junk), positive when only the pids agree, negative otherwise.
+ * key = order-preserving uint32 of the float32 (-0 -> +0; sign clear: bits ^ 0x80000000, else ~bits; NaN of either
+ * sign: 0xffffffff); bin = key >> (32 - bits); pos_hist / neg_hist [2^bits] int64 += 1 (integer atomics; zero-filled
+ * by the caller before the first block, accumulated over blocks).  g_pids / g_cams are indexed by the gallery index.
+ * Any ld >= ncols, ncols >= 1, nq >= 0; 16-byte loads when d and ld allow.  GRL_EINVAL: bits outside 8..20, a null
+ * pointer, a negative size.  A workgroup counts in 32-bit LDS slots and handles at most 1024 * ceil(nq / row groups)
+ * entries; GRL_EUNSUPPORTED if that could reach 2^32 (nq >= 2^22 in one call). */
+int grl_pair_hist_block(const float* d, int64_t ld, int nq, int col0, int ncols, const int32_t* q_pids,
+                        const int32_t* q_cams, const int32_t* g_pids, const int32_t* g_cams, int bits,
+                        int64_t* pos_hist, int64_t* neg_hist, void* stream);
+
 /* ---- query expansion / database-side augmentation (expand.hip, engine.expand_from_lists / expand_features) ----
  * out[i] = (x[i] + sum_p w_p * bank[j_p]) / (1 + sum_p w_p): a gather and a weighted sum over feature rows, without
  * the n x m x d tensor of bank[idx].  x [n][ldx], bank [nb][ldb], out [n][ldo] fp32 (d used); idx int64 / dist fp32
