@@ -166,6 +166,12 @@ _SIGNATURES = {
     'grl_rank_count_block': ([_fp, _i64, C.c_int, C.c_int, C.c_int] + [_fp] * 5 + [C.c_int, _fp, _fp], C.c_int),
     'grl_rank_finish': ([C.c_int] + [_fp] * 6 + [_fp], C.c_int),
     'grl_pair_hist_block': ([_fp, _i64, C.c_int, C.c_int, C.c_int] + [_fp] * 4 + [C.c_int, _fp, _fp, _fp], C.c_int),
+    'grl_cluster_edges_block': ([_fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp, _fp], C.c_int),
+    'grl_cluster_init': ([_fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
+    'grl_cluster_round': ([_fp, _fp, _fp, _fp, C.c_int, _fp, _fp], C.c_int),
+    'grl_cluster_border': ([_fp, _fp, _fp, _fp, C.c_int, _fp, _fp], C.c_int),
+    'grl_cluster_roots': ([_fp, _fp, C.c_int, _fp, _fp], C.c_int),
+    'grl_cluster_labels': ([_fp, _fp, _fp, _fp, C.c_int, _fp, _fp], C.c_int),
     'grl_expand_rows': ([_fp, _i64, _fp, _i64, _fp, _fp, _i64] + [C.c_int] * 7 + [_fp, _i64, _fp], C.c_int),
     'grl_verify_fold': ([_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
     'grl_verify_rows': ([_fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, _fp],

@@ -1638,6 +1638,7 @@ class PairRoc(object):
                    because only pairs that share a bin can be ordered differently
       eer          bins are accepted in ascending order; at the first bin boundary where FPR >= 1 - TPR, the FPR
                    linearly interpolated (in FPR + TPR - 1) between that boundary and the one before it
+      eer_threshold  the threshold (float32, as in curve()) of that first boundary
       tpr_at_fpr(f)  TPR at the last boundary whose FPR <= f
       curve()      (fpr, tpr, threshold) float64 / float64 / float32 numpy arrays over the non-empty bins: the rates
                    after accepting the bin, and the bin's upper edge (accept d <= threshold).  The bin that holds
@@ -1688,6 +1689,14 @@ class PairRoc(object):
         k = int(np.argmax(f >= 0.0))
         f0, fpr0 = (f[k - 1], fpr[k - 1]) if k > 0 else (-1.0, 0.0)
         return float(fpr0 + (0.0 - f0) / (f[k] - f0) * (fpr[k] - fpr0))
+
+    @property
+    def eer_threshold(self):
+        """The ``curve()`` threshold (float32) of the bin boundary ``eer`` selects, the first where FPR >= 1 - TPR:
+        accepting d <= eer_threshold is the operating point next to the equal error rate (``cluster``'s eps)."""
+        import numpy as np
+        _, _, _, tpr, fpr = self._points()
+        return self.curve()[2][int(np.argmax(fpr + tpr - 1.0 >= 0.0))]
 
     def tpr_at_fpr(self, target):
         import numpy as np
@@ -1776,6 +1785,234 @@ def pair_roc_matrix(distmat, q_pids, g_pids, q_camids, g_camids, bits=ROC_BITS_D
         def block(c0, c1):
             return distmat
     return _roc_blocks(_Whole, nq, ng, q_pids, g_pids, q_camids, g_camids, bits, False)
+
+
+# ----------------------------------------------------------------------------
+# identity discovery: DBSCAN on the eps-graph of the distance GEMM's column blocks (cluster.hip)
+# ----------------------------------------------------------------------------
+CLUSTER_MAX_EDGES = int(os.environ.get('GRL_CLUSTER_MAX_EDGES', str(1 << 28)))    # col is int32 [E]: 1 GiB at the limit
+CLUSTER_ROUND_BATCH = 4                    # component rounds enqueued per read-back of their "changed" flags
+
+
+def _cluster_eps(eps, what):
+    """eps as the float32 the kernel compares with (a Python float; +inf stays +inf and means FLT_MAX there)."""
+    import numbers
+    import numpy as np
+    if isinstance(eps, bool) or not isinstance(eps, numbers.Real) or eps != eps:
+        raise ValueError('%s: eps must be a number and not NaN (got %r)' % (what, eps))
+    with np.errstate(over='ignore'):
+        return float(np.float32(eps))
+
+
+def _cluster_min_samples(m, what):
+    import numbers
+    if isinstance(m, bool) or not isinstance(m, numbers.Integral) or not 1 <= m <= 2 ** 31 - 1:
+        raise ValueError('%s: min_samples must be an integer >= 1 (got %r)' % (what, m))
+    return int(m)
+
+
+class Clustering(object):
+    """The result of ``cluster`` / ``cluster_matrix`` / ``cluster_from_graph`` (DBSCAN):
+
+      labels       int64 device [n]: cluster id 0, 1, .. in ascending order of each cluster's smallest core index; -1 = noise
+      core         bool device [n]: deg + 1 >= min_samples
+      parent       int32 device [n]: a core point's root (its cluster's smallest core index); i for a non-core point
+      n_clusters, n_noise, n_edges (stored directed edges E), rounds (component rounds run), eps, min_samples
+      pair_scores(pids)   pairwise precision / recall / F1 / ARI of the labels against true identities"""
+
+    def __init__(self, labels, core, parent, n_clusters, n_noise, n_edges, rounds, eps, min_samples):
+        self.labels, self.core, self.parent = labels, core, parent
+        self.n_clusters, self.n_noise, self.n_edges, self.rounds = n_clusters, n_noise, n_edges, rounds
+        self.eps, self.min_samples = eps, min_samples
+
+    def pair_scores(self, pids):
+        """Pair-counting scores of the labels against ``pids`` [n], on the host over the n labels; a noise point is a
+        cluster of its own.  With the contingency table of (cluster, pid): tp = sum over cells of C(count, 2),
+        pred_pairs = sum over clusters, true_pairs = sum over pids, total_pairs = C(n, 2) (Python ints).
+        precision = tp / pred_pairs (1.0 when nothing is predicted together), recall = tp / true_pairs (1.0 when no
+        two samples share a pid), f1 = their harmonic mean (0.0 when both are 0), ari = the adjusted Rand index in
+        its pair-count form 2 (tp tn - fp fn) / ((tp + fn)(fn + tn) + (tp + fp)(fp + tn)), 1.0 when fp = fn = 0.
+        All four are float64."""
+        import numpy as np
+        lab = self.labels.cpu().numpy().astype(np.int64)
+        n = lab.size
+        pids = np.asarray(pids).reshape(-1)
+        if pids.size != n:
+            raise ValueError('pair_scores: expected %d pids, got %d' % (n, pids.size))
+        noise = lab < 0
+        lab[noise] = self.n_clusters + np.arange(int(noise.sum()))
+
+        def pairs(counts):
+            counts = counts.astype(np.int64)
+            return int((counts * (counts - 1) // 2).sum())
+        tp = pred = true = 0
+        if n:
+            pi = np.unique(pids, return_inverse=True)[1].reshape(-1).astype(np.int64)
+            tp = pairs(np.unique(lab * (int(pi.max()) + 1) + pi, return_counts=True)[1])
+            pred = pairs(np.unique(lab, return_counts=True)[1])
+            true = pairs(np.unique(pi, return_counts=True)[1])
+        total = n * (n - 1) // 2
+        fp, fn = pred - tp, true - tp
+        tn = total - tp - fp - fn
+        precision = tp / pred if pred else 1.0
+        recall = tp / true if true else 1.0
+        f1 = 2.0 * precision * recall / (precision + recall) if precision + recall > 0.0 else 0.0
+        ari = 1.0 if fp == 0 and fn == 0 else 2.0 * (tp * tn - fp * fn) / ((tp + fn) * (fn + tn) + (tp + fp) * (fp + tn))
+        return {'precision': float(precision), 'recall': float(recall), 'f1': float(f1), 'ari': float(ari), 'tp': tp,
+                'pred_pairs': pred, 'true_pairs': true, 'total_pairs': total, 'n': n}
+
+
+def _eps_graph_blocks(blocks, n, eps, max_edges=None):
+    """``eps_graph`` over any block source (``spans``, ``block(c0, c1)`` -> the [n, c1 - c0] columns of the n x n
+    distance matrix, ``qf``): count pass, grl_rrs_scan, one read-back of E = row_ptr[n], fill pass."""
+    eps = _cluster_eps(eps, 'eps_graph')
+    limit = CLUSTER_MAX_EDGES if max_edges is None else int(max_edges)
+    dev = blocks.qf.device
+    cnt = torch.zeros(n, dtype=torch.int32, device=dev)
+    row_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n == 0:
+        return row_ptr, torch.empty(0, dtype=torch.int32, device=dev)
+
+    def sweep(rp, col):
+        for c0, c1 in blocks.spans:
+            d = blocks.block(c0, c1)
+            _call('grl_cluster_edges_block', ptr(d), d.stride(0), n, 0, c0, c1 - c0, eps, ptr(cnt), rp, col)
+    sweep(None, None)
+    _call('grl_rrs_scan', ptr(cnt), n, ptr(row_ptr))
+    n_edges = int(row_ptr[n])
+    if n_edges > limit:
+        raise ValueError('eps_graph: eps = %r gives E = %d edges among %d samples, more than the limit of %d '
+                         '(max_edges / GRL_CLUSTER_MAX_EDGES): lower eps or raise the limit' % (eps, n_edges, n, limit))
+    col = torch.empty(n_edges, dtype=torch.int32, device=dev)
+    if n_edges:
+        cnt.zero_()
+        sweep(ptr(row_ptr), ptr(col))
+    return row_ptr, col
+
+
+def _cluster_metric(metric, what):
+    if isinstance(metric, VerifyMetric):
+        raise ValueError('%s: a verify_metric is the signed logit of modified query rows against gallery rows, not a '
+                         "distance between two samples of one set; cluster by 'cosine' or 'euclidean'" % what)
+    if metric not in ('cosine', 'euclidean'):
+        raise ValueError("%s: metric must be 'cosine' or 'euclidean' (got %r)" % (what, metric))
+
+
+def eps_graph(xf, eps, metric='cosine', block_cols=None, block_bytes=None, max_edges=None):
+    """The eps-neighbourhood graph of the rows of ``xf`` as a CSR ``(row_ptr int64 [n+1], col int32 [E])`` on the
+    device, without the n x n matrix: edge i -> j (j != i) iff D[i][j] <= float32(eps), D = ``cosin_dist(xf, xf)``
+    ('cosine': eps is a negated dot product, e.g. -0.7, the unit of roc.json's thresholds) or
+    ``pairwise_distance_tensor(xf, xf)`` ('euclidean').  A NaN distance is no edge; eps = +inf means FLT_MAX.  The
+    column blocks are ``search``'s (the full matrix's bits) and are computed twice: a count pass, one read-back of E, a
+    fill pass.  Columns ascend in every row; the result is the same bit for bit on every run and for every block width.
+    ValueError: a NaN eps, a ``verify_metric``, E above ``max_edges`` (default GRL_CLUSTER_MAX_EDGES = 2^28) -- raised
+    before ``col`` is allocated.  Not sharded: under torch.distributed every rank computes the full, identical graph."""
+    _cluster_metric(metric, 'eps_graph')
+    eps = _cluster_eps(eps, 'eps_graph')
+    require_device(xf, 'xf')
+    if xf.shape[0] == 0:                   # (no rows: no feature size to infer, nothing to compute)
+        return (torch.zeros(1, dtype=torch.int64, device=xf.device), torch.empty(0, dtype=torch.int32, device=xf.device))
+    blocks = _ColumnBlocks(xf, xf, metric, block_cols, block_bytes)
+    return _eps_graph_blocks(blocks, blocks.nq, eps, max_edges)
+
+
+def cluster_from_graph(row_ptr, col, n, min_samples=1, eps=None, _checked=False):
+    """DBSCAN's labels from a neighbourhood graph in CSR form on the device (``row_ptr`` int64 [n+1], ``col`` int32
+    [E]; any order inside a row): deg[i] = the stored entries of row i, core iff deg + 1 >= min_samples, i ~ j iff
+    i -> j or j -> i is stored, clusters = the connected components of the core points under ~, numbered in ascending
+    order of their smallest core index; a non-core point next to a core takes the smallest id among its adjacent
+    cores, everything else is noise (-1).  The components come from rounds of hooking (integer atomicMin) and pointer
+    jumping; the host reads one flag word per ``CLUSTER_ROUND_BATCH`` rounds and raises RuntimeError beyond n + 1
+    rounds.  ``eps`` is only recorded.  Not sharded: every rank computes the full result.  ValueError: a malformed
+    CSR, a bool or non-integer ``min_samples``."""
+    import numbers
+    min_samples = _cluster_min_samples(min_samples, 'cluster_from_graph')
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 0:
+        raise ValueError('cluster_from_graph: n must be an integer >= 0 (got %r)' % (n,))
+    n = int(n)
+    for t, dt, what in ((row_ptr, torch.int64, 'row_ptr'), (col, torch.int32, 'col')):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.dim() == 1):
+            raise ValueError('cluster_from_graph: %s must be a 1-d %s device tensor' % (what, dt))
+    if row_ptr.numel() != n + 1:
+        raise ValueError('cluster_from_graph: row_ptr must have n + 1 = %d entries (got %d)' % (n + 1, row_ptr.numel()))
+    row_ptr, col = row_ptr.contiguous(), col.contiguous()
+    dev, n_edges = row_ptr.device, col.numel()
+    length = row_ptr[1:] - row_ptr[:-1]
+    if not _checked:                       # a caller's graph: the kernels index parent / core by col
+        bad = torch.stack((row_ptr[0] != 0, row_ptr[n] != n_edges,
+                           (length < 0).any() if n else row_ptr[0] != 0,
+                           ((col < 0) | (col >= n)).any() if n_edges else row_ptr[0] != 0)).tolist()
+        if any(bad):
+            raise ValueError('cluster_from_graph: malformed CSR (%s)' % ', '.join(
+                w for w, b in zip(('row_ptr[0] != 0', 'row_ptr[n] != len(col)', 'row_ptr descends',
+                                   'a column outside 0..n-1'), bad) if b))
+    deg = length.to(torch.int32)
+    core = torch.empty(n, dtype=torch.uint8, device=dev)
+    parent = torch.empty(n, dtype=torch.int32, device=dev)
+    border = torch.empty(n, dtype=torch.int32, device=dev)
+    labels = torch.empty(n, dtype=torch.int64, device=dev)
+    if n == 0:
+        return Clustering(labels, core.bool(), parent, 0, 0, 0, 0, eps, min_samples)
+    _call('grl_cluster_init', ptr(deg), n, min_samples, ptr(core), ptr(parent), ptr(border))
+    flags = torch.empty(CLUSTER_ROUND_BATCH, dtype=torch.int32, device=dev)
+    rounds, cap, done = 0, n + 1, False
+    while not done:
+        if rounds >= cap:
+            raise RuntimeError('cluster_from_graph: the components did not settle in %d rounds' % cap)
+        batch = min(CLUSTER_ROUND_BATCH, cap - rounds)
+        flags.zero_()
+        for r in range(batch):
+            _call('grl_cluster_round', ptr(row_ptr), ptr(col), ptr(core), ptr(parent), n, flags.data_ptr() + 4 * r)
+        changed = flags[:batch].tolist()                 # one read-back per batch
+        quiet = changed.index(0) if 0 in changed else -1
+        rounds += batch if quiet < 0 else quiet + 1      # rounds after the first quiet one changed nothing
+        done = quiet >= 0
+    _call('grl_cluster_border', ptr(row_ptr), ptr(col), ptr(core), ptr(parent), n, ptr(border))
+    is_root = torch.empty(n, dtype=torch.int32, device=dev)
+    root_id = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    _call('grl_cluster_roots', ptr(core), ptr(parent), n, ptr(is_root))
+    _call('grl_rrs_scan', ptr(is_root), n, ptr(root_id))
+    _call('grl_cluster_labels', ptr(core), ptr(parent), ptr(border), ptr(root_id), n, ptr(labels))
+    n_clusters, n_noise = torch.stack((root_id[n], (labels < 0).sum())).tolist()
+    return Clustering(labels, core.bool(), parent, int(n_clusters), int(n_noise), n_edges, rounds, eps, min_samples)
+
+
+def cluster(xf, eps, min_samples=1, metric='cosine', block_cols=None, block_bytes=None, max_edges=None):
+    """DBSCAN of the rows of ``xf`` at the threshold ``eps`` on the project's own distance ('cosine' = cosin_dist,
+    eps a negated dot product such as ``PairRoc.eer_threshold``; 'euclidean' = pairwise_distance_tensor):
+    ``cluster_from_graph(*eps_graph(xf, eps, metric, ...), n, min_samples)`` as a ``Clustering``.  For a symmetric
+    distance the labels and the core set are those of sklearn's DBSCAN(metric='precomputed'); min_samples = 1 is plain
+    threshold linkage, 2 turns singletons into noise.  The host never holds more than the n labels.  Not sharded:
+    under torch.distributed every rank computes the full, identical result."""
+    min_samples = _cluster_min_samples(min_samples, 'cluster')
+    eps = _cluster_eps(eps, 'cluster')
+    row_ptr, col = eps_graph(xf, eps, metric, block_cols, block_bytes, max_edges)
+    return cluster_from_graph(row_ptr, col, xf.shape[0], min_samples, eps=eps, _checked=True)
+
+
+def cluster_matrix(distmat, eps, min_samples=1, max_edges=None):
+    """``cluster`` on an [n, n] float32 distance matrix that already lives on the device (any square matrix a caller
+    can build; it need not be symmetric: i ~ j iff either entry passes); rows may be strided (a column slice of a
+    wider matrix is read in place).  ValueError: not square.  Not collective: every rank that holds the matrix
+    gets the result from it."""
+    min_samples = _cluster_min_samples(min_samples, 'cluster_matrix')
+    eps = _cluster_eps(eps, 'cluster_matrix')
+    require_device(distmat, 'distmat')
+    if distmat.dim() != 2 or distmat.shape[0] != distmat.shape[1]:
+        raise ValueError('cluster_matrix: distmat must be square [n, n] (got %s)' % (tuple(distmat.shape),))
+    n = distmat.shape[0]
+    if n and (distmat.stride(1) != 1 or distmat.stride(0) < n):
+        distmat = distmat.contiguous()
+
+    class _Whole(object):                           # a block source of one block: the matrix itself
+        spans = [(0, n)] if n else []
+        qf = distmat
+
+        @staticmethod
+        def block(c0, c1):
+            return distmat
+    row_ptr, col = _eps_graph_blocks(_Whole, n, eps, max_edges)
+    return cluster_from_graph(row_ptr, col, n, min_samples, eps=eps, _checked=True)
 
 
 # ----------------------------------------------------------------------------

@@ -30,7 +30,7 @@ def _report(cmc_scores, mAP, cmc_topk=(1, 5, 10, 20), roc_lines=()):
     print('Mean AP: {:4.1%}'.format(mAP))
     for r in cmc_topk:
         print("Rank-{:<3}: {:.1%}".format(r, cmc_scores[r - 1]))
-    for line in roc_lines:                    # GRL_EVAL_ROC: the pair-level figures (_roc_report); none by default
+    for line in roc_lines:                    # GRL_EVAL_ROC / GRL_EVAL_CLUSTER: the extra figures; none by default
         print(line)
     print("------------------")
     return cmc_scores[0]
@@ -54,6 +54,35 @@ def _roc_report(roc, metric_name, path):
                       'threshold': [float(t) if np.isfinite(t) else None for t in thr]}
         with open((path or '') + 'roc.json', 'w') as fh:
             json.dump(s, fh, allow_nan=False)
+    return lines
+
+
+def _cluster_report(knob, qf, gf, ids, path, roc=None):
+    """GRL_EVAL_CLUSTER: DBSCAN of the query-prepended gallery ``gf`` by cosine (engine.cluster) -- the two lines
+    ``_report`` prints after any ROC lines, and ``path + 'clusters.json'`` (rank 0 alone writes; strict JSON).
+    ``knob`` = (eps or 'eer', min_samples); 'eer' is the ``eer_threshold`` of the cosine ``engine.pair_roc`` of
+    (qf, gf), taken from ``roc`` when the route has already computed that one."""
+    import json
+    eps, min_samples = knob
+    if eps == 'eer':
+        if roc is None:
+            roc = engine.pair_roc(qf, gf, *ids)
+        eps = float(roc.eer_threshold)
+        if not math.isfinite(eps):
+            raise ValueError('GRL_EVAL_CLUSTER=eer: the threshold at the equal error rate is %r, not a finite distance '
+                             '(the pairs are not separable by a finite cosine threshold); give eps as a number' % eps)
+    cl = engine.cluster(gf, eps, min_samples)
+    n = int(gf.size(0))
+    scores = cl.pair_scores(ids[1])
+    lines = ['Clusters: {} ({} noise of {}) at cosine eps = {:g}, min_samples = {}'.format(
+                 cl.n_clusters, cl.n_noise, n, cl.eps, cl.min_samples),
+             'Pairwise precision: {:.2%}  recall: {:.2%}  F1: {:.2%}  ARI: {:.4f}'.format(
+                 scores['precision'], scores['recall'], scores['f1'], scores['ari'])]
+    if grl_dist._rank_world(None, None)[0] == 0:
+        with open((path or '') + 'clusters.json', 'w') as fh:
+            json.dump({'eps': cl.eps, 'min_samples': cl.min_samples, 'metric': 'cosine', 'n': n,
+                       'n_clusters': cl.n_clusters, 'n_noise': cl.n_noise, 'n_edges': cl.n_edges,
+                       'pair_scores': scores, 'labels': cl.labels.cpu().tolist()}, fh, allow_nan=False)
     return lines
 
 
@@ -116,6 +145,26 @@ def parse_roc_knob(name, value):
         raise ValueError('%s: bits must be 1 (the default, %d) or in %d..%d (got %r)'
                          % (name, engine.ROC_BITS_DEFAULT, engine.ROC_BITS_MIN, engine.ROC_BITS_MAX, value))
     return bits
+
+
+def parse_cluster_knob(name, value):
+    """``GRL_EVAL_CLUSTER``: unset or empty -> None (off); "eps" or "eps,min_samples" -> (eps, min_samples) with eps a
+    float (a cosine distance: a negated dot product) or the word "eer", and an integer min_samples >= 1 (default 1;
+    engine.cluster).  Anything else is a ValueError that names the variable."""
+    if value is None or not value.strip():
+        return None
+    parts = [p.strip() for p in value.split(',')]
+    try:
+        if len(parts) > 2:
+            raise ValueError
+        eps = 'eer' if parts[0] == 'eer' else float(parts[0])
+        min_samples = int(parts[1]) if len(parts) == 2 else 1
+    except ValueError:
+        raise ValueError('%s must be "eps" or "eps,min_samples" with eps a float or "eer" and an integer min_samples '
+                         '(got %r)' % (name, value))
+    if eps != eps or not 1 <= min_samples <= 2 ** 31 - 1:
+        raise ValueError('%s: eps must not be NaN and min_samples must be >= 1 (got %r)' % (name, value))
+    return eps, min_samples
 
 
 class ATTEvaluator(object):
@@ -238,6 +287,14 @@ class ATTEvaluator(object):
         # pair-level metrics, off by default: ROC AUC / EER / TPR@FPR of the distances the route ranks by
         # (engine.pair_roc and its forms), printed after the CMC and stored in path + 'roc.json'
         roc_bits = parse_roc_knob('GRL_EVAL_ROC', os.environ.get('GRL_EVAL_ROC'))
+        # identity discovery, off by default: DBSCAN of the query-prepended gallery by cosine (engine.cluster), printed
+        # after any ROC lines and stored in path + 'clusters.json'
+        cluster_knob = parse_cluster_knob('GRL_EVAL_CLUSTER', os.environ.get('GRL_EVAL_CLUSTER'))
+        if cluster_knob is not None and knob is not None:
+            raise ValueError('GRL_EVAL_CLUSTER cannot be combined with GRL_EVAL_METRIC=%s: the verification head\'s '
+                             'distance is a signed logit of modified query rows against gallery rows, not a distance '
+                             'between two samples of one set (unset one of them)'
+                             % os.environ['GRL_EVAL_METRIC'].strip())
         qf, q_pids, q_camids = self.extract_feature(query_loader)
         print('Done, obtained {}-by-{} matrix'.format(qf.size(0), qf.size(1)))
         gf, g_pids, g_camids = self.extract_feature(gallery_loader)
@@ -263,6 +320,12 @@ class ATTEvaluator(object):
                                          visual, stream, roc_bits)
         ids = (q_pids, g_pids, q_camids, g_camids)
         roc_lines = ()
+
+        def extra(lines, cosine_roc=None):
+            """the route's ROC lines, then GRL_EVAL_CLUSTER's (always by cosine, whatever the route ranks by)"""
+            if cluster_knob is None:
+                return lines
+            return tuple(lines) + tuple(_cluster_report(cluster_knob, qf, gf, ids, path, cosine_roc))
         if visual:
             self._visualize(query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, rerank)
         if rerank_stream:
@@ -273,14 +336,16 @@ class ATTEvaluator(object):
             if roc_bits:                          # (a second pass over the re-ranking state: the knob's cost here)
                 roc_lines = _roc_report(engine.rerank_pair_roc(qf, gf, *ids, bits=roc_bits), 'rerank(cosine)', path)
             return _report(*engine.rerank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids),
-                           roc_lines=roc_lines)
+                           roc_lines=extra(roc_lines))
         if stream:
             # column blocks of the distance GEMM and exact CMC / mAP without a sort (engine.rank_metrics_streaming); under
             # torch.distributed the gallery columns are sharded and only match keys and rank histograms travel
+            roc = None
             if roc_bits:
-                roc_lines = _roc_report(engine.pair_roc(qf, gf, *ids, bits=roc_bits), 'cosine', path)
+                roc = engine.pair_roc(qf, gf, *ids, bits=roc_bits)
+                roc_lines = _roc_report(roc, 'cosine', path)
             return _report(*engine.rank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids),
-                           roc_lines=roc_lines)
+                           roc_lines=extra(roc_lines, roc))
         if roc_bits and rerank and qf.size(0) + gf.size(0) > 16384:
             raise ValueError('GRL_EVAL_ROC: %d samples re-rank on the host (more than 16384), where no device matrix '
                              'exists to measure; set GRL_EVAL_RERANK=stream' % (qf.size(0) + gf.size(0)))
@@ -289,24 +354,26 @@ class ATTEvaluator(object):
         # 16384 gallery entries -- MARS: 11310 -- the chunked network beyond): neither the distance nor
         # the index matrix leaves HBM
         if not rerank:
+            roc = None
             if roc_bits:
-                roc_lines = _roc_report(engine.pair_roc_matrix(dist_dev, *ids, bits=roc_bits), 'cosine', path)
+                roc = engine.pair_roc_matrix(dist_dev, *ids, bits=roc_bits)
+                roc_lines = _roc_report(roc, 'cosine', path)
             return evaluate_seq(None, q_pids, q_camids, g_pids, g_camids, path,
-                                indices=engine.rank_rows(dist_dev), roc_lines=roc_lines)
+                                indices=engine.rank_rows(dist_dev), roc_lines=extra(roc_lines, roc))
         if rerank and qf.size(0) + gf.size(0) <= 16384:
             print('Applying person re-ranking ...')            # entirely on the device
             dist_dev = re_ranking(dist_dev, pairwise_distance_tensor(qf, qf), pairwise_distance_tensor(gf, gf))
             if roc_bits:
                 roc_lines = _roc_report(engine.pair_roc_matrix(dist_dev, *ids, bits=roc_bits), 'rerank(cosine)', path)
             return evaluate_seq(None, q_pids, q_camids, g_pids, g_camids, path,
-                                indices=engine.rank_rows(dist_dev), roc_lines=roc_lines)
+                                indices=engine.rank_rows(dist_dev), roc_lines=extra(roc_lines))
         distmat = dist_dev.cpu().numpy()
         if rerank:                                             # beyond one LDS sort network: host numpy
             print('Applying person re-ranking ...')
             distmat_qq = pairwise_distance_tensor(qf, qf).cpu().numpy()
             distmat_gg = pairwise_distance_tensor(gf, gf).cpu().numpy()
             distmat = re_ranking(distmat, distmat_qq, distmat_gg)
-        return evaluate_seq(distmat, q_pids, q_camids, g_pids, g_camids, path)
+        return evaluate_seq(distmat, q_pids, q_camids, g_pids, g_camids, path, roc_lines=extra(roc_lines))
 
     def _evaluate_verify(self, beta, query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, visual, stream,
                          roc_bits=None):

@@ -40,7 +40,8 @@ const char* grl_last_error(void);
  * The column-block search / ranking entry points grl_topk_block .. grl_rank_finish were added at 10: they change no
  * struct layout or argument list, and a library without them fails to bind in _lib.load.  So were the streaming
  * re-ranking entry points grl_rrs_*, the CSR / CSC assembly of its sharded form (grl_rrs_expand_rows, grl_rrs_scan,
- * grl_rrs_place, grl_rrs_transpose) among them, grl_topk_block_filtered, grl_expand_rows and the grl_verify_* entry points. */
+ * grl_rrs_place, grl_rrs_transpose) among them, grl_topk_block_filtered, grl_expand_rows, the grl_verify_* entry points,
+ * grl_pair_hist_block and the clustering entry points grl_cluster_*. */
 #define GRL_ABI_VERSION 10
 int grl_abi_version(void);
 /* `waiter` (a hipStream_t) waits for everything enqueued on `signaler` so far: hipEventRecord + hipStreamWaitEvent on a
@@ -626,6 +627,40 @@ int grl_rank_finish(int nq, const int64_t* cand_off, const int32_t* n_match, con
 int grl_pair_hist_block(const float* d, int64_t ld, int nq, int col0, int ncols, const int32_t* q_pids,
                         const int32_t* q_cams, const int32_t* g_pids, const int32_t* g_cams, int bits,
                         int64_t* pos_hist, int64_t* neg_hist, void* stream);
+
+/* ---- DBSCAN over column blocks (cluster.hip, engine.eps_graph / cluster / cluster_from_graph) ----
+ * The eps-graph of n samples as a CSR, without the n x n matrix.  ``d`` [nrows][ld] (ncols used) is a block of the
+ * distance matrix: its row r is sample row0 + r, its column j is sample col0 + j.  Edge i -> j iff i != j and
+ * d <= eps (a NaN never passes; eps = +inf is taken as FLT_MAX, the block's own infinities are compared as they are).
+ * Count pass (row_ptr = col = NULL): cnt[row0 + r] += the row's edges in the block.  Fill pass (row_ptr [n+1] from
+ * grl_rrs_scan of the counts, col [E]): the column indices go to col[row_ptr[i] + cnt[i] ..] in ascending order and
+ * cnt[i] += their number, so cnt (int32 [n], zeroed by the caller before each pass) is the row's cursor and the
+ * blocks of a pass must be enqueued in ascending column order on one stream, every row at most once per call.  No
+ * atomics: col is the same bit for bit on every run.  16-byte loads when d and ld allow, single floats otherwise.
+ * GRL_EINVAL: a null pointer, a negative size, ncols < 1, ld < ncols, a NaN eps, row_ptr without col or col without
+ * row_ptr. */
+int grl_cluster_edges_block(const float* d, int64_t ld, int nrows, int row0, int col0, int ncols, float eps,
+                            int32_t* cnt, const int64_t* row_ptr, int32_t* col, void* stream);
+/* core[i] = deg[i] + 1 >= min_samples (a point counts itself), parent[i] = i, border[i] = INT32_MAX.
+ * GRL_EINVAL: min_samples < 1, n < 0, a null pointer with n > 0. */
+int grl_cluster_init(const int32_t* deg, int n, int min_samples, uint8_t* core, int32_t* parent, int32_t* border,
+                     void* stream);
+/* One round of connected components over the core points of a CSR (row_ptr [n+1] int64, col int32 in 0..n-1, any
+ * order, duplicates and self-loops allowed; an edge stored in one direction joins both ends): every stored edge with
+ * two core ends and two different roots hooks the larger root under the smaller (atomicMin) and sets *changed to 1,
+ * then every core node points at its root.  The caller zeroes *changed and repeats until a round leaves it 0: then
+ * parent[i] of a core point is the smallest core index of its component.  parent of a non-core point stays i. */
+int grl_cluster_round(const int64_t* row_ptr, const int32_t* col, const uint8_t* core, int32_t* parent, int n,
+                      int32_t* changed, void* stream);
+/* after convergence: border[j] = the smallest root among the core points adjacent to the non-core point j through an
+ * edge stored in either direction (INT32_MAX: none, noise) */
+int grl_cluster_border(const int64_t* row_ptr, const int32_t* col, const uint8_t* core, const int32_t* parent, int n,
+                       int32_t* border, void* stream);
+/* is_root[i] = core[i] && parent[i] == i (int32, for grl_rrs_scan: root_id [n+1], root_id[n] = the cluster count) */
+int grl_cluster_roots(const uint8_t* core, const int32_t* parent, int n, int32_t* is_root, void* stream);
+/* labels[i] = root_id[parent[i]] (core), root_id[border[i]] (border point), -1 (noise): ids ascend with the root */
+int grl_cluster_labels(const uint8_t* core, const int32_t* parent, const int32_t* border, const int64_t* root_id, int n,
+                       int64_t* labels, void* stream);
 
 /* ---- query expansion / database-side augmentation (expand.hip, engine.expand_from_lists / expand_features) ----
  * out[i] = (x[i] + sum_p w_p * bank[j_p]) / (1 + sum_p w_p): a gather and a weighted sum over feature rows, without
