@@ -206,8 +206,6 @@ inline int row_groups(int n) { return min(max(grl_ceil_div(n, CL_WAVES), 1), CL_
 
 }  // namespace
 
-#define GRL_REQUIRE(cond, msg) do { if (!(cond)) return grl_fail(GRL_EINVAL, msg); } while (0)
-
 extern "C" int grl_cluster_edges_block(const float* d, int64_t ld, int nrows, int row0, int col0, int ncols, float eps,
                                        int32_t* cnt, const int64_t* row_ptr, int32_t* col, void* stream) {
     GRL_REQUIRE(d && cnt, "cluster_edges_block: null");

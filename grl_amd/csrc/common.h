@@ -8,15 +8,70 @@ int grl_check_launch(const char* what);                 // hipGetLastError -> GR
 
 static inline int grl_ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// argument check of an extern "C" entry point
+#define GRL_REQUIRE(cond, msg) do { if (!(cond)) return grl_fail(GRL_EINVAL, msg); } while (0)
+
+// workgroups of a grid-stride launch over n items: 1 .. 8192
+static inline int grid_for(int64_t n, int block = 256) {
+    int64_t g = (n + block - 1) / block;
+    return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
+}
+
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+static __device__ __forceinline__ float sigmoidf_(float z) { return 1.f / (1.f + expf(-z)); }
+
+// 8 channels of a bf16-storage tensor (16 bytes) <-> fp32 registers; 8 consecutive floats (32-byte aligned vectors)
+static __device__ __forceinline__ f32x8 zero8() { return f32x8{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; }
+static __device__ __forceinline__ f32x8 ld8(const __bf16* p) {
+    const bf16x8 v = *reinterpret_cast<const bf16x8*>(p);
+    f32x8 r;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) r[e] = (float)v[e];
+    return r;
+}
+static __device__ __forceinline__ void st8(__bf16* p, const f32x8 v) {
+    bf16x8 r;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) r[e] = (__bf16)v[e];
+    *reinterpret_cast<bf16x8*>(p) = r;
+}
+static __device__ __forceinline__ f32x8 ld8f(const float* p) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+    return f32x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+}
+static __device__ __forceinline__ void st8f(float* p, const f32x8 v) {
+    *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<f32x4*>(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
+}
+
+// first position in [lo, hi) of the ascending array a whose value is >= x
+template <typename I>
+static __device__ __forceinline__ I lower_bound(const int32_t* __restrict__ a, I lo, I hi, int x) {
+    while (lo < hi) {
+        const I mid = (lo + hi) >> 1;
+        if (a[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 // wave64 sum (all lanes receive the total)
-__device__ __forceinline__ float wave_sum(float v) {
+static __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
 
 // block-wide sum for <= 16 waves; `red` is >= 16 floats of LDS. All threads get the total.
-__device__ __forceinline__ float block_sum(float v, float* red) {
+static __device__ __forceinline__ float block_sum(float v, float* red) {
     v = wave_sum(v);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nw = (blockDim.x + 63) >> 6;

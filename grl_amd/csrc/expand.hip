@@ -156,11 +156,7 @@ inline bool overlaps(const float* a, int64_t a_rows, int64_t a_ld, const float* 
     return a0 < b1 && b0 < a1;
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 }  // namespace
-
-#define GRL_REQUIRE(cond, msg) do { if (!(cond)) return grl_fail(GRL_EINVAL, msg); } while (0)
 
 extern "C" int grl_expand_rows(const float* x, int64_t ldx, const float* bank, int64_t ldb, const int64_t* idx,
                                const float* dist, int64_t ldl, int n, int nb, int d, int L, int m, int alpha,

@@ -34,10 +34,6 @@
 #include "../../include/grl_hip.h"
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
 typedef const __attribute__((address_space(1))) void* gptr_t;

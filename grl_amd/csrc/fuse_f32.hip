@@ -28,9 +28,6 @@
 #include "../../include/grl_hip.h"
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 namespace {
 
 // P: conv3 input channels, C4: its output channels (= conv1' input channels), PN: conv1' output channels (0: no chain),

@@ -31,11 +31,6 @@
 #include "../../include/grl_hip.h"
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
 constexpr int TB = 256;                       // tile rows = tile cols

@@ -38,11 +38,6 @@
 
 namespace ring {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 #ifndef GRL_RING_SCHED
 #define GRL_RING_SCHED 2
 #endif

@@ -31,7 +31,6 @@
 namespace {
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int MX_BM = 128, MX_BN = 128, MX_BK = 128;     // tile rows, tile columns, k per stage (4 blocks)
 constexpr int MX_LDS_ROW = MX_BK + 16;                   // LDS row pitch of an operand tile (bytes)

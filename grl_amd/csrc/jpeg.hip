@@ -508,8 +508,6 @@ extern "C" int grl_jpeg_parallel_mode(int on) {
     return was;
 }
 
-#define GRL_REQUIRE(cond, msg) do { if (!(cond)) return grl_fail(GRL_EINVAL, msg); } while (0)
-
 extern "C" int grl_jpeg_parse(const uint8_t* p, int64_t len, int64_t base_off, GrlJpegFrame* out) {
     GRL_REQUIRE(p && out && len >= 4 && base_off >= 0, "jpeg_parse: null / empty");
     GRL_REQUIRE(base_off + len < (1ll << 32), "jpeg_parse: the batch buffer must stay below 4 GiB (32-bit stream offsets)");

@@ -11,8 +11,6 @@
 #include "../../include/grl_hip.h"
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 __device__ __forceinline__ float wave_max(float v) {
@@ -273,8 +271,6 @@ __global__ void scale_dev_kernel(const float* __restrict__ x, const float* __res
 }
 
 }  // namespace
-
-#define GRL_REQUIRE(cond, msg) do { if (!(cond)) return grl_fail(GRL_EINVAL, msg); } while (0)
 
 extern "C" int grl_softmax_ce(const float* logits, int64_t ld, const int64_t* labels, const float* weight, int n,
                               int c, float* loss, float* correct, float* dlogits, int64_t ldd, float* ws,

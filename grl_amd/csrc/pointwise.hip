@@ -9,12 +9,9 @@
 #include <stdlib.h>
 #include "../../include/grl_hip.h"
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "sort_order.h"
 
 namespace {
-
-__device__ __forceinline__ float sigmoidf_(float z) { return 1.f / (1.f + expf(-z)); }
 
 // ---------------------------------------------------------------------------------
 __global__ void pack_conv_weight_kernel(const float* __restrict__ w, float* __restrict__ out,
@@ -107,7 +104,6 @@ __global__ __launch_bounds__(256) void stem_conv7x7_kernel(
 // read with ds_read_b32 through a k -> patch-offset table, the B operand with
 // ds_read_b128 (rows padded to 164 floats: conflict-free).  Same k-permutation as the
 // GEMM kernel: lane half h supplies k = 8q + 4h + s at step s of chunk q.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int SM_TH = 8, SM_TW = 16;                 // output tile
 constexpr int SM_PH = 2 * SM_TH + 5, SM_PW = 2 * SM_TW + 5, SM_PWP = SM_PW + 1;   // 21 x 37 (+1)
 constexpr int SM_K = 160, SM_WLD = 164;
@@ -592,19 +588,11 @@ __global__ __launch_bounds__(256) void pair_verify_kernel(
 }
 
 // Row-wise argsort of the distance matrix (eva_functions.py:139 `np.argsort(distmat, axis=1)`)
-// as one LDS bitonic network per row: (key, index) pairs, ascending, ties broken by the
-// smaller index (np.argsort(kind='stable') order; numpy's default introsort leaves ties
-// unspecified).  One workgroup of 1024 lanes per row, n <= 16384 (128 KiB of LDS).
-// Keys are compared as order-preserving unsigned integers so that the comparator is a strict
-// total order for every input: -0 == +0, NaN (any sign) sorts after +inf as in numpy, and the
-// padding of the network after every real element -- the output is always a permutation of 0..n-1.
+// as one LDS bitonic network per row: (key, index) pairs in the total order of sort_order.h,
+// ascending, ties broken by the smaller index.  One workgroup of 1024 lanes per row,
+// n <= 16384 (128 KiB of LDS).  The padding of the network sorts after every real element --
+// the output is always a permutation of 0..n-1.
 constexpr int SORT_MAX = 16384;
-__device__ __forceinline__ unsigned sort_key(float v) {
-    unsigned u = __float_as_uint(v);
-    if (v != v) u = 0x7fc00000u;                       // canonical NaN
-    else if (v == 0.f) u = 0u;                         // -0 -> +0
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 __global__ __launch_bounds__(1024) void row_argsort_kernel(const float* __restrict__ d, int64_t ld,
                                                            int n, int P, int* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned sm_sort[];
@@ -613,7 +601,7 @@ __global__ __launch_bounds__(1024) void row_argsort_kernel(const float* __restri
     const int row = blockIdx.x, tid = threadIdx.x;
     const float* dr = d + (int64_t)row * ld;
     for (int i = tid; i < P; i += 1024) {
-        key[i] = i < n ? sort_key(dr[i]) : 0xffffffffu;
+        key[i] = i < n ? order_key(dr[i]) : 0xffffffffu;
         idx[i] = i < n ? i : 0x7fffffff;
     }
     __syncthreads();
@@ -657,7 +645,7 @@ __global__ __launch_bounds__(1024) void sort_chunk_kernel(const float* __restric
         const float* dr = d + (int64_t)row * ld;
         for (int i = tid; i < SORT_CH; i += 1024) {
             const int gi = g0 + i;
-            key[i] = gi < n ? sort_key(dr[gi]) : 0xffffffffu;
+            key[i] = gi < n ? order_key(dr[gi]) : 0xffffffffu;
             idx[i] = gi < n ? gi : 0x7fffffff;
         }
     } else {
@@ -698,11 +686,6 @@ __global__ void sort_global_step_kernel(unsigned* __restrict__ gkey, int* __rest
         const bool gt = ki > kl || (ki == kl && ii > il);
         if (gt == asc) { rk[i] = kl; rk[l] = ki; ri[i] = il; ri[l] = ii; }
     }
-}
-
-inline int grid_for(int64_t n, int block = 256) {
-    int64_t g = (n + block - 1) / block;
-    return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
 }
 
 }  // namespace
@@ -782,8 +765,6 @@ __global__ void resize_bilinear_u8_kernel(const uint8_t* __restrict__ x, uint8_t
     }
 }
 }  // namespace
-
-#define GRL_REQUIRE(cond, msg) do { if (!(cond)) return grl_fail(GRL_EINVAL, msg); } while (0)
 
 extern "C" int grl_resize_bilinear_u8(const uint8_t* x, uint8_t* y, const int* bounds_h, const int* coefs_h, int kh,
                                       const int* bounds_v, const int* coefs_v, int kv, int64_t planes, int Hin,
@@ -894,8 +875,6 @@ static int stem_launch(const float* x, const float* norm, const float* w, const 
 // rows go to LDS as [pixel][channel] fp32 (16-byte chunks XOR-swizzled), the pooling threads read 3 x 3 windows
 // against the carried previous row.  The k order differs from stem_mfma_kernel's (c, ky, kx) walk: same products,
 // another fp32 summation order (tested against torch at 1e-5 like the stem itself).  128 frames: 239 + 75 us -> ~170.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16p __attribute__((ext_vector_type(16)));
 constexpr int FP_TW = 64;                              // stem columns = the full width of a 128-pixel-wide frame
 constexpr int FP_ROWP = 2 * FP_TW + 6;                 // cells per staged input row: columns -3 .. 130
 constexpr int FP_ROWB = FP_ROWP * 4;                   // 536 bytes
@@ -994,7 +973,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool_f32_kernel(
             pv[k] = load_row(rr >> 2, 4 * py + 9 + (rr & 3));
         }
         __builtin_amdgcn_sched_barrier(0);                     // (hipcc otherwise sinks the loads below the MFMAs, next to their use)
-        f32x16p acc[2];
+        f32x16 acc[2];
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
 #pragma unroll

@@ -8,26 +8,7 @@
 #include "../../include/grl_hip.h"
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
-
-__device__ __forceinline__ f32x8 ld8(const __bf16* p) {
-    const bf16x8 v = *reinterpret_cast<const bf16x8*>(p);
-    f32x8 r;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = (float)v[e];
-    return r;
-}
-__device__ __forceinline__ void st8(__bf16* p, const f32x8 v) {
-    bf16x8 r;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = (__bf16)v[e];
-    *reinterpret_cast<bf16x8*>(p) = r;
-}
-__device__ __forceinline__ float sigmoidf_(float z) { return 1.f / (1.f + expf(-z)); }
 
 __global__ void cast_bf16_kernel(const float* __restrict__ x, __bf16* __restrict__ y, int64_t n8) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n8;
@@ -185,7 +166,6 @@ __global__ void add_strided_b16_kernel(const __bf16* __restrict__ a, const __bf1
 // reads and writes); rows are padded to 368 bytes so that the ds_read_b128 fragment reads hit distinct
 // bank slots.  (Round 1 ordered k as (c, ky, kx) unpadded, K = 147 -> 160, and gathered element by
 // element with k/49, k/7, k%7 per element: 0.96 ms per 512 frames, VALU-bound at 4 % MFMA busy.)
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int SB_TH = 8, SB_TW = 16, SB_PH = 2 * SB_TH + 5, SB_PW = 2 * SB_TW + 5, SB_PWP = SB_PW + 1;
 constexpr int SB_CH = 22;                                      // 8-wide k chunks: 21 (channel, ky) rows + one of zeros
 constexpr int SB_K = SB_CH * 8, SB_ROWB = SB_K * 2 + 16;       // 176 k; bytes per bf16 row (352 + 16 pad)
@@ -331,14 +311,8 @@ __global__ __launch_bounds__(256) void stem_b16_kernel(
     }
 }
 
-inline int grid_for(int64_t n, int block = 256) {
-    int64_t g = (n + block - 1) / block;
-    return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
-}
-
 }  // namespace
 
-#define GRL_REQUIRE(cond, msg) do { if (!(cond)) return grl_fail(GRL_EINVAL, msg); } while (0)
 #define B16(p) reinterpret_cast<__bf16*>(p)
 #define CB16(p) reinterpret_cast<const __bf16*>(p)
 
@@ -568,8 +542,6 @@ constexpr int S2_LDS = 5 * S2_ROWBUF + S2_PATCHB + 512;       // + folded BatchN
 #define GRL_SP2_KO 0      // timing-only knock-outs (1: no fragment reads / MFMAs, 2: no epilogue, 4: no pooling reads, 8: no input staging); wrong results
 #endif
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4_s2 __attribute__((ext_vector_type(4)));
-typedef float f32x2_s2 __attribute__((ext_vector_type(2)));
 
 template <bool U8>
 __global__ __launch_bounds__(256, 2) void stem_pool2_b16_kernel(
@@ -596,17 +568,17 @@ __global__ __launch_bounds__(256, 2) void stem_pool2_b16_kernel(
         const int iy = ry - 3;
         const bool ok = (unsigned)iy < (unsigned)H;
         const int64_t o = ((int64_t)c * H + (ok ? iy : 0)) * W + 2 * lane;
-        f32x2_s2 v;
+        f32x2 v;
         if constexpr (U8) {
             const unsigned short u = *reinterpret_cast<const unsigned short*>(xu + o);
             v[0] = __builtin_bit_cast(float, (uint32_t)u);
             v[1] = 0.f;
         } else {
-            v = *reinterpret_cast<const f32x2_s2*>(xi + o);
+            v = *reinterpret_cast<const f32x2*>(xi + o);
         }
         return v;
     };
-    auto store_row = [&](int c, int ry, f32x2_s2 v) {
+    auto store_row = [&](int c, int ry, f32x2 v) {
         const bool ok = (unsigned)(ry - 3) < (unsigned)H;
         if constexpr (U8) {
             const uint32_t u = __builtin_bit_cast(uint32_t, v[0]);
@@ -640,7 +612,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool2_b16_kernel(
             asm volatile("" : "+v"(wf[j][s]));                 // (pinned: hipcc re-loaded all 22 fragments inside the row loop)
         }
     constexpr int P_IT = 6;                                     // rows per wave of the 3 x 8 new input rows of an iteration
-    f32x2_s2 pv[P_IT];
+    f32x2 pv[P_IT];
     const int c8 = tid & 7, ppx = tid >> 3;                     // pooling: this thread's pooled column and 8 channels
     __syncthreads();
     for (int it = 0; oyb < oy_end; oyb += 4, ++it) {
@@ -709,8 +681,8 @@ __global__ __launch_bounds__(256, 2) void stem_pool2_b16_kernel(
                         const float tv = acc[cb][j][4 * q + e] * sc[e] + sh[e];
                         v[e] = tv > 0.f ? tv : 0.f;
                     }
-                    *reinterpret_cast<bf16x4_s2*>(rowbuf + myslot * S2_ROWBUF + px * 128 + 8 * hf + (((4 * j + q) ^ ((px >> 1) & 7)) << 4)) =
-                        __builtin_convertvector(v, bf16x4_s2);
+                    *reinterpret_cast<bf16x4*>(rowbuf + myslot * S2_ROWBUF + px * 128 + 8 * hf + (((4 * j + q) ^ ((px >> 1) & 7)) << 4)) =
+                        __builtin_convertvector(v, bf16x4);
                 }
             }
         __syncthreads();                                       // the four stem rows are in rowbuf; nobody reads the patch any more

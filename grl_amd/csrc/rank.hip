@@ -75,8 +75,6 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const int32_t* __rest
 
 }  // namespace
 
-#define GRL_REQUIRE(cond, msg) do { if (!(cond)) return grl_fail(GRL_EINVAL, msg); } while (0)
-
 extern "C" int grl_rank_metrics(const int32_t* idx, int64_t ld, const int32_t* q_pids, const int32_t* q_cams,
                                 const int32_t* g_pids, const int32_t* g_cams, int nq, int ng, int32_t* first_hit,
                                 int32_t* n_hits, double* ap, void* stream) {

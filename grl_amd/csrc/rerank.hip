@@ -179,8 +179,6 @@ __global__ __launch_bounds__(256) void rr_jaccard_kernel(const float* __restrict
 
 }  // namespace
 
-#define GRL_REQUIRE(cond, msg) do { if (!(cond)) return grl_fail(GRL_EINVAL, msg); } while (0)
-
 extern "C" int grl_rerank_build(const float* q_g, const float* q_q, const float* g_g, int nq, int ng, float* D,
                                 float* colmax_ws, void* stream) {
     GRL_REQUIRE(q_g && q_q && g_g && D && colmax_ws && nq > 0 && ng > 0, "rerank_build: bad args");

@@ -19,6 +19,7 @@
 #include "../../include/grl_hip.h"
 #include "common.h"
 #include "rerank_common.h"
+#include "sort_order.h"
 
 namespace {
 
@@ -119,11 +120,7 @@ __global__ __launch_bounds__(64) void rrs_weights_kernel(Seg s, int i0, const fl
 __device__ __forceinline__ float sparse_at(const int32_t* __restrict__ lcnt, const int32_t* __restrict__ lidx,
                                            const float* __restrict__ lval, int row, int e) {
     const int32_t* li = lidx + (int64_t)row * RR_LMAX;
-    int lo = 0, hi = lcnt[row];
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (li[mid] < e) lo = mid + 1; else hi = mid;
-    }
+    const int lo = lower_bound(li, 0, lcnt[row], e);
     return (lo < lcnt[row] && li[lo] == e) ? lval[(int64_t)row * RR_LMAX + lo] : 0.f;
 }
 
@@ -165,17 +162,7 @@ __global__ __launch_bounds__(256) void rrs_expand_kernel(const int32_t* __restri
         es[a] = e;
     }
     __syncthreads();
-    for (int k = 2; k <= P; k <<= 1) {                  // ascending bitonic sort of the P entries
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (P >> 1); t += 256) {
-                const int a = 2 * j * (t / j) + (t % j), b = a + j;
-                const bool asc = (a & k) == 0;
-                const int x = es[a], y = es[b];
-                if ((x > y) == asc) { es[a] = y; es[b] = x; }
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_lds(es, nullptr, P);
     const unsigned long long below = (1ull << lane) - 1ull;
     int n = 0;
     for (int a0 = 0; a0 < total; a0 += 256) {           // ordered compaction, 256 entries per round
@@ -204,15 +191,6 @@ __global__ __launch_bounds__(256) void rrs_expand_kernel(const int32_t* __restri
         __syncthreads();
     }
     if (tid == 0 && !row_ptr) cnt[i] = n;
-}
-
-// first position in [lo, hi) of the ascending array a whose value is >= x
-__device__ __forceinline__ int64_t lower_bound_rows(const int32_t* __restrict__ a, int64_t lo, int64_t hi, int x) {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 // One wave per (query q, chunk of RRS_CHUNK columns of the block).  The block holds q x g distances x
@@ -244,8 +222,8 @@ __global__ __launch_bounds__(64) void rrs_final_kernel(float* __restrict__ d, in
         if (a < qe) {
             const int k = q_col[a];
             v = q_val[a];
-            lo = lower_bound_rows(csc_row, csc_ptr[k], csc_ptr[k + 1], jlo);
-            hi = lower_bound_rows(csc_row, lo, csc_ptr[k + 1], jhi);
+            lo = lower_bound(csc_row, csc_ptr[k], csc_ptr[k + 1], jlo);
+            hi = lower_bound(csc_row, lo, csc_ptr[k + 1], jhi);
         }
         const int m = (int)min((int64_t)64, qe - a0);
         for (int t = 0; t < m; ++t) {
@@ -388,8 +366,6 @@ Seg make_seg(const float* up, int64_t ldu, const float* lo, int64_t lrs, int64_t
 }
 
 }  // namespace
-
-#define GRL_REQUIRE(cond, msg) do { if (!(cond)) return grl_fail(GRL_EINVAL, msg); } while (0)
 
 extern "C" int grl_rrs_segment_rows(const float* up, int64_t ldu, const float* lo, int64_t lo_rs, int64_t lo_cs, int nq,
                                     int ng, int w, float* colmax, float* drows, int64_t ldd, void* stream) {

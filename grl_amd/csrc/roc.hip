@@ -1,7 +1,8 @@
 // Pair-level (verification) histograms of a column block of the query x gallery distance matrix
 // (engine.pair_roc / rerank_pair_roc / pair_roc_matrix).  Every entry is classified by the id arrays
 // (same pid AND camera: dropped; same pid, another camera: positive; another pid: negative), mapped to the
-// order-preserving uint32 key of its float32 and counted in bin = key >> (32 - bits) of its class's histogram.
+// order-preserving uint32 key of its float32 (sort_order.h roc_key) and counted in bin = key >> (32 - bits) of its
+// class's histogram.
 // The counts are integers: they do not depend on the order of the adds, the block width or the sharding.
 //
 // Contention.  More than 99 % of the entries are negatives that fall into a few hundred neighbouring bins, so a
@@ -19,6 +20,7 @@
 #include <stdint.h>
 #include "../../include/grl_hip.h"
 #include "common.h"
+#include "sort_order.h"
 
 namespace {
 
@@ -27,14 +29,6 @@ constexpr int ROC_COLS = 4 * ROC_THREADS;      // columns per workgroup: 16 byte
 constexpr int ROC_SLOTS = 4096;                // LDS table: 4096 x (tag, count) = 32 KiB
 constexpr int ROC_TARGET_GROUPS = 1024;        // ~4 workgroups per CU: the flush is paid once per workgroup
 constexpr unsigned ROC_EMPTY = 0xffffffffu;    // above every tag (a tag has at most 21 bits)
-
-// -0 -> +0, NaN of either sign -> the largest key, ascending otherwise
-__device__ __forceinline__ unsigned roc_key(float v) {
-    unsigned u = __float_as_uint(v);
-    if (v != v) return 0xffffffffu;
-    if (v == 0.f) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u ^ 0x80000000u);
-}
 
 __device__ __forceinline__ void roc_count(float v, int cls, int shift, unsigned* tags, unsigned* cnt,
                                           unsigned long long* pos_hist, unsigned long long* neg_hist) {
@@ -107,8 +101,6 @@ __global__ __launch_bounds__(ROC_THREADS) void pair_hist_kernel(const float* __r
 }
 
 }  // namespace
-
-#define GRL_REQUIRE(cond, msg) do { if (!(cond)) return grl_fail(GRL_EINVAL, msg); } while (0)
 
 extern "C" int grl_pair_hist_block(const float* d, int64_t ld, int nq, int col0, int ncols, const int32_t* q_pids,
                                    const int32_t* q_cams, const int32_t* g_pids, const int32_t* g_cams, int bits,

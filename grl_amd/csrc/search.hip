@@ -4,13 +4,14 @@
 // a block holds exactly the same bits as the same columns of the full matrix.  Everything here is
 // selection, gathering and integer counting; nothing needs the whole matrix.
 //
-// Total order: the one of grl_row_argsort (pointwise.hip sort_key): canonical NaN, -0 -> +0, ascending
+// Total order: the one of grl_row_argsort (sort_order.h order_key): canonical NaN, -0 -> +0, ascending
 // key, ties to the smaller gallery index = np.argsort(kind='stable').  An entry is the 64-bit composite
 // (key << 32) | gallery index, unique per row, so "before" is a plain integer compare.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/grl_hip.h"
 #include "common.h"
+#include "sort_order.h"
 
 namespace {
 
@@ -19,44 +20,6 @@ constexpr int TOPK_MAX = 1024;
 constexpr int MATCH_LIST_MAX = 8192;      // candidates (gallery entries of one pid) per query: one LDS sort
 constexpr int COUNT_CHUNK = 4096;         // gallery columns per workgroup of the rank-count pass
 constexpr uint64_t PAD = ~0ull;           // above every real composite (the largest key is 0xffc00000, NaN)
-
-__device__ __forceinline__ unsigned search_key(float v) {
-    unsigned u = __float_as_uint(v);
-    if (v != v) u = 0x7fc00000u;                       // canonical NaN
-    else if (v == 0.f) u = 0u;                         // -0 -> +0
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ uint64_t composite(unsigned key, int g) {
-    return ((uint64_t)key << 32) | (uint32_t)g;
-}
-
-// Ascending bitonic sort of n (a power of two) LDS entries, optionally carrying a float payload.
-// Callers synchronise before; the last stage ends with a barrier.
-__device__ void bitonic_lds(uint64_t* c, float* v, int n) {
-    for (int k = 2; k <= n; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < (n >> 1); t += blockDim.x) {
-                const int i = 2 * j * (t / j) + (t % j), l = i + j;
-                const bool asc = (i & k) == 0;
-                const uint64_t ci = c[i], cl = c[l];
-                if ((ci > cl) == asc) {
-                    c[i] = cl; c[l] = ci;
-                    if (v) { const float f = v[i]; v[i] = v[l]; v[l] = f; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
-__device__ __forceinline__ int lower_bound_i32(const int32_t* a, int lo, int hi, int x) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 // One workgroup per query row.  LDS holds the row's running list in [0, P) (sorted, the first k entries
 // valid, the rest padding) and a candidate buffer in [P, 2P).  A column enters the buffer only if it comes
@@ -103,7 +66,7 @@ __global__ __launch_bounds__(SEARCH_THREADS) void topk_block_kernel(const float*
             const int g = cidx ? cidx[(int64_t)q * ldc + j] : col0 + j;
             if (g >= 0) {
                 const float x = dr[j];
-                const uint64_t cc = composite(search_key(x), g);
+                const uint64_t cc = composite(order_key(x), g);
                 bool take = cc < thr;
                 if constexpr (FILTER) take = take && !(g_pids[g] == qp && g_cams[g] == qc);
                 if (take) {
@@ -140,11 +103,11 @@ __global__ __launch_bounds__(SEARCH_THREADS) void match_gather_kernel(const floa
     const int s = q_slot[q];
     if (s < 0) return;
     const int lo = pid_ptr[s], hi = pid_ptr[s + 1];
-    const int a = lower_bound_i32(pid_list, lo, hi, col0);
-    const int b = lower_bound_i32(pid_list, a, hi, col0 + ncols);
+    const int a = lower_bound(pid_list, lo, hi, col0);
+    const int b = lower_bound(pid_list, a, hi, col0 + ncols);
     const float* dr = d + (int64_t)q * ld;
     uint32_t* out = cand_key + cand_off[q] - lo;
-    for (int j = a + threadIdx.x; j < b; j += SEARCH_THREADS) out[j] = search_key(dr[pid_list[j] - col0]);
+    for (int j = a + threadIdx.x; j < b; j += SEARCH_THREADS) out[j] = order_key(dr[pid_list[j] - col0]);
 }
 
 // One workgroup per query: keep the candidates from another camera (the query's matches; same pid AND
@@ -218,7 +181,7 @@ __global__ __launch_bounds__(SEARCH_THREADS) void rank_count_kernel(const float*
     for (int j = j0 + tid; j < j1; j += SEARCH_THREADS) {
         const int g = col0 + j;
         if (g_pids[g] == qp) continue;                           // a match or junk: not a kept non-match
-        const uint64_t cc = composite(search_key(dr[j]), g);
+        const uint64_t cc = composite(order_key(dr[j]), g);
         if (cc > last) continue;                                 // after every match (cc != last: indices differ)
         int lo = 0, len = n;
         while (len > 0) {
@@ -264,8 +227,6 @@ int pow2_at_least(int x) {
 }
 
 }  // namespace
-
-#define GRL_REQUIRE(cond, msg) do { if (!(cond)) return grl_fail(GRL_EINVAL, msg); } while (0)
 
 extern "C" int grl_topk_block(const float* d, int64_t ld, const int32_t* cidx, int64_t ldc, int nq, int ncols,
                               int col0, int k, uint64_t* run_key, float* run_val, void* stream) {

@@ -15,11 +15,6 @@
 #include "../../include/grl_hip.h"
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
 constexpr int CHUNK = 128;     // rows per partial of the column reductions
@@ -1111,7 +1106,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs p, const 
     // 64 (not c + 32 i), so a lane's two A (two B) values of a k-step are NEIGHBOURS in the linear LDS row: one ds_read_b64
     // at a compile-time offset instead of a ds_read2_b32 behind a v_add.  Only the labels of the accumulators change (the
     // slab store below un-permutes): every output still sums its pixels in the same order -- bit-identical.
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
     auto rdf = [&](int set, int buf, int s) {
         const float* Ab = As + buf * 32 * BM + wm * WTM + (2 * s + fhalf) * BM;
         const float* Bb = Bs + buf * 32 * BN + wn * WTN + (2 * s + fhalf) * BN;
@@ -1676,15 +1670,13 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ slab, int splits, 
     }
 }
 
-inline int grid_for(int64_t n, int block = 256) {
-    int64_t g = (n + block - 1) / block;
-    g = g < 1 ? 1 : (g > 8192 ? 8192 : g);
-    return (int)(g > 1 ? (g + 1) & ~(int64_t)1 : g);   // even: grid * 256 is then a multiple of every C/4 <= 512 of the path
+// grid_for rounded up to even (8192 is): grid * 256 is then a multiple of every C/4 <= 512 of the path
+inline int grid_even(int64_t n) {
+    const int g = grid_for(n);
+    return g > 1 ? (g + 1) & ~1 : g;
 }
 
 }  // namespace
-
-#define GRL_REQUIRE(cond, msg) do { if (!(cond)) return grl_fail(GRL_EINVAL, msg); } while (0)
 
 extern "C" int grl_col_stats_rows(int M) { return (M + CHUNK - 1) / CHUNK; }
 
@@ -1729,7 +1721,7 @@ extern "C" int grl_bn_apply(const float* z, const float* scale, const float* shi
                             int64_t M, int C, int relu, void* stream) {
     GRL_REQUIRE(z && scale && shift && y && M > 0 && C % 4 == 0, "bn_apply: bad args");
     const int64_t total4 = M * C / 4;
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)stream, z, scale, shift,
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_even(total4)), dim3(256), 0, (hipStream_t)stream, z, scale, shift,
                        res, y, C / 4, total4, relu);
     return grl_check_launch("grl_bn_apply");
 }
@@ -1739,7 +1731,7 @@ extern "C" int grl_bn_apply_centered(const float* z, const float* mean, const fl
                                      void* stream) {
     GRL_REQUIRE(z && mean && scale && y && M > 0 && C % 4 == 0, "bn_apply_centered: bad args");
     const int64_t total4 = M * C / 4;
-    hipLaunchKernelGGL(bn_apply_centered_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)stream, z, mean,
+    hipLaunchKernelGGL(bn_apply_centered_kernel, dim3(grid_even(total4)), dim3(256), 0, (hipStream_t)stream, z, mean,
                        scale, beta, res, y, C / 4, total4, relu, relu_bits);
     return grl_check_launch("grl_bn_apply_centered");
 }
@@ -1776,11 +1768,11 @@ extern "C" int grl_bn_bwd(const float* dy, const float* z, const float* act, con
     if (int e = grl_launch_bn_bwd_finalize(slab_ws, rows, C, (double)M, dgamma, dbeta, coef_ws, s)) return e;
     const int64_t total4 = (int64_t)M * C / 4;
     if (inplace)
-        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(total4)), dim3(256), 0, s, dy, z, (const float*)nullptr, mean,
+        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_even(total4)), dim3(256), 0, s, dy, z, (const float*)nullptr, mean,
                            invstd, gamma, coef_ws, dz, C, total4, (float*)nullptr, 0, (const float*)nullptr, (const float*)nullptr,
                            (const uint8_t*)nullptr);
     else
-        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(total4)), dim3(256), 0, s, dy, z, act, mean, invstd, gamma,
+        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_even(total4)), dim3(256), 0, s, dy, z, act, mean, invstd, gamma,
                            coef_ws, dz, C, total4, gres, gres_accumulate, mask_scale, mask_beta, relu_bits);
     return grl_check_launch("grl_bn_bwd");
 }
@@ -1797,7 +1789,7 @@ extern "C" int grl_bn_bwd_finish(const float* g, const float* z, const float* me
                                           gres2 ? gres_accumulate : 0, nullptr, nullptr, nullptr, s);
     if (int e = grl_launch_bn_bwd_finalize(slab, rows, C, (double)M, dgamma, dbeta, coef_ws, s)) return e;
     const int64_t total4 = (int64_t)M * C / 4;
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(total4)), dim3(256), 0, s, g, z, (const float*)nullptr, mean, invstd,
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_even(total4)), dim3(256), 0, s, g, z, (const float*)nullptr, mean, invstd,
                        gamma, coef_ws, dz, C, total4, gres2, gres2 ? gres_accumulate : 0, (const float*)nullptr,
                        (const float*)nullptr, (const uint8_t*)nullptr);
     return grl_check_launch("grl_bn_bwd_finish");
@@ -1805,14 +1797,14 @@ extern "C" int grl_bn_bwd_finish(const float* g, const float* z, const float* me
 
 extern "C" int grl_relu_bwd(const float* dy, const float* act, float* out, int64_t n, int accumulate, void* stream) {
     GRL_REQUIRE(dy && out && n > 0 && n % 4 == 0, "relu_bwd: bad args");
-    hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, dy, act, out, n / 4,
+    hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_even(n / 4)), dim3(256), 0, (hipStream_t)stream, dy, act, out, n / 4,
                        accumulate);
     return grl_check_launch("grl_relu_bwd");
 }
 
 extern "C" int grl_axpby(const float* a, const float* b, float* y, float alpha, float beta, int64_t n, void* stream) {
     GRL_REQUIRE(a && y && n > 0 && n % 4 == 0, "axpby: bad args");
-    hipLaunchKernelGGL(axpby_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, a, b, y, alpha, beta,
+    hipLaunchKernelGGL(axpby_kernel, dim3(grid_even(n / 4)), dim3(256), 0, (hipStream_t)stream, a, b, y, alpha, beta,
                        n / 4);
     return grl_check_launch("grl_axpby");
 }
@@ -1822,7 +1814,7 @@ extern "C" int grl_axpy_strided(float* dst, int64_t dst_stride, const float* src
     GRL_REQUIRE(dst && src && nb > 0 && inner > 0 && inner % 4 == 0 && dst_stride % 4 == 0 && src_stride % 4 == 0,
                 "axpy_strided: bad args");
     const int64_t total4 = (int64_t)nb * inner / 4;
-    hipLaunchKernelGGL(axpy_strided_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)stream, dst,
+    hipLaunchKernelGGL(axpy_strided_kernel, dim3(grid_even(total4)), dim3(256), 0, (hipStream_t)stream, dst,
                        dst_stride / 4, src, src_stride / 4, inner / 4, alpha, accumulate, total4);
     return grl_check_launch("grl_axpy_strided");
 }
@@ -1842,7 +1834,7 @@ extern "C" int grl_weight_prep(const GrlPrepEntry* table_dev, int count, void* s
 
 extern "C" int grl_pack_dgrad_weight(const float* w, float* out, int N, int C, int kh, int kw, void* stream) {
     GRL_REQUIRE(w && out && N > 0 && C > 0 && kh > 0 && kw > 0, "pack_dgrad_weight: bad args");
-    hipLaunchKernelGGL(pack_dgrad_weight_kernel, dim3(grid_for((int64_t)N * C * kh * kw)), dim3(256), 0,
+    hipLaunchKernelGGL(pack_dgrad_weight_kernel, dim3(grid_even((int64_t)N * C * kh * kw)), dim3(256), 0,
                        (hipStream_t)stream, w, out, N, C, kh * kw);
     return grl_check_launch("grl_pack_dgrad_weight");
 }
@@ -1852,7 +1844,7 @@ extern "C" int grl_dilate2(const float* dz, float* up, int n, int Ho, int Wo, in
     GRL_REQUIRE(dz && up && n > 0 && C % 4 == 0, "dilate2: bad args");
     GRL_REQUIRE((oy_off == 0 || oy_off == 1) && (ox_off == 0 || ox_off == 1), "dilate2: offsets are 0 or 1");
     const int64_t total4 = (int64_t)n * H * W * (C / 4);
-    hipLaunchKernelGGL(dilate2_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)stream, dz, up, Ho, Wo, H, W,
+    hipLaunchKernelGGL(dilate2_kernel, dim3(grid_even(total4)), dim3(256), 0, (hipStream_t)stream, dz, up, Ho, Wo, H, W,
                        C / 4, total4, accumulate, oy_off, ox_off);
     return grl_check_launch("grl_dilate2");
 }
@@ -1861,7 +1853,7 @@ extern "C" int grl_maxpool3x3s2_bwd(const float* x, const float* dy, float* dx, 
                                     void* stream) {
     GRL_REQUIRE(x && dy && dx && n > 0 && C % 4 == 0, "maxpool_bwd: bad args");
     const int64_t total4 = (int64_t)n * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);      // 2x2 input blocks
-    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, H, W,
+    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_even(total4)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, H, W,
                        C / 4, total4);
     return grl_check_launch("grl_maxpool3x3s2_bwd");
 }
@@ -1870,7 +1862,7 @@ extern "C" int grl_bn_relu_maxpool3x3s2(const float* z, const float* mean, const
                                         uint8_t* idx, int n, int H, int W, int C, void* stream) {
     GRL_REQUIRE(z && mean && scale && y && idx && n > 0 && C % 4 == 0 && ((uintptr_t)idx & 3) == 0, "bn_relu_maxpool: bad args");
     const int64_t total = (int64_t)n * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);
-    hipLaunchKernelGGL(bn_relu_maxpool_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, z, mean, scale, beta,
+    hipLaunchKernelGGL(bn_relu_maxpool_kernel, dim3(grid_even(total)), dim3(256), 0, (hipStream_t)stream, z, mean, scale, beta,
                        y, idx, n, H, W, C);
     return grl_check_launch("grl_bn_relu_maxpool3x3s2");
 }
@@ -1879,7 +1871,7 @@ extern "C" int grl_maxpool3x3s2_bwd_idx(const uint8_t* idx, const float* dy, flo
                                         void* stream) {
     GRL_REQUIRE(idx && dy && dx && n > 0 && C % 4 == 0 && ((uintptr_t)idx & 3) == 0, "maxpool_bwd_idx: bad args");
     const int64_t total4 = (int64_t)n * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);      // 2x2 input blocks
-    hipLaunchKernelGGL(maxpool_bwd_idx_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)stream, idx, dy, dx, H, W,
+    hipLaunchKernelGGL(maxpool_bwd_idx_kernel, dim3(grid_even(total4)), dim3(256), 0, (hipStream_t)stream, idx, dy, dx, H, W,
                        C / 4, total4);
     return grl_check_launch("grl_maxpool3x3s2_bwd_idx");
 }
@@ -1887,7 +1879,7 @@ extern "C" int grl_maxpool3x3s2_bwd_idx(const uint8_t* idx, const float* dy, flo
 extern "C" int grl_stem_im2col(const float* x, float* col, int n, int H, int W, int Kp, void* stream) {
     GRL_REQUIRE(x && col && n > 0 && Kp >= 147 && Kp % 32 == 0, "stem_im2col: bad args");
     const int64_t total = (int64_t)n * (H / 2) * (W / 2) * Kp;
-    hipLaunchKernelGGL(stem_im2col_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, col, H, W, Kp,
+    hipLaunchKernelGGL(stem_im2col_kernel, dim3(grid_even(total)), dim3(256), 0, (hipStream_t)stream, x, col, H, W, Kp,
                        total);
     return grl_check_launch("grl_stem_im2col");
 }
@@ -1912,7 +1904,7 @@ extern "C" int grl_stem_wgrad(const float* x, const void* dz, int dz_bf16, float
     else
         hipLaunchKernelGGL(stem_wgrad_kernel<false>, dim3(wgs), dim3(512), 0, s, x, dz, ws, n, H, W);
     if (int e = grl_check_launch("grl_stem_wgrad")) return e;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for((int64_t)64 * (SW_K / 4))), dim3(256), 0, s, ws, wgs,
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_even((int64_t)64 * (SW_K / 4))), dim3(256), 0, s, ws, wgs,
                        (int64_t)64 * SW_K, 64, SW_K, 1, SW_K, dw, 147, accumulate ? 1 : 0);
     return grl_check_launch("grl_stem_wgrad (reduce)");
 }
@@ -2037,7 +2029,7 @@ extern "C" int grl_conv_wgrad_f32(const GrlWgrad* desc, void* stream) {
     GRL_REQUIRE(taps == 1 || kout == d.K, "wgrad conv: k_out is a dense-only option");
     GRL_REQUIRE(kout == d.K || ((uintptr_t)d.dw & 3) == 0, "wgrad: dw alignment");
     GRL_REQUIRE(kout != d.K || taps > 1 || ((uintptr_t)d.dw & 15) == 0, "wgrad: dw must be 16-byte aligned");
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for((int64_t)d.N * (d.K / 4))), dim3(256), 0, s, d.workspace,
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_even((int64_t)d.N * (d.K / 4))), dim3(256), 0, s, d.workspace,
                        real_splits, a.slab_stride, d.N, Cc, taps, d.K, d.dw, kout, d.accumulate);
     return grl_check_launch("grl_conv_wgrad_f32");
 }

@@ -11,42 +11,9 @@
 #include "../../include/grl_hip.h"
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
 constexpr int CHUNK = 128;     // rows per partial of the column reductions (= grl_col_stats_rows)
-
-__device__ __forceinline__ f32x8 zero8() { return f32x8{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; }
-__device__ __forceinline__ f32x8 ld8(const __bf16* p) {
-    const bf16x8 v = *reinterpret_cast<const bf16x8*>(p);
-    f32x8 r;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = (float)v[e];
-    return r;
-}
-__device__ __forceinline__ void st8(__bf16* p, const f32x8 v) {
-    bf16x8 r;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = (__bf16)v[e];
-    *reinterpret_cast<bf16x8*>(p) = r;
-}
-__device__ __forceinline__ f32x8 ld8f(const float* p) {      // 8 consecutive floats (32-byte aligned vectors)
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-    return f32x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-__device__ __forceinline__ void st8f(float* p, const f32x8 v) {
-    *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
-    *reinterpret_cast<f32x4*>(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
-}
-__device__ __forceinline__ float sigmoidf_(float z) { return 1.f / (1.f + expf(-z)); }
-
-inline int grid_for(int64_t n, int block = 256) {
-    int64_t g = (n + block - 1) / block;
-    return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
-}
 
 // ---------------------------------------------------------------------------------
 // y = relu?((z - mean) * scale + beta + res)        (train-mode BatchNorm apply, centred first as torch does)
@@ -581,7 +548,6 @@ inline int lpr_for(int C) {
 
 }  // namespace
 
-#define GRL_REQUIRE(cond, msg) do { if (!(cond)) return grl_fail(GRL_EINVAL, msg); } while (0)
 #define B16(p) reinterpret_cast<__bf16*>(p)
 #define CB16(p) reinterpret_cast<const __bf16*>(p)
 static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }

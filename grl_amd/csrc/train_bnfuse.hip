@@ -19,10 +19,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int FA_CH = 64;        // channels per workgroup
 constexpr int FA_ROWS = 64;      // most slab rows the fused form takes
 
@@ -244,8 +240,6 @@ int grl_launch_bn_bwd_finapply(int b16, const float* slab, int rows, int C, doub
     }
     return grl_check_launch("bn_bwd_finapply");
 }
-
-#define GRL_REQUIRE(cond, msg) do { if (!(cond)) return grl_fail(GRL_EINVAL, msg); } while (0)
 
 static int finalize_apply(int b16, const float* slab, int rows, int C, int64_t count, const float* gamma, const float* beta,
                           float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum, float eps,

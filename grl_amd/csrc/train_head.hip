@@ -7,11 +7,8 @@
 #include "../../include/grl_hip.h"
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
-__device__ __forceinline__ float sigmoidf_(float z) { return 1.f / (1.f + expf(-z)); }
 __device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
 
 // map = sigmoid(y[m*ldy]) ; xc = x*map ; xu = x*(1-map)        (one wave per pixel row)
@@ -329,14 +326,7 @@ __global__ __launch_bounds__(256) void oim_update_kernel(float* __restrict__ lut
     }
 }
 
-inline int grid_for(int64_t n, int block = 256) {
-    int64_t g = (n + block - 1) / block;
-    return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
-}
-
 }  // namespace
-
-#define GRL_REQUIRE(cond, msg) do { if (!(cond)) return grl_fail(GRL_EINVAL, msg); } while (0)
 
 extern "C" int grl_gate_apply(const float* y, int ldy, const float* x, float* cmap, float* xc, float* xu, int M,
                               int C, void* stream) {

@@ -150,11 +150,7 @@ __global__ __launch_bounds__(FINISH_THREADS) void verify_finish_kernel(float* __
     }
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 }  // namespace
-
-#define GRL_REQUIRE(cond, msg) do { if (!(cond)) return grl_fail(GRL_EINVAL, msg); } while (0)
 
 extern "C" int grl_verify_fold(const float* bn_weight, const float* bn_bias, const float* bn_mean, const float* bn_var,
                                const double* eps, const float* W, const float* b, int D, float* w, double* c64,

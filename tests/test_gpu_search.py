@@ -107,6 +107,67 @@ def test_search_ties_and_signed_zero():
         engine.search(torch.from_numpy(qf).to(DEV), torch.from_numpy(gf).to(DEV), 1025)
 
 
+def _order_key(bits):
+    """order_key of grl_amd/csrc/sort_order.h on the uint32 bit patterns of float32 values (integer arithmetic, so
+    that no host float operation meets a signalling NaN): canonical NaN, -0 -> +0, order-preserving uint32."""
+    u = bits.copy()
+    mag = u & np.uint32(0x7fffffff)
+    u[mag > 0x7f800000] = 0x7fc00000                            # v != v
+    u[mag == 0] = 0                                             # v == 0.f
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def test_argsort_topk_and_pair_hist_share_one_order():
+    """grl_row_argsort, grl_topk_block and grl_pair_hist_block on one hand-made block of special values (no GEMM):
+    both zeros, both infinities, NaN of either sign with and without payload, the smallest and largest denormal of
+    either sign, +-FLT_MAX, each repeated on both sides of column 256 (topk_block_kernel's chunk), between normals.
+    run_val carries the block's own bits (include/grl_hip.h), so a NaN comes back with the sign and payload it went
+    in with; the canonical NaN 0x7fc00000 it is ranked as is read from the key half of run_key."""
+    from grl_amd import engine
+    from grl_amd._lib import ptr
+    nq, n = 4, 320
+    special = np.array([0x00000000, 0x80000000, 0x7f800000, 0xff800000, 0x7fc00000, 0xffc00000, 0x7fa00001, 0xffc12345,
+                        0x00000001, 0x80000001, 0x007fffff, 0x807fffff, 0x7f7fffff, 0xff7fffff], np.uint32)
+    g = np.random.Generator(np.random.PCG64(11))
+    bits = g.standard_normal((nq, n)).astype(np.float32).view(np.uint32)
+    for r in range(nq):                                         # 3 copies left of column 256, 2 right, shuffled per row
+        left, right = g.permutation(256)[:3 * special.size], 256 + g.permutation(64)[:2 * special.size]
+        bits[r, left] = np.tile(special, 3)
+        bits[r, right] = np.tile(special, 2)
+    key = _order_key(bits)
+    nan = (bits & np.uint32(0x7fffffff)) > 0x7f800000
+    assert nan.sum() == nq * 20 and (key[nan] == 0xffc00000).all()
+    assert (key[(bits & np.uint32(0x7fffffff)) == 0] == 0x80000000).all()
+    d = torch.from_numpy(bits.view(np.int32)).to(DEV).view(torch.float32)
+    assert torch.equal(d.view(torch.int32).cpu(), torch.from_numpy(bits.view(np.int32)))        # every payload arrived
+
+    order = engine.rank_rows(d).long()
+    assert np.array_equal(order.cpu().numpy(), np.argsort(key, axis=1, kind='stable'))
+    run_key = torch.full((nq, n), -1, dtype=torch.int64, device=DEV)
+    run_val = torch.full((nq, n), float('inf'), dtype=torch.float32, device=DEV)
+    engine._call('grl_topk_block', ptr(d), n, None, 0, nq, n, 0, n, ptr(run_key), ptr(run_val))
+    assert torch.equal(run_key & 0xffffffff, order)
+    assert torch.equal(run_val.view(torch.int32), torch.gather(d, 1, order).view(torch.int32))
+    ranked_as = (run_key >> 32) & 0xffffffff                    # the key every entry was ranked by: NaN as 0x7fc00000
+    assert np.array_equal(ranked_as.cpu().numpy(), np.take_along_axis(key, order.cpu().numpy(), 1).astype(np.int64))
+
+    def hist(block, nrows):
+        """neg histogram at bits = 8 of a contiguous block: every pair is a negative, nothing is junk"""
+        ids = [torch.full((m,), v, dtype=torch.int32, device=DEV) for m, v in
+               ((nrows, 0), (nrows, 0), (block.shape[1], 1), (block.shape[1], 0))]
+        pos = torch.zeros(256, dtype=torch.int64, device=DEV)
+        neg = torch.zeros(256, dtype=torch.int64, device=DEV)
+        engine._pair_hist_block(block, 0, ids, 8, pos, neg)
+        assert int(pos.sum()) == 0
+        return neg.cpu().numpy()
+    neg = hist(d, nq)
+    assert neg.sum() == nq * n and np.array_equal(neg, np.bincount((key >> 24).ravel(), minlength=256))
+    nans = d[0][torch.from_numpy(nan[0]).to(DEV)].contiguous().view(1, -1)       # 20 NaN of every kind: the last bin
+    assert np.array_equal(np.flatnonzero(hist(nans, 1)), [255]) and nans.shape[1] == 20
+    zeros = torch.tensor([[0x00000000, -0x80000000]], dtype=torch.int32, device=DEV).view(torch.float32)
+    assert hist(zeros, 1)[128] == 2                                              # +0 and -0: one bin
+
+
 def _per_query_ref(full, qp, gp, qc, gc):
     from grl_amd import engine, _lib
     from grl_amd._lib import ptr
