@@ -172,6 +172,11 @@ _SIGNATURES = {
     'grl_cluster_border': ([_fp, _fp, _fp, _fp, C.c_int, _fp, _fp], C.c_int),
     'grl_cluster_roots': ([_fp, _fp, C.c_int, _fp, _fp], C.c_int),
     'grl_cluster_labels': ([_fp, _fp, _fp, _fp, C.c_int, _fp, _fp], C.c_int),
+    'grl_kmeans_relabel': ([_fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp], C.c_int),
+    'grl_kmeans_label_counts': ([_fp, C.c_int, C.c_int, _fp, _fp], C.c_int),
+    'grl_kmeans_members': ([_fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp], C.c_int),
+    'grl_segment_rowsum': ([_fp, _i64, C.c_int, _fp, _fp, _i64, C.c_int, C.c_int, _fp, _i64, _fp], C.c_int),
+    'grl_kmeans_finish': ([_fp, _i64, _fp, _fp, _fp, _i64, C.c_int, C.c_int, C.c_int, _fp, _i64, _fp, _fp], C.c_int),
     'grl_expand_rows': ([_fp, _i64, _fp, _i64, _fp, _fp, _i64] + [C.c_int] * 7 + [_fp, _i64, _fp], C.c_int),
     'grl_verify_fold': ([_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
     'grl_verify_rows': ([_fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, _fp],

@@ -1818,7 +1818,8 @@ class Clustering(object):
       core         bool device [n]: deg + 1 >= min_samples
       parent       int32 device [n]: a core point's root (its cluster's smallest core index); i for a non-core point
       n_clusters, n_noise, n_edges (stored directed edges E), rounds (component rounds run), eps, min_samples
-      pair_scores(pids)   pairwise precision / recall / F1 / ARI of the labels against true identities"""
+      pair_scores(pids)   pairwise precision / recall / F1 / ARI of the labels against true identities
+      centroids(xf, reduce='unit')   the clusters' centres (cluster_centroids)"""
 
     def __init__(self, labels, core, parent, n_clusters, n_noise, n_edges, rounds, eps, min_samples):
         self.labels, self.core, self.parent = labels, core, parent
@@ -1833,33 +1834,44 @@ class Clustering(object):
         two samples share a pid), f1 = their harmonic mean (0.0 when both are 0), ari = the adjusted Rand index in
         its pair-count form 2 (tp tn - fp fn) / ((tp + fn)(fn + tn) + (tp + fp)(fp + tn)), 1.0 when fp = fn = 0.
         All four are float64."""
-        import numpy as np
-        lab = self.labels.cpu().numpy().astype(np.int64)
-        n = lab.size
-        pids = np.asarray(pids).reshape(-1)
-        if pids.size != n:
-            raise ValueError('pair_scores: expected %d pids, got %d' % (n, pids.size))
-        noise = lab < 0
-        lab[noise] = self.n_clusters + np.arange(int(noise.sum()))
+        return _pair_scores(self.labels, self.n_clusters, pids)
 
-        def pairs(counts):
-            counts = counts.astype(np.int64)
-            return int((counts * (counts - 1) // 2).sum())
-        tp = pred = true = 0
-        if n:
-            pi = np.unique(pids, return_inverse=True)[1].reshape(-1).astype(np.int64)
-            tp = pairs(np.unique(lab * (int(pi.max()) + 1) + pi, return_counts=True)[1])
-            pred = pairs(np.unique(lab, return_counts=True)[1])
-            true = pairs(np.unique(pi, return_counts=True)[1])
-        total = n * (n - 1) // 2
-        fp, fn = pred - tp, true - tp
-        tn = total - tp - fp - fn
-        precision = tp / pred if pred else 1.0
-        recall = tp / true if true else 1.0
-        f1 = 2.0 * precision * recall / (precision + recall) if precision + recall > 0.0 else 0.0
-        ari = 1.0 if fp == 0 and fn == 0 else 2.0 * (tp * tn - fp * fn) / ((tp + fn) * (fn + tn) + (tp + fp) * (fp + tn))
-        return {'precision': float(precision), 'recall': float(recall), 'f1': float(f1), 'ari': float(ari), 'tp': tp,
-                'pred_pairs': pred, 'true_pairs': true, 'total_pairs': total, 'n': n}
+    def centroids(self, xf, reduce='unit'):
+        """The clusters' centres ``(centroids [n_clusters, d], counts int64 [n_clusters])`` of the rows of ``xf`` the
+        labels were computed from: ``cluster_centroids(xf, labels, n_clusters, reduce)``, noise ignored."""
+        return cluster_centroids(xf, self.labels, self.n_clusters, reduce)
+
+
+def _pair_scores(labels, n_clusters, pids):
+    """``Clustering.pair_scores`` / ``KMeans.pair_scores``: ``labels`` int64 device [n]; a label < 0 (noise, an
+    unassigned sample) is a cluster of its own, numbered from ``n_clusters``."""
+    import numpy as np
+    lab = labels.cpu().numpy().astype(np.int64)
+    n = lab.size
+    pids = np.asarray(pids).reshape(-1)
+    if pids.size != n:
+        raise ValueError('pair_scores: expected %d pids, got %d' % (n, pids.size))
+    noise = lab < 0
+    lab[noise] = n_clusters + np.arange(int(noise.sum()))
+
+    def pairs(counts):
+        counts = counts.astype(np.int64)
+        return int((counts * (counts - 1) // 2).sum())
+    tp = pred = true = 0
+    if n:
+        pi = np.unique(pids, return_inverse=True)[1].reshape(-1).astype(np.int64)
+        tp = pairs(np.unique(lab * (int(pi.max()) + 1) + pi, return_counts=True)[1])
+        pred = pairs(np.unique(lab, return_counts=True)[1])
+        true = pairs(np.unique(pi, return_counts=True)[1])
+    total = n * (n - 1) // 2
+    fp, fn = pred - tp, true - tp
+    tn = total - tp - fp - fn
+    precision = tp / pred if pred else 1.0
+    recall = tp / true if true else 1.0
+    f1 = 2.0 * precision * recall / (precision + recall) if precision + recall > 0.0 else 0.0
+    ari = 1.0 if fp == 0 and fn == 0 else 2.0 * (tp * tn - fp * fn) / ((tp + fn) * (fn + tn) + (tp + fp) * (fp + tn))
+    return {'precision': float(precision), 'recall': float(recall), 'f1': float(f1), 'ari': float(ari), 'tp': tp,
+            'pred_pairs': pred, 'true_pairs': true, 'total_pairs': total, 'n': n}
 
 
 def _eps_graph_blocks(blocks, n, eps, max_edges=None):
@@ -2013,6 +2025,229 @@ def cluster_matrix(distmat, eps, min_samples=1, max_edges=None):
             return distmat
     row_ptr, col = _eps_graph_blocks(_Whole, n, eps, max_edges)
     return cluster_from_graph(row_ptr, col, n, min_samples, eps=eps, _checked=True)
+
+
+# ----------------------------------------------------------------------------
+# k-means and cluster centroids: search's top-1 assignment + a deterministic segmented row sum (kmeans.hip)
+# ----------------------------------------------------------------------------
+KMEANS_REDUCE = {'sum': 0, 'mean': 1, 'unit': 2}         # GRL_KMEANS_SUM / _MEAN / _UNIT of include/grl_hip.h
+
+
+def _kmeans_int(v, lo, what, name):
+    import numbers
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= 2 ** 31 - 1:
+        raise ValueError('%s: %s must be an integer >= %d (got %r)' % (what, name, lo, v))
+    return int(v)
+
+
+def _kmeans_rows(xf, what):
+    require_device(xf, 'xf')
+    if xf.dim() < 2:
+        raise ValueError('%s: xf must be [n, d] (got %s)' % (what, tuple(xf.shape)))
+    xf = xf.contiguous().view(xf.shape[0], -1)
+    if xf.shape[1] == 0:
+        raise ValueError('%s: xf has no feature columns' % what)
+    return xf
+
+
+def _kmeans_top1(xf, centroids, metric, block_cols, block_bytes):
+    """The k = 1 running lists of ``search(xf, centroids, 1, metric)`` as the kernels keep them: ``run_key`` int64 [n]
+    (the composites) and ``run_val`` float32 [n].  Unsharded: every rank assigns every sample."""
+    blocks = _ColumnBlocks(xf, centroids, metric, block_cols, block_bytes)
+    n = blocks.nq
+    run_key = torch.full((n, 1), -1, dtype=torch.int64, device=xf.device)
+    run_val = torch.full((n, 1), float('inf'), dtype=torch.float32, device=xf.device)
+    if n:
+        for c0, c1 in blocks.spans:
+            d = blocks.block(c0, c1)
+            _call('grl_topk_block', ptr(d), c1 - c0, None, 0, n, c1 - c0, c0, 1, ptr(run_key), ptr(run_val))
+    return run_key.view(n), run_val.view(n)
+
+
+def _kmeans_relabel(run_key, run_val, k, prev_labels=None):
+    """(labels int32 [n], counts int32 [k], changed int32 [1]) of a top-1 assignment (grl_kmeans_relabel)."""
+    n, dev = run_key.shape[0], run_key.device
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    counts = torch.zeros(k, dtype=torch.int32, device=dev)
+    changed = torch.zeros(1, dtype=torch.int32, device=dev)
+    _call('grl_kmeans_relabel', ptr(run_key), ptr(run_val), n, k, ptr(prev_labels), ptr(labels), ptr(counts),
+          ptr(changed))
+    return labels, counts, changed
+
+
+def _kmeans_update(xf, labels32, counts32, k, reduce, prev=None):
+    """Centroids [k, d] of int32 labels (< 0 or >= k: nobody's) whose per-cluster counts are ``counts32``: member
+    lists, the segmented row sum, the finish.  Returns ``(centroids, empty int32 [1])``; nothing is read back."""
+    n, d = xf.shape
+    dev = xf.device
+    mptr = torch.empty(k + 1, dtype=torch.int64, device=dev)
+    _call('grl_rrs_scan', ptr(counts32), k, ptr(mptr))
+    cursor = torch.zeros(k, dtype=torch.int32, device=dev)
+    tmp = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    mem = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    _call('grl_kmeans_members', ptr(labels32), n, k, ptr(mptr), ptr(cursor), ptr(tmp), ptr(mem))
+    lds = (d + 3) // 4 * 4                            # rows grl_row_sqnorm can read; the padding stays zero
+    total = torch.zeros((k, lds), dtype=torch.float32, device=dev)
+    _call('grl_segment_rowsum', ptr(xf), xf.stride(0), n, ptr(mptr), ptr(mem), n, k, d, ptr(total), lds)
+    sq = None
+    if reduce == 'unit':
+        sq = torch.empty(k, dtype=torch.float32, device=dev)
+        _call('grl_row_sqnorm', ptr(total), ptr(sq), k, lds, lds)
+    out = torch.empty((k, d), dtype=torch.float32, device=dev)
+    empty = torch.zeros(1, dtype=torch.int32, device=dev)
+    _call('grl_kmeans_finish', ptr(total), lds, ptr(counts32), ptr(sq), ptr(prev), prev.stride(0) if prev is not None else 0,
+          k, d, KMEANS_REDUCE[reduce], ptr(out), d, ptr(empty))
+    return out, empty
+
+
+def _kmeans_prev(prev, k, d, what):
+    if prev is None:
+        return None
+    require_device(prev, 'prev')
+    if tuple(prev.shape) != (k, d):
+        raise ValueError('%s: prev must be [k, d] = [%d, %d] (got %s)' % (what, k, d, tuple(prev.shape)))
+    return prev.contiguous()
+
+
+def kmeans_assign(xf, centroids, metric='cosine', block_cols=None, block_bytes=None):
+    """Every sample's nearest centroid: ``(labels int64 [n], dist float32 [n])`` on the device, the index and the
+    distance of ``search(xf, centroids, 1, metric)`` bit for bit ('cosine' = cosin_dist, 'euclidean' =
+    pairwise_distance_tensor; ties go to the smaller centroid index), except that a sample whose best distance is NaN
+    gets label -1 (cosin_dist keeps a NaN; pairwise_distance_tensor's clamp at 1e-12 turns one into a number, which is
+    ranked as search ranks it).  The distances are computed in column blocks of the centroids (``block_cols`` / ``block_bytes`` as
+    in ``search``): never an [n, k] matrix beyond a block.  Not sharded: every rank assigns every sample.
+    ValueError: a ``verify_metric``, no centroid."""
+    _cluster_metric(metric, 'kmeans_assign')
+    xf = _kmeans_rows(xf, 'kmeans_assign')
+    require_device(centroids, 'centroids')
+    k = centroids.shape[0]
+    if k < 1:
+        raise ValueError('kmeans_assign: at least one centroid is needed (got %s)' % (tuple(centroids.shape),))
+    run_key, run_val = _kmeans_top1(xf, centroids, metric, block_cols, block_bytes)
+    labels = _kmeans_relabel(run_key, run_val, k)[0]
+    return labels.to(torch.int64), run_val
+
+
+def cluster_centroids(xf, labels, k=None, reduce='mean', prev=None):
+    """Per-cluster sums / means / unit means of the rows of ``xf`` [n, d]: ``(centroids float32 [k, d], counts int64
+    [k])`` on the device.  ``labels``: any integer device tensor [n]; entries < 0 belong to nobody.  ``k`` defaults to
+    max(label) + 1.  Cluster j's members are summed in a fixed order (ascending sample index dealt to four partial
+    sums), without floating-point atomics: the same bits on every run, unlike ``index_add_``.
+    ``reduce``: 'sum', 'mean' (sum / count) or 'unit' (sum scaled to unit length).  A cluster without members -- or,
+    for 'unit', with a sum whose norm is zero or not finite -- takes its row of ``prev`` [k, d] when given, else zeros.
+    ValueError: a label >= k (one device-side check), labels that are not n integers, an unknown ``reduce``."""
+    xf = _kmeans_rows(xf, 'cluster_centroids')
+    n, d = xf.shape
+    if reduce not in KMEANS_REDUCE:
+        raise ValueError("cluster_centroids: reduce must be 'sum', 'mean' or 'unit' (got %r)" % (reduce,))
+    if not (torch.is_tensor(labels) and labels.is_cuda and labels.dim() == 1 and labels.numel() == n
+            and not labels.dtype.is_floating_point and not labels.dtype.is_complex and labels.dtype != torch.bool):
+        raise ValueError('cluster_centroids: labels must be an integer device tensor with one entry per row of xf '
+                         '(%d)' % n)
+    top = int(labels.max()) if n else -1              # the one read-back: k's default and the bound check
+    k = _kmeans_int(max(top + 1, 0) if k is None else k, 0, 'cluster_centroids', 'k')
+    if top >= k:
+        raise ValueError('cluster_centroids: label %d is outside 0..k-1 = 0..%d' % (top, k - 1))
+    prev = _kmeans_prev(prev, k, d, 'cluster_centroids')
+    if k == 0:
+        return (torch.empty((0, d), dtype=torch.float32, device=xf.device),
+                torch.empty(0, dtype=torch.int64, device=xf.device))
+    labels32 = labels.to(torch.int64).clamp(min=-1).to(torch.int32)
+    counts = torch.zeros(k, dtype=torch.int32, device=xf.device)
+    _call('grl_kmeans_label_counts', ptr(labels32), n, k, ptr(counts))
+    out, _ = _kmeans_update(xf, labels32, counts, k, reduce, prev)
+    return out, counts.to(torch.int64)
+
+
+class KMeans(object):
+    """The result of ``kmeans``:
+
+      labels       int64 device [n]: the cluster of every sample at the last assignment; -1 = unassigned (a NaN distance)
+      centroids    float32 device [k, d]: the update of those labels (``cluster_centroids(xf, labels, k, ..)``)
+      counts       int64 device [k]: members per cluster
+      n_iter, converged, n_changed (labels changed per iteration; the first entry is n), n_empty (clusters without a
+      usable sum at the last update: they kept their previous row), n_unassigned, k, metric
+      inertia      float64: the sum over assigned samples of the distance to their centroid at the last assignment
+                   ('cosine': the negated dot products; 'euclidean': the squared distances)
+      pair_scores(pids)   pairwise precision / recall / F1 / ARI of the labels against true identities"""
+
+    def __init__(self, labels, centroids, counts, n_iter, converged, n_changed, n_empty, n_unassigned, k, metric,
+                 inertia):
+        self.labels, self.centroids, self.counts = labels, centroids, counts
+        self.n_iter, self.converged, self.n_changed = n_iter, converged, n_changed
+        self.n_empty, self.n_unassigned, self.k, self.metric, self.inertia = n_empty, n_unassigned, k, metric, inertia
+
+    def pair_scores(self, pids):
+        """``Clustering.pair_scores``: an unassigned sample is a cluster of its own."""
+        return _pair_scores(self.labels, self.k, pids)
+
+
+def _kmeans_init(xf, k, init, seed):
+    """C0 [k, d] as a fresh device tensor: a [k, d] tensor as it is, k distinct sample indices, or 'random'."""
+    import numbers
+    import numpy as np
+    n, d = xf.shape
+    if torch.is_tensor(init) and init.dim() == 2:
+        require_device(init, 'init')
+        if tuple(init.shape) != (k, d):
+            raise ValueError('kmeans: init centroids must be [k, d] = [%d, %d] (got %s)' % (k, d, tuple(init.shape)))
+        return init.contiguous().clone()
+    if isinstance(init, str):
+        if init != 'random':
+            raise ValueError("kmeans: init must be 'random', k sample indices or a [k, d] device tensor (got %r)" % (init,))
+        if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or seed < 0:
+            raise ValueError('kmeans: seed must be an integer >= 0 (got %r)' % (seed,))
+        idx = np.random.Generator(np.random.PCG64(int(seed))).choice(n, k, replace=False)
+    else:
+        try:
+            idx = np.asarray(init.cpu() if torch.is_tensor(init) else list(init))
+        except TypeError:
+            raise ValueError("kmeans: init must be 'random', k sample indices or a [k, d] device tensor (got %r)" % (init,))
+        if idx.ndim != 1 or idx.dtype.kind not in 'iu' or idx.size != k:
+            raise ValueError('kmeans: init must hold k = %d integer sample indices' % k)
+        if idx.size and (idx.min() < 0 or idx.max() >= n):
+            raise ValueError('kmeans: init indices must be in 0..n-1 = 0..%d' % (n - 1))
+        if np.unique(idx).size != k:
+            raise ValueError('kmeans: init indices must be distinct')
+    return xf[torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(xf.device)].contiguous()
+
+
+def kmeans(xf, k, metric='cosine', init='random', seed=0, max_iter=50, block_cols=None, block_bytes=None):
+    """Lloyd's k-means of the rows of ``xf`` [n, d] on the device as a ``KMeans``: 'cosine' is spherical k-means
+    (distance = cosin_dist = -dot, centroids = the unit-length sum of the members; the rows and the initial
+    centroids should be unit already -- nothing is normalised behind the caller's back), 'euclidean' the classic
+    form (pairwise_distance_tensor, centroids = the mean).  Iteration t assigns every sample to its nearest centroid
+    (``kmeans_assign``: search's column blocks and tie rule, never an [n, k] matrix beyond a block) and recomputes
+    the centroids by the deterministic segmented row sum (``cluster_centroids`` with ``prev`` = the old centroids, so
+    an empty cluster keeps its row).  It stops after the first iteration whose labels equal the previous one's
+    (``converged``) or after ``max_iter`` iterations; the host reads one int32, the number of changed labels, per
+    iteration.  ``init``: a [k, d] device tensor, k distinct sample indices, or 'random' = numpy's
+    Generator(PCG64(seed)).choice(n, k, replace=False).  The result is the same bit for bit on every run and for
+    every block width.  Not sharded: under torch.distributed every rank computes the full, identical result.
+    ValueError: a ``verify_metric``, k outside 1..n, max_iter < 1, a bad ``init``."""
+    import numpy as np
+    _cluster_metric(metric, 'kmeans')
+    xf = _kmeans_rows(xf, 'kmeans')
+    n, d = xf.shape
+    k = _kmeans_int(k, 1, 'kmeans', 'k')
+    if k > n:
+        raise ValueError('kmeans: k must be in 1..n = 1..%d (got %d)' % (n, k))
+    max_iter = _kmeans_int(max_iter, 1, 'kmeans', 'max_iter')
+    cent = _kmeans_init(xf, k, init, seed)
+    reduce = 'unit' if metric == 'cosine' else 'mean'
+    labels, n_changed, converged = None, [], False
+    while len(n_changed) < max_iter and not converged:
+        run_key, run_val = _kmeans_top1(xf, cent, metric, block_cols, block_bytes)
+        labels, counts, changed = _kmeans_relabel(run_key, run_val, k, labels)
+        cent, empty = _kmeans_update(xf, labels, counts, k, reduce, cent)
+        n_changed.append(int(changed))                # the iteration's one read-back
+        converged = n_changed[-1] == 0
+    best = run_val.cpu().numpy().astype(np.float64)
+    assigned = labels.cpu().numpy() >= 0
+    inertia = float((best[assigned] if metric == 'cosine' else best[assigned] ** 2).sum())
+    counts = counts.to(torch.int64)
+    return KMeans(labels.to(torch.int64), cent, counts, len(n_changed), converged, n_changed, int(empty),
+                  n - int(assigned.sum()), k, metric, inertia)
 
 
 # ----------------------------------------------------------------------------

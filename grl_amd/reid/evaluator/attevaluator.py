@@ -86,6 +86,32 @@ def _cluster_report(knob, qf, gf, ids, path, roc=None):
     return lines
 
 
+def _kmeans_report(knob, gf, ids, path):
+    """GRL_EVAL_KMEANS: spherical k-means of the query-prepended gallery ``gf`` (engine.kmeans, 'cosine', random
+    initial rows) -- the two lines ``_report`` prints last, and ``path + 'kmeans.json'`` (rank 0 alone writes; strict
+    JSON, no centroids).  ``knob`` = (k or 'ids', max_iter, seed); 'ids' is the number of distinct pids in ``gf``."""
+    import json
+    k, max_iter, seed = knob
+    if k == 'ids':
+        k = int(np.unique(np.asarray(ids[1])).size)
+    km = engine.kmeans(gf, k, 'cosine', 'random', seed, max_iter)
+    n = int(gf.size(0))
+    scores = km.pair_scores(ids[1])
+    lines = ['K-means: {} clusters of {} ({} iterations, {}, {} empty), inertia = {:.6g}'.format(
+                 km.k, n, km.n_iter, 'converged' if km.converged else 'not converged', km.n_empty, km.inertia),
+             'Pairwise precision: {:.2%}  recall: {:.2%}  F1: {:.2%}  ARI: {:.4f}'.format(
+                 scores['precision'], scores['recall'], scores['f1'], scores['ari'])]
+    if grl_dist._rank_world(None, None)[0] == 0:
+        with open((path or '') + 'kmeans.json', 'w') as fh:
+            json.dump({'k': km.k, 'max_iter': max_iter, 'seed': seed, 'init': 'random', 'metric': 'cosine', 'n': n,
+                       'n_iter': km.n_iter, 'converged': km.converged, 'n_changed': km.n_changed,
+                       'n_empty': km.n_empty, 'n_unassigned': km.n_unassigned,
+                       'inertia': km.inertia if math.isfinite(km.inertia) else None,
+                       'counts': km.counts.cpu().tolist(), 'pair_scores': scores, 'labels': km.labels.cpu().tolist()},
+                      fh, allow_nan=False)
+    return lines
+
+
 def cosin_dist(qf, gf):
     return engine.cosin_dist(qf, gf)
 
@@ -165,6 +191,28 @@ def parse_cluster_knob(name, value):
     if eps != eps or not 1 <= min_samples <= 2 ** 31 - 1:
         raise ValueError('%s: eps must not be NaN and min_samples must be >= 1 (got %r)' % (name, value))
     return eps, min_samples
+
+
+def parse_kmeans_knob(name, value):
+    """``GRL_EVAL_KMEANS``: unset or empty -> None (off); "k", "k,max_iter" or "k,max_iter,seed" -> (k, max_iter,
+    seed) with k an integer >= 1 or the word "ids" (the number of distinct pids in the query-prepended gallery), an
+    integer max_iter >= 1 (default 50) and an integer seed >= 0 (default 0; engine.kmeans).  Anything else is a
+    ValueError that names the variable."""
+    if value is None or not value.strip():
+        return None
+    parts = [p.strip() for p in value.split(',')]
+    try:
+        if len(parts) > 3:
+            raise ValueError
+        k = 'ids' if parts[0] == 'ids' else int(parts[0])
+        max_iter = int(parts[1]) if len(parts) >= 2 else 50
+        seed = int(parts[2]) if len(parts) == 3 else 0
+    except ValueError:
+        raise ValueError('%s must be "k", "k,max_iter" or "k,max_iter,seed" with k an integer or "ids" and integer '
+                         'max_iter and seed (got %r)' % (name, value))
+    if (k != 'ids' and not 1 <= k <= 2 ** 31 - 1) or not 1 <= max_iter <= 2 ** 31 - 1 or seed < 0:
+        raise ValueError('%s: k and max_iter must be >= 1 and seed >= 0 (got %r)' % (name, value))
+    return k, max_iter, seed
 
 
 class ATTEvaluator(object):
@@ -295,6 +343,13 @@ class ATTEvaluator(object):
                              'distance is a signed logit of modified query rows against gallery rows, not a distance '
                              'between two samples of one set (unset one of them)'
                              % os.environ['GRL_EVAL_METRIC'].strip())
+        # k-means with a known or budgeted number of identities, off by default: spherical k-means of the query-prepended
+        # gallery (engine.kmeans), printed last and stored in path + 'kmeans.json'
+        kmeans_knob = parse_kmeans_knob('GRL_EVAL_KMEANS', os.environ.get('GRL_EVAL_KMEANS'))
+        if kmeans_knob is not None and knob is not None:
+            raise ValueError('GRL_EVAL_KMEANS cannot be combined with GRL_EVAL_METRIC=%s: k-means runs by cosine on '
+                             'the routes that rank by cosine (unset one of them)'
+                             % os.environ['GRL_EVAL_METRIC'].strip())
         qf, q_pids, q_camids = self.extract_feature(query_loader)
         print('Done, obtained {}-by-{} matrix'.format(qf.size(0), qf.size(1)))
         gf, g_pids, g_camids = self.extract_feature(gallery_loader)
@@ -322,10 +377,13 @@ class ATTEvaluator(object):
         roc_lines = ()
 
         def extra(lines, cosine_roc=None):
-            """the route's ROC lines, then GRL_EVAL_CLUSTER's (always by cosine, whatever the route ranks by)"""
-            if cluster_knob is None:
-                return lines
-            return tuple(lines) + tuple(_cluster_report(cluster_knob, qf, gf, ids, path, cosine_roc))
+            """the route's ROC lines, then GRL_EVAL_CLUSTER's and GRL_EVAL_KMEANS's (always by cosine, whatever the
+            route ranks by)"""
+            if cluster_knob is not None:
+                lines = tuple(lines) + tuple(_cluster_report(cluster_knob, qf, gf, ids, path, cosine_roc))
+            if kmeans_knob is not None:
+                lines = tuple(lines) + tuple(_kmeans_report(kmeans_knob, gf, ids, path))
+            return lines
         if visual:
             self._visualize(query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, rerank)
         if rerank_stream:

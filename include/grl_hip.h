@@ -41,7 +41,8 @@ const char* grl_last_error(void);
  * struct layout or argument list, and a library without them fails to bind in _lib.load.  So were the streaming
  * re-ranking entry points grl_rrs_*, the CSR / CSC assembly of its sharded form (grl_rrs_expand_rows, grl_rrs_scan,
  * grl_rrs_place, grl_rrs_transpose) among them, grl_topk_block_filtered, grl_expand_rows, the grl_verify_* entry points,
- * grl_pair_hist_block and the clustering entry points grl_cluster_*. */
+ * grl_pair_hist_block, the clustering entry points grl_cluster_* and the k-means entry points grl_kmeans_* /
+ * grl_segment_rowsum. */
 #define GRL_ABI_VERSION 10
 int grl_abi_version(void);
 /* `waiter` (a hipStream_t) waits for everything enqueued on `signaler` so far: hipEventRecord + hipStreamWaitEvent on a
@@ -661,6 +662,38 @@ int grl_cluster_roots(const uint8_t* core, const int32_t* parent, int n, int32_t
 /* labels[i] = root_id[parent[i]] (core), root_id[border[i]] (border point), -1 (noise): ids ascend with the root */
 int grl_cluster_labels(const uint8_t* core, const int32_t* parent, const int32_t* border, const int64_t* root_id, int n,
                        int64_t* labels, void* stream);
+
+/* ---- k-means and cluster centroids (kmeans.hip, engine.kmeans / kmeans_assign / cluster_centroids) ----
+ * The assignment is grl_topk_block at k = 1 over column blocks of the sample x centroid distance matrix; these entry
+ * points are the update.  Integer atomics only: every output is the same bit for bit on every run.
+ * labels[i] = the index in run_key[i] (the k = 1 composite of sample i), or -1 when run_val[i] is NaN, the slot is
+ * empty or the index is outside 0..k-1; counts[label] += 1 (int32 [k], zeroed by the caller); *changed += the number
+ * of labels that differ from prev_labels (NULL: every label counts). */
+int grl_kmeans_relabel(const uint64_t* run_key, const float* run_val, int n, int k, const int32_t* prev_labels,
+                       int32_t* labels, int32_t* counts, int32_t* changed, void* stream);
+/* counts[l] += 1 for every label l in 0..k-1 (others belong to nobody); counts zeroed by the caller */
+int grl_kmeans_label_counts(const int32_t* labels, int n, int k, int32_t* counts, void* stream);
+/* The clusters' member lists as a CSR: mptr [k+1] = grl_rrs_scan of the counts, mem [mptr[k]] (allocated for n) =
+ * every cluster's samples in ASCENDING order.  cursor [k] int32 zeroed by the caller, tmp int32 [n] scratch.  A slot
+ * is taken by an integer atomic; the final place of a sample is the number of its cluster's samples below it, so mem
+ * does not depend on the order of arrival. */
+int grl_kmeans_members(const int32_t* labels, int n, int k, const int64_t* mptr, int32_t* cursor, int32_t* tmp,
+                       int32_t* mem, void* stream);
+/* sum[j][c] (row stride lds) = the sum of x[m][c] (x [n][ld]) over cluster j's members m = mem[mptr[j] .. mptr[j+1]),
+ * in this fixed order: four partial sums p_w, w = 0..3, each the sequential fp32 sum from +0.0f of the members
+ * m_w, m_{w+4}, m_{w+8}, .. (positions in the list), then (p0 + p1) + (p2 + p3).  Adds only, no atomics.  One
+ * workgroup per (cluster, 256 columns); 16-byte loads when x is 16-byte aligned and ld and d are multiples of 4,
+ * single floats otherwise.  Entries of mem outside 0..n-1 and list positions at or beyond nmem are skipped. */
+int grl_segment_rowsum(const float* x, int64_t ld, int n, const int64_t* mptr, const int32_t* mem, int64_t nmem, int k,
+                       int d, float* sum, int64_t lds, void* stream);
+#define GRL_KMEANS_SUM  0
+#define GRL_KMEANS_MEAN 1
+#define GRL_KMEANS_UNIT 2
+/* out[j] = sum[j] (SUM), sum[j] / float(counts[j]) (MEAN), sum[j] * (1 / sqrt(sq[j])) (UNIT; sq = grl_row_sqnorm of
+ * sum).  A cluster with counts[j] == 0, or (UNIT) with sq[j] zero or not finite, is empty: out[j] = prev[j] (row
+ * stride ldp) or zeros when prev is NULL, and *empty += 1 (int32, zeroed by the caller).  Plain stores. */
+int grl_kmeans_finish(const float* sum, int64_t lds, const int32_t* counts, const float* sq, const float* prev,
+                      int64_t ldp, int k, int d, int reduce, float* out, int64_t ldo, int32_t* empty, void* stream);
 
 /* ---- query expansion / database-side augmentation (expand.hip, engine.expand_from_lists / expand_features) ----
  * out[i] = (x[i] + sum_p w_p * bank[j_p]) / (1 + sum_p w_p): a gather and a weighted sum over feature rows, without
