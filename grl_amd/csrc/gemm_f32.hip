@@ -48,6 +48,10 @@ constexpr int SEG_STAGES = 16;     // fp32 path: accumulator segment = 16 stages
 #define GRL_GEMM_PIPE 1   // hand-scheduled stage loop of the dense fp32 LDS-DMA kernels (0: the compiler-scheduled loop)
 #endif
 
+#ifndef GRL_GEMM_EV_OCC3
+#define GRL_GEMM_EV_OCC3 1 // 128 x 64 eval variants: bounded to three waves per SIMD (0: the shared (256, 2); A/B builds)
+#endif
+
 typedef __attribute__((address_space(3))) char* lds_cptr_t;
 // LDS-DMA piece the compiler does not see (wave-uniform 64-bit base in SGPRs + per-lane 32-bit offset).  While a
 // compiler-VISIBLE global_load_lds is outstanding hipcc waits vmcnt(0) in front of every LDS read that follows (it cannot
@@ -91,9 +95,21 @@ struct RowInfo {          // per staged A row: where it comes from
 // layers run the instantiation without the second accumulator set).
 // SPLITK (skinny K-blocked GEMMs, GrlGemm.splitk_ws): blockIdx.y is a 512-k segment of the K-blocked chain; the
 // workgroup runs that segment as a plain chain from zero and stores the raw accumulator to ws[segment][M][N].
-template <int BM, int BN, bool CONV, int MATH, bool SEG, bool DMA = false, bool SPLITK = false>
-__global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GrlGemm p_in, const int tiles_n,
-                                                           const int num_tiles, const int vec_epi) {
+// EV (the eval variants, hand-scheduled exact-fp32 LDS-DMA kernels only; launch_math picks them): the descriptor fields an
+// inference launch never sets are compile-time constants, so the statistics slabs and their smaller-tile orders, the fused
+// BatchNorm-backward reduce, rowscale, kblock and the NEGDOT / EUCLID epilogues are dead code and hold no registers.
+//   EV_AFFINE  scale / shift (may be null), res, relu, gbias + rows_per_group; the vectorised and the scalar store
+//   EV_SQDIFF  the TRL step's squared-difference epilogue alone (128 x 128, vectorised)
+// Same K loop, same epilogue expressions in the same order as EV_NONE: bit-identical outputs (tested).  The 128 x 64 eval
+// variants fit the 168 VGPRs of three waves per SIMD and are bounded to it (3 x 48 KB of LDS: three workgroups per CU).
+constexpr int EV_NONE = 0, EV_AFFINE = 1, EV_SQDIFF = 2;
+template <int BM, int BN, bool CONV, int MATH, bool SEG, bool DMA = false, bool SPLITK = false, int EV = EV_NONE>
+__global__ __launch_bounds__(256, (GRL_GEMM_EV_OCC3 && EV != EV_NONE && BN == 64) ? 3 : 2) void gemm_f32_kernel(const GrlGemm p_in, const int tiles_n,
+                                                                                               const int num_tiles, const int vec_epi_in) {
+    static_assert(EV == EV_NONE || (MATH == 0 && BM == 128 && DMA && !SEG && !SPLITK && GRL_GEMM_PIPE), "eval variants: the hand-scheduled fp32 kernels");
+    static_assert(EV != EV_SQDIFF || (BN == 128 && !CONV), "SQDIFF: dense, 128 x 128");
+    // (EV: no statistics order in bits 1..2; SQDIFF is launched with the vectorised epilogue only)
+    const int vec_epi = EV == EV_NONE ? vec_epi_in : EV == EV_SQDIFF ? (vec_epi_in & 8) | 1 : vec_epi_in & 9;
     GrlGemm p_seg;
     if constexpr (SPLITK) {
         p_seg = p_in;
@@ -107,7 +123,20 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GrlGemm p_in, co
         p_seg.stats = nullptr;
         p_seg.relu = 0;
     }
-    const GrlGemm& p = SPLITK ? p_seg : p_in;
+    GrlGemm p_ev;
+    if constexpr (EV != EV_NONE) {
+        p_ev = p_in;
+        p_ev.epilogue = EV == EV_SQDIFF ? GRL_EPI_SQDIFF : GRL_EPI_AFFINE;
+        p_ev.stats = nullptr;
+        p_ev.rowscale = p_ev.rnorm = p_ev.cnorm = nullptr;
+        p_ev.bn_z = p_ev.bn_mean = p_ev.bn_invstd = p_ev.bn_mscale = p_ev.bn_mbeta = nullptr;
+        p_ev.bn_bits = nullptr;
+        p_ev.splitk_ws = nullptr;
+        p_ev.kblock = 0;
+        p_ev.out_f32 = 0;
+        if constexpr (EV == EV_SQDIFF) { p_ev.gbias = nullptr; p_ev.relu = 0; }
+    }
+    const GrlGemm& p = SPLITK ? p_seg : EV != EV_NONE ? p_ev : p_in;
     constexpr int WTM = BM / 2, WTN = BN / 2;     // wave tile
     constexpr int MT = WTM / 32, NT = WTN / 32;   // MFMA tiles per wave
     constexpr int ESZ = MATH == 2 ? 2 : 4;        // bytes per operand element in HBM
@@ -960,7 +989,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GrlGemm p_in, co
         // the epilogue of a short-K layer is a read-modify-write of the output at HBM speed, and a residual load
         // issued per row inside the store loop serialises its latency with the stores
         constexpr int EPI_ROWS = WTM / (64 / (WTN / 4));
-        constexpr bool RES_PREFETCH = MATH != 2 && !SEG && !(BM == 128 && BN == 128);     // (16 rows x 4 VGPRs would spill there)
+        // (128 x 128: 16 rows x 4 VGPRs would spill in the generic kernel.  The eval variant has the registers, but its residual
+        //  layers are interior tiles that leave through the fast path above, which requests its rows a chunk ahead: left off)
+        constexpr bool RES_PREFETCH = MATH != 2 && !SEG && !(BM == 128 && BN == 128);
         constexpr int EPI_UNROLL = RES_PREFETCH ? EPI_ROWS : 4;
         f32x4 rpre[RES_PREFETCH ? EPI_ROWS : 1];
         // ... and the rows of z (+ ReLU mask words) of a fused BatchNorm-backward reduce (GrlGemm.bn_z): the data-gradient
@@ -1559,6 +1590,25 @@ void launch_kernel(const GrlGemm& d, hipStream_t s, size_t lds, int tiles_n, int
                        vec_epi);
 }
 
+// Which kernel a launch runs.  The eval variants take a descriptor exactly when it uses nothing they leave
+// out: exact fp32 on a 128-row tile with LDS-DMA staging, the AFFINE epilogue (scale, shift, res, relu, gbias) or -- on
+// the vectorised 128 x 128 tile -- SQDIFF; no stats, bn_z, rowscale or kblock.  GRL_GEMM_EVAL_VARIANT=0 (read per call:
+// the tests and A/B runs toggle it) sends everything through the generic kernel.
+int eval_variant(const GrlGemm& d, int bm, int bn, int vec_epi) {
+    if (d.math != GRL_MATH_F32 || bm != 128 || d.stats || d.bn_z || d.rowscale || d.kblock) return EV_NONE;
+    if (d.epilogue == GRL_EPI_SQDIFF ? !(bn == 128 && (vec_epi & 1)) : d.epilogue != GRL_EPI_AFFINE) return EV_NONE;
+    const char* const e = getenv("GRL_GEMM_EVAL_VARIANT");
+    if (e && atoi(e) == 0) return EV_NONE;
+    return d.epilogue == GRL_EPI_SQDIFF ? EV_SQDIFF : EV_AFFINE;
+}
+
+// GRL_DEBUG_SYNC (debugging and the routing tests; read per call): name the instantiation of every launch on stderr
+void debug_name(int bm, int bn, const GrlGemm& d, int math, bool seg, bool dma, int ev) {
+    if (!getenv("GRL_DEBUG_SYNC")) return;
+    fprintf(stderr, "[grl] gemm_f32_kernel<%d,%d,conv=%d,math=%d,seg=%d,dma=%d> variant=%s\n", bm, bn, d.conv ? 1 : 0, math, seg ? 1 : 0,
+            dma ? 1 : 0, ev == EV_AFFINE ? "eval" : ev == EV_SQDIFF ? "eval-sqdiff" : "generic");
+}
+
 template <int BM, int BN, int MATH>
 int launch_math(const GrlGemm& d, hipStream_t s, int smode) {
     const int tiles_m = (d.M + BM - 1) / BM, tiles_n = (d.N + BN - 1) / BN;
@@ -1577,9 +1627,19 @@ int launch_math(const GrlGemm& d, hipStream_t s, int smode) {
     constexpr bool CAN_SEG = MATH == 0;
     const bool seg = CAN_SEG && d.kblock && d.K > SEG_STAGES * BK;
     static const bool dma_conv_on = [] { const char* e = getenv("GRL_GEMM_DMA_CONV"); return !e || atoi(e) != 0; }();
+    constexpr bool CAN_EV = GRL_GEMM_PIPE && MATH == 0 && BM == 128;
+    const int ev = CAN_EV ? eval_variant(d, BM, BN, vec_epi) : EV_NONE;
     if (d.conv) {
         constexpr bool CAN_DMA_CONV = (MATH == 0 || MATH == 2) && BM == 128;
-        if (CAN_DMA_CONV && dma_conv_on && d.ldw < (1 << 22) && d.kh * d.kw <= 32) {     // (one validity bit per tap)
+        const bool dma = CAN_DMA_CONV && dma_conv_on && d.ldw < (1 << 22) && d.kh * d.kw <= 32;     // (one validity bit per tap)
+        debug_name(BM, BN, d, MATH, seg, dma, dma ? ev : EV_NONE);
+        if constexpr (CAN_EV) {
+            if (dma && ev == EV_AFFINE) {
+                launch_kernel<gemm_f32_kernel<BM, BN, true, MATH, false, true, false, EV_AFFINE>>(d, s, lds, tiles_n, num_tiles, vec_epi);
+                return grl_check_launch("grl_conv_gemm_f32");
+            }
+        }
+        if (dma) {
             if (seg) launch_kernel<gemm_f32_kernel<BM, BN, true, MATH, CAN_SEG, CAN_DMA_CONV>>(d, s, lds, tiles_n, num_tiles, vec_epi);
             else launch_kernel<gemm_f32_kernel<BM, BN, true, MATH, false, CAN_DMA_CONV>>(d, s, lds, tiles_n, num_tiles, vec_epi);
         } else if (seg) launch_kernel<gemm_f32_kernel<BM, BN, true, MATH, CAN_SEG>>(d, s, lds, tiles_n, num_tiles, vec_epi);
@@ -1590,7 +1650,21 @@ int launch_math(const GrlGemm& d, hipStream_t s, int smode) {
         constexpr bool CAN_DMA = (MATH == 0 || MATH == 2) && BM == 128;     // 128-byte operand rows (fp32 x 32 / bf16 x 64)
         // (the hand-scheduled loop addresses a tile's rows with 32-bit byte offsets from its first row: 127 rows x ld x 4 B)
         static const int dma_mink = [] { const char* e = getenv("GRL_GEMM_DMA_MINK"); return e ? atoi(e) : 256; }();
-        if (CAN_DMA && dma_on && d.K >= dma_mink && d.lda < (1 << 22) && d.ldw < (1 << 22)) {
+        const bool dma = CAN_DMA && dma_on && d.K >= dma_mink && d.lda < (1 << 22) && d.ldw < (1 << 22);
+        debug_name(BM, BN, d, MATH, seg, dma, dma ? ev : EV_NONE);
+        if constexpr (CAN_EV) {
+            if (dma && ev == EV_AFFINE) {
+                launch_kernel<gemm_f32_kernel<BM, BN, false, MATH, false, true, false, EV_AFFINE>>(d, s, lds, tiles_n, num_tiles, vec_epi);
+                return grl_check_launch("grl_conv_gemm_f32");
+            }
+            if constexpr (BN == 128) {
+                if (dma && ev == EV_SQDIFF) {
+                    launch_kernel<gemm_f32_kernel<BM, BN, false, MATH, false, true, false, EV_SQDIFF>>(d, s, lds, tiles_n, num_tiles, vec_epi);
+                    return grl_check_launch("grl_conv_gemm_f32");
+                }
+            }
+        }
+        if (dma) {
             if (seg) launch_kernel<gemm_f32_kernel<BM, BN, false, MATH, CAN_SEG, CAN_DMA>>(d, s, lds, tiles_n, num_tiles, vec_epi);
             else launch_kernel<gemm_f32_kernel<BM, BN, false, MATH, false, CAN_DMA>>(d, s, lds, tiles_n, num_tiles, vec_epi);
         } else if (seg) launch_kernel<gemm_f32_kernel<BM, BN, false, MATH, CAN_SEG>>(d, s, lds, tiles_n, num_tiles, vec_epi);
