@@ -172,6 +172,7 @@ _SIGNATURES = {
     'grl_cluster_border': ([_fp, _fp, _fp, _fp, C.c_int, _fp, _fp], C.c_int),
     'grl_cluster_roots': ([_fp, _fp, C.c_int, _fp, _fp], C.c_int),
     'grl_cluster_labels': ([_fp, _fp, _fp, _fp, C.c_int, _fp, _fp], C.c_int),
+    'grl_jaccard_edges': ([_fp] * 6 + [C.c_int, C.c_float, C.c_int] + [_fp] * 5, C.c_int),
     'grl_kmeans_relabel': ([_fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp], C.c_int),
     'grl_kmeans_label_counts': ([_fp, C.c_int, C.c_int, _fp, _fp], C.c_int),
     'grl_kmeans_members': ([_fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp], C.c_int),

@@ -2473,3 +2473,166 @@ def rerank_pair_roc(qf, gf, q_pids, g_pids, q_camids, g_camids, k1=20, k2=6, lam
     rr = _Rerank(qf, gf, k1, k2, lambda_value, block_cols, block_bytes)
     return _roc_blocks(_RerankBlocks(qf, gf, rr, block_cols, block_bytes), rr.nq, rr.ng, q_pids, g_pids, q_camids,
                        g_camids, bits, rr.sharded)
+
+
+# ----------------------------------------------------------------------------
+# DBSCAN on the k-reciprocal Jaccard distance of one sample set (jaccard.hip)
+# ----------------------------------------------------------------------------
+def _jaccard_args(xf, eps, k1, k2, what):
+    """The checks of ``jaccard_graph`` / ``cluster_jaccard``, all before any device work: (n, eps as the float32 the
+    kernel compares with, k1, k2)."""
+    import math
+    import numbers
+    import numpy as np
+    if not (torch.is_tensor(xf) and xf.is_cuda and xf.dtype == torch.float32 and xf.dim() == 2):
+        raise ValueError('%s: xf must be a 2-d float32 tensor [n, d] on a HIP device (got %s)'
+                         % (what, '%s %s on %s' % (tuple(xf.shape), xf.dtype, xf.device) if torch.is_tensor(xf)
+                            else type(xf).__name__))
+    n = int(xf.shape[0])
+    if n < 2 or xf.shape[1] < 1:
+        raise ValueError('%s: needs n >= 2 samples of d >= 1 features (got %s)' % (what, tuple(xf.shape)))
+    for v, name in ((k1, 'k1'), (k2, 'k2')):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError('%s: %s must be an integer (got %r)' % (what, name, v))
+    if not (1 <= k1 <= RERANK_K1_MAX and k1 < n):
+        raise ValueError('%s: k1 must be in 1..%d and below n = %d (got %r)' % (what, RERANK_K1_MAX, n, k1))
+    if not (1 <= k2 <= RERANK_K2_MAX and k2 <= n):
+        raise ValueError('%s: k2 must be in 1..%d and at most n = %d (got %r)' % (what, RERANK_K2_MAX, n, k2))
+    if isinstance(eps, bool) or not isinstance(eps, numbers.Real):
+        raise ValueError('%s: eps must be a number (got %r)' % (what, eps))
+    with np.errstate(over='ignore'):
+        e32 = float(np.float32(eps))
+    if not math.isfinite(e32) or e32 >= 1.0:
+        raise ValueError('%s: eps must be finite and < 1 as a float32 (got %r): at a Jaccard distance of 1 two samples '
+                         'share no neighbour, so eps >= 1 joins every pair' % (what, eps))
+    return n, e32, int(k1), int(k2)
+
+
+def _pad_features(xf):
+    """``xf`` [n, d] as contiguous rows whose width is a multiple of 32, what the distance GEMM takes: zero columns are
+    appended when d is not (they add +0 to every dot product and norm)."""
+    n, d = xf.shape
+    if d % 32 == 0:
+        return xf.contiguous()
+    out = torch.zeros((n, -(-d // 32) * 32), dtype=xf.dtype, device=xf.device)
+    out[:, :d] = xf
+    return out
+
+
+class _JaccardSet(object):
+    """The sparse k-reciprocal state of ONE sample set ``xf`` [n, d] (all-vs-all, nothing stacked, no sample counted
+    twice): colmax [n], the first K = max(k1 + 1, k2) rank entries of every D row, the expansion lists with their
+    weights ([n][256]), V2 as CSR and its transpose over all rows as CSC.  S = pairwise_distance_tensor(xf, xf) (of the
+    rows zero-padded to a multiple of 32 features, ``_pad_features``) comes in column blocks of the 'euclidean' ``_ColumnBlocks`` (twice: pass A1 and pass A2), D[i][j] = S[j][i]^2 / colmax[i];
+    the kernels are ``_Rerank``'s, the block [n][w] handed over as one upper row and n - 1 lower rows.  Nothing of size
+    n x n is allocated; the block width follows ``_SampleBlocks``' rule.  Not sharded: under torch.distributed every
+    rank builds the full, identical state and no collective is issued."""
+
+    def __init__(self, xf, k1, k2, block_cols=None, block_bytes=None):
+        n = xf.shape[0]
+        self.n, self.k1, self.k2, self.K = n, k1, k2, max(k1 + 1, k2)
+        if block_cols is None:
+            budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
+            block_cols = max(32, budget // (12 * n) // 32 * 32)
+            block_cols = min(block_cols, max(32, -(-n // 64) * 32))               # never the whole n x n matrix
+        self.width = w = max(1, min(int(block_cols), n))
+        spans = [(i, min(i + w, n)) for i in range(0, n, w)]
+        xf = _pad_features(xf)
+        cb = _ColumnBlocks(xf, xf, 'euclidean', block_cols=w)
+        dev, K = cb.qf.device, self.K
+
+        def segment(i0, i1):                      # S[:, i0:i1] as (up, ldu, lo, lo_rs, lo_cs, nq = 1, ng = n - 1, w)
+            s = cb.block(i0, i1)
+            return ptr(s), i1 - i0, ptr(s[1:]), i1 - i0, 1, 1, n - 1, i1 - i0
+        # pass A1: colmax and the first K entries of every D row (grl_topk_block's order)
+        self.colmax = torch.empty(n, dtype=torch.float32, device=dev)
+        run_key = torch.full((n, K), -1, dtype=torch.int64, device=dev)
+        run_val = torch.full((n, K), float('inf'), dtype=torch.float32, device=dev)
+        drows = _new((w * n,), cb.qf)
+        for i0, i1 in spans:
+            _call('grl_rrs_segment_rows', *segment(i0, i1) + (ptr(self.colmax[i0:]), ptr(drows), n))
+            _call('grl_topk_block', ptr(drows), n, None, 0, i1 - i0, n, 0, K, ptr(run_key[i0:]), ptr(run_val[i0:]))
+        del drows, run_val
+        self.rank = (run_key & 0xffffffff).to(torch.int32)
+        del run_key
+        # expansion lists, then pass A2: their weights
+        self.lcnt = torch.empty(n, dtype=torch.int32, device=dev)
+        self.lidx = torch.empty((n, RERANK_LMAX), dtype=torch.int32, device=dev)
+        _call('grl_rrs_lists', ptr(self.rank), K, n, k1, ptr(self.lcnt), ptr(self.lidx))
+        self.lval = torch.empty((n, RERANK_LMAX), dtype=torch.float32, device=dev)
+        for i0, i1 in spans:
+            _call('grl_rrs_weights', *segment(i0, i1) + (i0, ptr(self.colmax), ptr(self.lcnt), ptr(self.lidx),
+                                                         ptr(self.lval)))
+        del cb
+        # V2 as CSR (count, scan, one read-back of nnz, fill) and its transpose over all n rows
+        cnt = torch.empty(n, dtype=torch.int32, device=dev)
+        _call('grl_rrs_expand', ptr(self.rank), K, ptr(self.lcnt), ptr(self.lidx), ptr(self.lval), n, k2, None, ptr(cnt),
+              None, None)
+        self.row_ptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        _call('grl_rrs_scan', ptr(cnt), n, ptr(self.row_ptr))
+        self.nnz = nnz = int(self.row_ptr[n])
+        m = max(nnz, 1)
+        self.col = torch.empty(m, dtype=torch.int32, device=dev)
+        self.val = torch.empty(m, dtype=torch.float32, device=dev)
+        _call('grl_rrs_expand', ptr(self.rank), K, ptr(self.lcnt), ptr(self.lidx), ptr(self.lval), n, k2,
+              ptr(self.row_ptr), None, ptr(self.col), ptr(self.val))
+        self.csc_ptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        self.csc_row = torch.zeros(m, dtype=torch.int32, device=dev)
+        self.csc_val = torch.zeros(m, dtype=torch.float32, device=dev)
+        tmp_row = torch.empty(m, dtype=torch.int32, device=dev)
+        tmp_val = torch.empty(m, dtype=torch.float32, device=dev)
+        _call('grl_rrs_transpose', ptr(self.row_ptr), ptr(self.col), ptr(self.val), 0, n, ptr(cnt), ptr(tmp_row),
+              ptr(tmp_val), ptr(self.csc_ptr), ptr(self.csc_row), ptr(self.csc_val))
+
+    def _edges(self, eps, window, cnt, row_ptr, col, val):
+        _call('grl_jaccard_edges', ptr(self.row_ptr), ptr(self.col), ptr(self.val), ptr(self.csc_ptr),
+              ptr(self.csc_row), ptr(self.csc_val), self.n, C.c_float(eps), window, ptr(cnt), ptr(row_ptr), ptr(col),
+              ptr(val))
+
+    def graph(self, eps, max_edges=None, return_dist=False, window=0):
+        """``jaccard_graph``'s result for this state: count pass, grl_rrs_scan, one read-back of E, fill pass.
+        ``window`` is grl_jaccard_edges' (0 = the library's; the result does not depend on it)."""
+        n, dev = self.n, self.row_ptr.device
+        limit = CLUSTER_MAX_EDGES if max_edges is None else int(max_edges)
+        cnt = torch.empty(n, dtype=torch.int32, device=dev)
+        row_ptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        self._edges(eps, window, cnt, None, None, None)
+        _call('grl_rrs_scan', ptr(cnt), n, ptr(row_ptr))
+        n_edges = int(row_ptr[n])
+        if n_edges > limit:
+            raise ValueError('jaccard_graph: eps = %r gives E = %d edges among %d samples, more than the limit of %d '
+                             '(max_edges / GRL_CLUSTER_MAX_EDGES): lower eps or raise the limit'
+                             % (eps, n_edges, n, limit))
+        col = torch.empty(n_edges, dtype=torch.int32, device=dev)
+        val = torch.empty(n_edges, dtype=torch.float32, device=dev) if return_dist else None
+        if n_edges:
+            self._edges(eps, window, None, row_ptr, col, val)
+        return (row_ptr, col, val) if return_dist else (row_ptr, col)
+
+
+def jaccard_graph(xf, eps, k1=20, k2=6, block_cols=None, block_bytes=None, max_edges=None, return_dist=False):
+    """The eps-graph of the rows of ``xf`` [n, d] under the k-reciprocal Jaccard distance (the ``compute_jaccard_distance``
+    of cluster-based re-ID, here the pure Jaccard term of ``re_ranking`` on the one-set Euclidean matrix)
+    as a CSR ``(row_ptr int64 [n+1], col int32 [E])`` on the device, with ``return_dist`` also ``val`` float32 [E], the
+    distance of every edge.  Edge i -> j (j != i) iff J[i][j] = 1 - t / (2 - t) <= float32(eps), t = the sum over the
+    non-zero k of V2[i], ascending, of min(V2[i][k], V2[j][k]).  J lies in [0, 1]; 1 = no shared neighbour, so eps must
+    be finite and < 1, and only pairs whose V2 rows overlap are ever looked at: no n x n pass after the two passes over
+    the distance GEMM's column blocks that build V2.  Columns ascend in every row; the same bits on every run, for
+    every ``block_cols`` / ``block_bytes``.  2 <= n, k1 <= 20, k1 < n, k2 <= 8, k2 <= n; any d >= 1 (rows are zero-padded
+    to the multiple of 32 features the distance GEMM takes).  ValueError, before any device
+    work: a host or non-2-d ``xf``, n < 2, k1 / k2 out of range, eps not finite or >= 1; after the count pass: E above
+    ``max_edges`` (default GRL_CLUSTER_MAX_EDGES), before ``col`` is allocated.  Not sharded: under torch.distributed
+    every rank computes the full, identical graph."""
+    n, eps, k1, k2 = _jaccard_args(xf, eps, k1, k2, 'jaccard_graph')
+    return _JaccardSet(xf, k1, k2, block_cols, block_bytes).graph(eps, max_edges, return_dist)
+
+
+def cluster_jaccard(xf, eps, min_samples=1, k1=20, k2=6, block_cols=None, block_bytes=None, max_edges=None):
+    """DBSCAN of the rows of ``xf`` on the k-reciprocal Jaccard distance at the threshold ``eps`` (0 <= J <= 1; 0.5 -
+    0.6 in the clustering literature): ``cluster_from_graph(*jaccard_graph(xf, eps, k1, k2, ...), n, min_samples)``,
+    the ``Clustering`` that ``cluster`` returns (``pair_scores``, ``centroids``).  A neighbourhood measured in shared
+    k-reciprocal neighbours adapts to each identity's density, where one cosine threshold cannot.  Not sharded."""
+    min_samples = _cluster_min_samples(min_samples, 'cluster_jaccard')
+    n, eps, k1, k2 = _jaccard_args(xf, eps, k1, k2, 'cluster_jaccard')
+    row_ptr, col = _JaccardSet(xf, k1, k2, block_cols, block_bytes).graph(eps, max_edges)
+    return cluster_from_graph(row_ptr, col, n, min_samples, eps=eps, _checked=True)

@@ -86,6 +86,28 @@ def _cluster_report(knob, qf, gf, ids, path, roc=None):
     return lines
 
 
+def _cluster_jaccard_report(knob, gf, ids, path):
+    """GRL_EVAL_CLUSTER_JACCARD: DBSCAN of the query-prepended gallery ``gf`` on the k-reciprocal Jaccard distance
+    (engine.cluster_jaccard) -- the two lines ``_report`` prints after GRL_EVAL_CLUSTER's, and
+    ``path + 'cluster_jaccard.json'`` (rank 0 alone writes; strict JSON): the fields of clusters.json plus k1 and k2.
+    ``knob`` = (eps, min_samples, k1, k2)."""
+    import json
+    eps, min_samples, k1, k2 = knob
+    cl = engine.cluster_jaccard(gf, eps, min_samples, k1, k2)
+    n = int(gf.size(0))
+    scores = cl.pair_scores(ids[1])
+    lines = ['Jaccard clusters: {} ({} noise of {}) at eps = {:g}, min_samples = {}, k1 = {}, k2 = {}'.format(
+                 cl.n_clusters, cl.n_noise, n, cl.eps, cl.min_samples, k1, k2),
+             'Pairwise precision: {:.2%}  recall: {:.2%}  F1: {:.2%}  ARI: {:.4f}'.format(
+                 scores['precision'], scores['recall'], scores['f1'], scores['ari'])]
+    if grl_dist._rank_world(None, None)[0] == 0:
+        with open((path or '') + 'cluster_jaccard.json', 'w') as fh:
+            json.dump({'eps': cl.eps, 'min_samples': cl.min_samples, 'metric': 'jaccard', 'k1': k1, 'k2': k2, 'n': n,
+                       'n_clusters': cl.n_clusters, 'n_noise': cl.n_noise, 'n_edges': cl.n_edges,
+                       'pair_scores': scores, 'labels': cl.labels.cpu().tolist()}, fh, allow_nan=False)
+    return lines
+
+
 def _kmeans_report(knob, gf, ids, path):
     """GRL_EVAL_KMEANS: spherical k-means of the query-prepended gallery ``gf`` (engine.kmeans, 'cosine', random
     initial rows) -- the two lines ``_report`` prints last, and ``path + 'kmeans.json'`` (rank 0 alone writes; strict
@@ -191,6 +213,30 @@ def parse_cluster_knob(name, value):
     if eps != eps or not 1 <= min_samples <= 2 ** 31 - 1:
         raise ValueError('%s: eps must not be NaN and min_samples must be >= 1 (got %r)' % (name, value))
     return eps, min_samples
+
+
+def parse_cluster_jaccard_knob(name, value):
+    """``GRL_EVAL_CLUSTER_JACCARD``: unset or empty -> None (off); "eps", "eps,min_samples", "eps,min_samples,k1" or
+    "eps,min_samples,k1,k2" -> (eps, min_samples, k1, k2) with eps a finite float below 1 (a Jaccard distance), an
+    integer min_samples >= 1 (default 1), k1 in 1..20 (default 20) and k2 in 1..8 (default 6; engine.cluster_jaccard).
+    Anything else is a ValueError that names the variable."""
+    if value is None or not value.strip():
+        return None
+    parts = [p.strip() for p in value.split(',')]
+    try:
+        if len(parts) > 4:
+            raise ValueError
+        eps = float(parts[0])
+        min_samples, k1, k2 = [int(p) for p in parts[1:]] + [1, 20, 6][len(parts) - 1:]
+    except ValueError:
+        raise ValueError('%s must be "eps[,min_samples[,k1[,k2]]]" with a float eps and integer min_samples, k1 and k2 '
+                         '(got %r)' % (name, value))
+    if not (math.isfinite(eps) and float(np.float32(eps)) < 1.0):
+        raise ValueError('%s: eps is a Jaccard distance threshold, finite and below 1 (got %r)' % (name, value))
+    if not (1 <= min_samples <= 2 ** 31 - 1 and 1 <= k1 <= engine.RERANK_K1_MAX and 1 <= k2 <= engine.RERANK_K2_MAX):
+        raise ValueError('%s: min_samples must be >= 1, k1 in 1..%d and k2 in 1..%d (got %r)'
+                         % (name, engine.RERANK_K1_MAX, engine.RERANK_K2_MAX, value))
+    return eps, min_samples, k1, k2
 
 
 def parse_kmeans_knob(name, value):
@@ -343,6 +389,14 @@ class ATTEvaluator(object):
                              'distance is a signed logit of modified query rows against gallery rows, not a distance '
                              'between two samples of one set (unset one of them)'
                              % os.environ['GRL_EVAL_METRIC'].strip())
+        # the same on the k-reciprocal Jaccard distance, off by default (engine.cluster_jaccard), printed after
+        # GRL_EVAL_CLUSTER's lines and stored in path + 'cluster_jaccard.json'
+        jaccard_knob = parse_cluster_jaccard_knob('GRL_EVAL_CLUSTER_JACCARD', os.environ.get('GRL_EVAL_CLUSTER_JACCARD'))
+        if jaccard_knob is not None and knob is not None:
+            raise ValueError('GRL_EVAL_CLUSTER_JACCARD cannot be combined with GRL_EVAL_METRIC=%s: the verification '
+                             'head\'s distance is a signed logit of modified query rows against gallery rows, not a '
+                             'distance between two samples of one set (unset one of them)'
+                             % os.environ['GRL_EVAL_METRIC'].strip())
         # k-means with a known or budgeted number of identities, off by default: spherical k-means of the query-prepended
         # gallery (engine.kmeans), printed last and stored in path + 'kmeans.json'
         kmeans_knob = parse_kmeans_knob('GRL_EVAL_KMEANS', os.environ.get('GRL_EVAL_KMEANS'))
@@ -377,10 +431,12 @@ class ATTEvaluator(object):
         roc_lines = ()
 
         def extra(lines, cosine_roc=None):
-            """the route's ROC lines, then GRL_EVAL_CLUSTER's and GRL_EVAL_KMEANS's (always by cosine, whatever the
-            route ranks by)"""
+            """the route's ROC lines, then GRL_EVAL_CLUSTER's, GRL_EVAL_CLUSTER_JACCARD's and GRL_EVAL_KMEANS's (by
+            cosine or by the Jaccard distance of the features, whatever the route ranks by)"""
             if cluster_knob is not None:
                 lines = tuple(lines) + tuple(_cluster_report(cluster_knob, qf, gf, ids, path, cosine_roc))
+            if jaccard_knob is not None:
+                lines = tuple(lines) + tuple(_cluster_jaccard_report(jaccard_knob, gf, ids, path))
             if kmeans_knob is not None:
                 lines = tuple(lines) + tuple(_kmeans_report(kmeans_knob, gf, ids, path))
             return lines

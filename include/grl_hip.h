@@ -41,8 +41,8 @@ const char* grl_last_error(void);
  * struct layout or argument list, and a library without them fails to bind in _lib.load.  So were the streaming
  * re-ranking entry points grl_rrs_*, the CSR / CSC assembly of its sharded form (grl_rrs_expand_rows, grl_rrs_scan,
  * grl_rrs_place, grl_rrs_transpose) among them, grl_topk_block_filtered, grl_expand_rows, the grl_verify_* entry points,
- * grl_pair_hist_block, the clustering entry points grl_cluster_* and the k-means entry points grl_kmeans_* /
- * grl_segment_rowsum. */
+ * grl_pair_hist_block, the clustering entry points grl_cluster_*, the k-means entry points grl_kmeans_* /
+ * grl_segment_rowsum and grl_jaccard_edges. */
 #define GRL_ABI_VERSION 10
 int grl_abi_version(void);
 /* `waiter` (a hipStream_t) waits for everything enqueued on `signaler` so far: hipEventRecord + hipStreamWaitEvent on a
@@ -662,6 +662,21 @@ int grl_cluster_roots(const uint8_t* core, const int32_t* parent, int n, int32_t
 /* labels[i] = root_id[parent[i]] (core), root_id[border[i]] (border point), -1 (noise): ids ascend with the root */
 int grl_cluster_labels(const uint8_t* core, const int32_t* parent, const int32_t* border, const int64_t* root_id, int n,
                        int64_t* labels, void* stream);
+
+/* ---- eps-graph of the k-reciprocal Jaccard distance of one sample set (jaccard.hip, engine.jaccard_graph /
+ * cluster_jaccard) ----
+ * row_ptr_v2 / col_v2 / val_v2: V2 of all n samples as CSR (grl_rrs_expand: ascending columns, no zeros, at most 2048
+ * entries a row); csc_ptr / csc_row / csc_val: its transpose over ALL rows (grl_rrs_transpose with nq = 0).
+ * t[i][j] = the fp32 sum over row i's entries k, ascending, of min(V2[i][k], V2[j][k]); J = 1 - t / (2 - t); edge
+ * i -> j iff j != i and J <= eps.  Count pass (out_row_ptr = out_col = out_val = NULL): cnt[i] = the edges of row i.
+ * Fill pass (out_row_ptr [n+1] = grl_rrs_scan of cnt): out_col gets every row's columns in ascending order and
+ * out_val, when not NULL, their J.  ``window`` = columns of a row whose sums are held in LDS at a time: 0 (the
+ * library's choice, 8192) or a multiple of 256 up to 8192; the result does not depend on it.  No float atomics: the
+ * same bits on every run.  GRL_EINVAL, before any launch: a null pointer, n < 2, eps not finite or >= 1, a window that
+ * is negative, no multiple of 256 or above 8192, cnt missing in the count pass, out_col missing in the fill pass. */
+int grl_jaccard_edges(const int64_t* row_ptr_v2, const int32_t* col_v2, const float* val_v2, const int64_t* csc_ptr,
+                      const int32_t* csc_row, const float* csc_val, int n, float eps, int window, int32_t* cnt,
+                      const int64_t* out_row_ptr, int32_t* out_col, float* out_val, void* stream);
 
 /* ---- k-means and cluster centroids (kmeans.hip, engine.kmeans / kmeans_assign / cluster_centroids) ----
  * The assignment is grl_topk_block at k = 1 over column blocks of the sample x centroid distance matrix; these entry
