@@ -178,6 +178,10 @@ _SIGNATURES = {
     'grl_kmeans_members': ([_fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp], C.c_int),
     'grl_segment_rowsum': ([_fp, _i64, C.c_int, _fp, _fp, _i64, C.c_int, C.c_int, _fp, _i64, _fp], C.c_int),
     'grl_kmeans_finish': ([_fp, _i64, _fp, _fp, _fp, _i64, C.c_int, C.c_int, C.c_int, _fp, _i64, _fp, _fp], C.c_int),
+    'grl_silhouette_block': ([_fp, _i64, C.c_int, C.c_int, _i64, C.c_int, _fp, _fp, C.c_int] + [_fp] * 6 + [_fp],
+                             C.c_int),
+    'grl_silhouette_finish': ([_fp, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp], C.c_int),
+    'grl_silhouette_rinv': ([_fp, C.c_int, _fp, _fp], C.c_int),
     'grl_expand_rows': ([_fp, _i64, _fp, _i64, _fp, _fp, _i64] + [C.c_int] * 7 + [_fp, _i64, _fp], C.c_int),
     'grl_verify_fold': ([_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
     'grl_verify_rows': ([_fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, _fp],

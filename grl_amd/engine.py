@@ -1819,7 +1819,8 @@ class Clustering(object):
       parent       int32 device [n]: a core point's root (its cluster's smallest core index); i for a non-core point
       n_clusters, n_noise, n_edges (stored directed edges E), rounds (component rounds run), eps, min_samples
       pair_scores(pids)   pairwise precision / recall / F1 / ARI of the labels against true identities
-      centroids(xf, reduce='unit')   the clusters' centres (cluster_centroids)"""
+      centroids(xf, reduce='unit')   the clusters' centres (cluster_centroids)
+      silhouette(xf, metric='cosine', noise='singleton')   the label-free score of the labels (silhouette)"""
 
     def __init__(self, labels, core, parent, n_clusters, n_noise, n_edges, rounds, eps, min_samples):
         self.labels, self.core, self.parent = labels, core, parent
@@ -1840,6 +1841,10 @@ class Clustering(object):
         """The clusters' centres ``(centroids [n_clusters, d], counts int64 [n_clusters])`` of the rows of ``xf`` the
         labels were computed from: ``cluster_centroids(xf, labels, n_clusters, reduce)``, noise ignored."""
         return cluster_centroids(xf, self.labels, self.n_clusters, reduce)
+
+    def silhouette(self, xf, metric='cosine', noise='singleton'):
+        """``silhouette(xf, labels, metric, noise)`` of the rows the labels were computed from."""
+        return silhouette(xf, self.labels, metric, noise)
 
 
 def _pair_scores(labels, n_clusters, pids):
@@ -2169,7 +2174,8 @@ class KMeans(object):
       usable sum at the last update: they kept their previous row), n_unassigned, k, metric
       inertia      float64: the sum over assigned samples of the distance to their centroid at the last assignment
                    ('cosine': the negated dot products; 'euclidean': the squared distances)
-      pair_scores(pids)   pairwise precision / recall / F1 / ARI of the labels against true identities"""
+      pair_scores(pids)   pairwise precision / recall / F1 / ARI of the labels against true identities
+      silhouette(xf, metric=None)   the label-free score of the labels (silhouette)"""
 
     def __init__(self, labels, centroids, counts, n_iter, converged, n_changed, n_empty, n_unassigned, k, metric,
                  inertia):
@@ -2180,6 +2186,11 @@ class KMeans(object):
     def pair_scores(self, pids):
         """``Clustering.pair_scores``: an unassigned sample is a cluster of its own."""
         return _pair_scores(self.labels, self.k, pids)
+
+    def silhouette(self, xf, metric=None):
+        """``silhouette(xf, labels, metric)``; ``metric`` defaults to the run's own.  An unassigned
+        sample is a cluster of its own, as in ``pair_scores``."""
+        return silhouette(xf, self.labels, self.metric if metric is None else metric)
 
 
 def _kmeans_init(xf, k, init, seed):
@@ -2636,3 +2647,199 @@ def cluster_jaccard(xf, eps, min_samples=1, k1=20, k2=6, block_cols=None, block_
     n, eps, k1, k2 = _jaccard_args(xf, eps, k1, k2, 'cluster_jaccard')
     row_ptr, col = _JaccardSet(xf, k1, k2, block_cols, block_bytes).graph(eps, max_edges)
     return cluster_from_graph(row_ptr, col, n, min_samples, eps=eps, _checked=True)
+
+
+# ----------------------------------------------------------------------------
+# silhouette coefficients of a clustering over the distance GEMM's column blocks (silhouette.hip)
+# ----------------------------------------------------------------------------
+class Silhouette(object):
+    """The result of ``silhouette`` / ``silhouette_matrix``:
+
+      samples      float32 device [n]: s(i) = (b - a) / max(a, b); 0 for a sample whose cluster has one member
+      a, b         float32 device [n]: the mean distance to the sample's own cluster (itself left out) and the smallest
+                   mean distance to another cluster
+      scored       bool device [n]: False for the samples ``noise='drop'`` left out (their samples / a / b are 0)
+      score        float64: the mean of ``samples`` over the scored rows, NaN if one of them is NaN
+      n_scored, n_clusters (the non-empty clusters, singletons included), metric, noise"""
+
+    def __init__(self, samples, a, b, scored, score, n_scored, n_clusters, metric, noise):
+        self.samples, self.a, self.b, self.scored = samples, a, b, scored
+        self.score, self.n_scored, self.n_clusters, self.metric, self.noise = score, n_scored, n_clusters, metric, noise
+
+
+def _silhouette_args(labels, n, noise, what):
+    """The checks that need no device."""
+    if noise not in ('singleton', 'drop'):
+        raise ValueError("%s: noise must be 'singleton' or 'drop' (got %r)" % (what, noise))
+    if not (torch.is_tensor(labels) and labels.dim() == 1 and labels.numel() == n
+            and not labels.dtype.is_floating_point and not labels.dtype.is_complex and labels.dtype != torch.bool):
+        raise ValueError('%s: labels must be an integer device tensor with one entry per sample (%d)' % (what, n))
+
+
+def _silhouette_labels(labels, n, noise, what):
+    """The clusters as the kernels take them: (labels int32 [n] with -1 = nobody's, counts int32 [k], mptr int64 [k+1],
+    mem int32 [m], k, m, n_clusters).  Two read-backs: (max label, labels < 0) and the number of non-empty clusters."""
+    if not labels.is_cuda:
+        raise _lib.GrlHipError('labels must live on a HIP device (got %s): grl_amd has no CPU path' % labels.device)
+    dev = labels.device
+    lab = labels.to(torch.int64).clamp(min=-1)
+    neg = lab < 0
+    top, n_neg = (torch.stack((lab.max(), neg.sum())).tolist()) if n else (-1, 0)
+    k = top + 1
+    if noise == 'singleton' and n_neg:          # pair_scores' convention: every label < 0 is a cluster of its own
+        lab = torch.where(neg, k - 1 + torch.cumsum(neg.to(torch.int64), 0), lab)
+        k += n_neg
+    if k > 2 ** 31 - 1:
+        raise ValueError('%s: cluster ids must stay below 2^31 (got %d)' % (what, k - 1))
+    if k < 2:
+        raise ValueError('%s: the scored samples lie in fewer than 2 clusters' % what)
+    lab32 = lab.to(torch.int32)
+    counts = torch.zeros(k, dtype=torch.int32, device=dev)
+    _call('grl_kmeans_label_counts', ptr(lab32), n, k, ptr(counts))
+    n_clusters = int((counts > 0).sum())
+    if n_clusters < 2:
+        raise ValueError('%s: the scored samples lie in fewer than 2 clusters (%d)' % (what, n_clusters))
+    mptr = torch.empty(k + 1, dtype=torch.int64, device=dev)
+    _call('grl_rrs_scan', ptr(counts), k, ptr(mptr))
+    cursor = torch.zeros(k, dtype=torch.int32, device=dev)
+    tmp = torch.empty(n, dtype=torch.int32, device=dev)
+    mem = torch.empty(n, dtype=torch.int32, device=dev)
+    _call('grl_kmeans_members', ptr(lab32), n, k, ptr(mptr), ptr(cursor), ptr(tmp), ptr(mem))
+    m = n - (n_neg if noise == 'drop' else 0)
+    return lab32, counts, mptr, mem[:m], k, m, n_clusters
+
+
+def _silhouette_width(n, m, block_cols, block_bytes):
+    if block_cols is None:
+        budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
+        block_cols = max(256, budget // (4 * max(n, 1)) // 256 * 256)
+    return max(1, min(int(block_cols), m))
+
+
+def _silhouette_pass(block, n, width, cl, rinv, metric, noise):
+    """The pass over the member order: ``block(c0, c1)`` -> the [n, c1 - c0] distances of every sample against the
+    samples mem[c0:c1]; the blocks go to grl_silhouette_block in ascending position order on the current stream."""
+    import numpy as np
+    lab32, counts, mptr, mem, k, m, n_clusters = cl
+    dev = lab32.device
+    part = torch.empty((n, 64), dtype=torch.float32, device=dev)
+    a = torch.empty(n, dtype=torch.float32, device=dev)
+    b = torch.empty(n, dtype=torch.float32, device=dev)
+    s = torch.empty(n, dtype=torch.float32, device=dev)
+    rinv_pos = rinv[mem.to(torch.int64)] if rinv is not None else None
+    for c0 in range(0, m, width):
+        c1 = min(c0 + width, m)
+        d = block(c0, c1)
+        _call('grl_silhouette_block', ptr(d), d.stride(0), n, 0, c0, c1 - c0, ptr(mem), ptr(mptr), k, ptr(lab32),
+              ptr(rinv), ptr(rinv_pos), ptr(part), ptr(a), ptr(b))
+    _call('grl_silhouette_finish', ptr(a), ptr(b), ptr(lab32), ptr(counts), n, k, ptr(s))
+    scored = lab32 >= 0
+    host = s.cpu().numpy().astype(np.float64)[scored.cpu().numpy()]
+    return Silhouette(s, a, b, scored, float(host.mean()), int(host.size), n_clusters, metric, noise)
+
+
+def silhouette(xf, labels, metric='cosine', noise='singleton', block_cols=None, block_bytes=None):
+    """The silhouette coefficient s(i) = (b - a) / max(a, b) of every row of ``xf`` [n, d] under ``labels`` (any integer
+    device tensor [n]) as a ``Silhouette``: the label-free measure of a clustering, for choosing ``eps``,
+    ``min_samples`` or ``k`` without ground truth.  a = the mean distance to the other members of the sample's cluster,
+    b = the smallest mean distance to the members of another cluster; a cluster of one scores 0 (scikit-learn's rule).
+    'cosine' is 1 - cos of the rows, which need not be unit: dist = max(0, 1 + (D * rinv_i) * rinv_j) with D =
+    ``cosin_dist(xf, xf)`` and rinv = 1 / sqrt(grl_row_sqnorm) -- no normalised copy of ``xf`` is made; 'euclidean' is
+    ``pairwise_distance_tensor(xf, xf)``.  ``noise``: 'singleton' (the convention of ``pair_scores``: every label < 0 is
+    a cluster of its own and scores 0) or 'drop' (those samples are neither rows nor columns: ``samples`` 0, ``scored``
+    False).  The distances come in column blocks of the MEMBER ORDER (the samples of cluster 0 ascending, then cluster
+    1's, ..): the rows xf[mem[c0:c1]] are gathered into a buffer of the block's width and go through ``_ColumnBlocks``'
+    GEMM, so every entry carries the full matrix's bits, and a small kernel folds the block into O(n) state.  No n x n,
+    n x k or second n x d tensor exists (rows whose width is no multiple of 32 are zero-padded first, as the distance
+    GEMM requires).  Every sum has a fixed order: the same bits on every run and for every block width.
+    Cluster ids are used as they are (ids without members are skipped; the state holds max(label) + 1 counters).  Not
+    sharded: under torch.distributed every rank computes the full, identical result.  ValueError: a ``verify_metric``,
+    an unknown ``metric`` or ``noise``, labels that are not n integers, fewer than 2 non-empty clusters among the
+    scored samples, ``xf`` without columns."""
+    _cluster_metric(metric, 'silhouette')
+    if not torch.is_tensor(xf) or xf.dim() < 2:
+        raise ValueError('silhouette: xf must be a tensor [n, d] (got %s)'
+                         % (tuple(xf.shape) if torch.is_tensor(xf) else type(xf).__name__,))
+    _silhouette_args(labels, xf.shape[0], noise, 'silhouette')
+    xf = _kmeans_rows(xf, 'silhouette')
+    n = xf.shape[0]
+    cl = _silhouette_labels(labels, n, noise, 'silhouette')
+    mem, m = cl[3], cl[5]
+    xf = _pad_features(xf)
+    d = xf.shape[1]
+    width = _silhouette_width(n, m, block_cols, block_bytes)
+    rows = _new((width, d), xf)
+    buf = _new((n * width,), xf)
+    sq = _new((n,), xf)
+    _call('grl_row_sqnorm', ptr(xf), ptr(sq), n, d, d)
+    rinv = cn = None
+    if metric == 'cosine':
+        rinv = _new((n,), xf)
+        _call('grl_silhouette_rinv', ptr(sq), n, ptr(rinv))
+    else:
+        cn = _new((width,), xf)
+    mem64 = mem.to(torch.int64)
+
+    def block(c0, c1):
+        w = c1 - c0
+        torch.index_select(xf, 0, mem64[c0:c1], out=rows[:w])
+        out = buf[:n * w].view(n, w)
+        if metric == 'cosine':
+            return gemm(xf, rows[:w], out, n, w, d, epilogue=EPI_NEGDOT, math=MATH_F32)
+        torch.index_select(sq, 0, mem64[c0:c1], out=cn[:w])
+        return gemm(xf, rows[:w], out, n, w, d, epilogue=EPI_EUCLID, rnorm=sq, cnorm=cn[:w], math=MATH_F32)
+    return _silhouette_pass(block, n, width, cl, rinv, metric, noise)
+
+
+def silhouette_matrix(distmat, labels, noise='singleton', block_cols=None, block_bytes=None):
+    """``silhouette`` on an [n, n] float32 distance matrix that already lives on the device, used as given (entry [i][j]
+    is the distance of sample i to sample j; it need not be symmetric); rows may be strided.  The columns are gathered
+    into the member order one block at a time.  ``metric`` of the result is 'precomputed'.  ValueError: not square."""
+    if not torch.is_tensor(distmat) or distmat.dim() != 2 or distmat.shape[0] != distmat.shape[1]:
+        raise ValueError('silhouette_matrix: distmat must be square [n, n] (got %s)'
+                         % (tuple(distmat.shape) if torch.is_tensor(distmat) else type(distmat).__name__,))
+    n = distmat.shape[0]
+    _silhouette_args(labels, n, noise, 'silhouette_matrix')
+    if distmat.dtype != torch.float32:
+        raise ValueError('silhouette_matrix: distmat must be float32 (got %s)' % distmat.dtype)
+    require_device(distmat, 'distmat')
+    cl = _silhouette_labels(labels, n, noise, 'silhouette_matrix')
+    mem, m = cl[3], cl[5]
+    width = _silhouette_width(n, m, block_cols, block_bytes)
+    buf = _new((n * width,), distmat)
+    mem64 = mem.to(torch.int64)
+
+    def block(c0, c1):
+        out = buf[:n * (c1 - c0)].view(n, c1 - c0)
+        return torch.index_select(distmat, 1, mem64[c0:c1], out=out)
+    return _silhouette_pass(block, n, width, cl, None, 'precomputed', noise)
+
+
+def cluster_select(xf, eps_list, min_samples=1, metric='cosine', score_metric=None, block_cols=None, block_bytes=None,
+                   max_edges=None):
+    """``cluster(xf, eps, min_samples, metric)`` at every eps of ``eps_list``, each result scored by
+    ``silhouette(xf, labels, score_metric or metric, noise='singleton')`` -- noise as singletons, which score 0, so that
+    shedding samples as noise cannot raise the score.  Returns ``(best Clustering, rows)``; ``rows`` is a list of dicts
+    ``eps`` (the float32 compared with), ``n_clusters``, ``n_noise``, ``score`` in the order given, ``score`` None where
+    fewer than 2 clusters exist.  The best is the highest finite score; ties go to the smaller eps.  ValueError: an
+    empty list, no eps with a finite score."""
+    import math
+    score_metric = metric if score_metric is None else score_metric
+    _cluster_metric(metric, 'cluster_select')
+    _cluster_metric(score_metric, 'cluster_select')
+    eps_list = [_cluster_eps(e, 'cluster_select') for e in eps_list]
+    if not eps_list:
+        raise ValueError('cluster_select: eps_list is empty')
+    best, rows = None, []
+    for eps in eps_list:
+        cl = cluster(xf, eps, min_samples, metric, block_cols, block_bytes, max_edges)
+        score = None
+        if cl.n_clusters + cl.n_noise >= 2:
+            score = silhouette(xf, cl.labels, score_metric, 'singleton', block_cols, block_bytes).score
+        rows.append({'eps': eps, 'n_clusters': cl.n_clusters, 'n_noise': cl.n_noise, 'score': score})
+        if score is not None and math.isfinite(score):
+            if best is None or score > best[0] or (score == best[0] and eps < best[1]):
+                best = (score, eps, cl)
+    if best is None:
+        raise ValueError('cluster_select: no eps of %r gives 2 or more clusters with a finite score' % (eps_list,))
+    return best[2], rows

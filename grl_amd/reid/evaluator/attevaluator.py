@@ -57,11 +57,31 @@ def _roc_report(roc, metric_name, path):
     return lines
 
 
-def _cluster_report(knob, qf, gf, ids, path, roc=None):
+def _silhouette_report(sil, gf, labels, js):
+    """GRL_EVAL_SILHOUETTE: the label-free score of a report's ``labels`` on the features ``gf`` (engine.silhouette) --
+    the report's third line, and its JSON's "silhouette" entry (a score that is not finite is null; labels with fewer
+    than 2 clusters have no silhouette: the line says so and the entry's score is null).  ``sil`` = (metric, noise) or
+    None, which adds nothing."""
+    if sil is None:
+        return []
+    metric, noise = sil
+    lab = labels.cpu().numpy()
+    if np.unique(lab[lab >= 0]).size + (int((lab < 0).sum()) if noise == 'singleton' else 0) < 2:
+        js['silhouette'] = {'metric': metric, 'noise': noise, 'score': None, 'n_scored': 0, 'n_clusters': 0}
+        return ['Silhouette ({}): undefined, fewer than 2 clusters'.format(metric)]
+    r = engine.silhouette(gf, labels, metric, noise)
+    js['silhouette'] = {'metric': metric, 'noise': noise, 'score': r.score if math.isfinite(r.score) else None,
+                        'n_scored': r.n_scored, 'n_clusters': r.n_clusters}
+    return ['Silhouette ({}): {:.4f} over {} of {} samples, {} clusters'.format(
+        metric, r.score, r.n_scored, int(gf.size(0)), r.n_clusters)]
+
+
+def _cluster_report(knob, qf, gf, ids, path, roc=None, sil=None):
     """GRL_EVAL_CLUSTER: DBSCAN of the query-prepended gallery ``gf`` by cosine (engine.cluster) -- the two lines
     ``_report`` prints after any ROC lines, and ``path + 'clusters.json'`` (rank 0 alone writes; strict JSON).
     ``knob`` = (eps or 'eer', min_samples); 'eer' is the ``eer_threshold`` of the cosine ``engine.pair_roc`` of
-    (qf, gf), taken from ``roc`` when the route has already computed that one."""
+    (qf, gf), taken from ``roc`` when the route has already computed that one.  ``sil`` (GRL_EVAL_SILHOUETTE): a third
+    line and the JSON's "silhouette" entry (``_silhouette_report``)."""
     import json
     eps, min_samples = knob
     if eps == 'eer':
@@ -78,19 +98,22 @@ def _cluster_report(knob, qf, gf, ids, path, roc=None):
                  cl.n_clusters, cl.n_noise, n, cl.eps, cl.min_samples),
              'Pairwise precision: {:.2%}  recall: {:.2%}  F1: {:.2%}  ARI: {:.4f}'.format(
                  scores['precision'], scores['recall'], scores['f1'], scores['ari'])]
+    js = {'eps': cl.eps, 'min_samples': cl.min_samples, 'metric': 'cosine', 'n': n, 'n_clusters': cl.n_clusters,
+          'n_noise': cl.n_noise, 'n_edges': cl.n_edges, 'pair_scores': scores, 'labels': cl.labels.cpu().tolist()}
+    lines += _silhouette_report(sil, gf, cl.labels, js)
     if grl_dist._rank_world(None, None)[0] == 0:
         with open((path or '') + 'clusters.json', 'w') as fh:
-            json.dump({'eps': cl.eps, 'min_samples': cl.min_samples, 'metric': 'cosine', 'n': n,
-                       'n_clusters': cl.n_clusters, 'n_noise': cl.n_noise, 'n_edges': cl.n_edges,
-                       'pair_scores': scores, 'labels': cl.labels.cpu().tolist()}, fh, allow_nan=False)
+            json.dump(js, fh, allow_nan=False)
     return lines
 
 
-def _cluster_jaccard_report(knob, gf, ids, path):
+def _cluster_jaccard_report(knob, gf, ids, path, sil=None):
     """GRL_EVAL_CLUSTER_JACCARD: DBSCAN of the query-prepended gallery ``gf`` on the k-reciprocal Jaccard distance
     (engine.cluster_jaccard) -- the two lines ``_report`` prints after GRL_EVAL_CLUSTER's, and
     ``path + 'cluster_jaccard.json'`` (rank 0 alone writes; strict JSON): the fields of clusters.json plus k1 and k2.
-    ``knob`` = (eps, min_samples, k1, k2)."""
+    ``knob`` = (eps, min_samples, k1, k2).  ``sil`` (GRL_EVAL_SILHOUETTE): a third line and the JSON's "silhouette"
+    entry -- the score of the Jaccard LABELS under the feature metric (cosine or Euclidean distance of the rows of
+    ``gf``), not under the Jaccard distance itself, which is sparse and has no silhouette kernel."""
     import json
     eps, min_samples, k1, k2 = knob
     cl = engine.cluster_jaccard(gf, eps, min_samples, k1, k2)
@@ -100,18 +123,21 @@ def _cluster_jaccard_report(knob, gf, ids, path):
                  cl.n_clusters, cl.n_noise, n, cl.eps, cl.min_samples, k1, k2),
              'Pairwise precision: {:.2%}  recall: {:.2%}  F1: {:.2%}  ARI: {:.4f}'.format(
                  scores['precision'], scores['recall'], scores['f1'], scores['ari'])]
+    js = {'eps': cl.eps, 'min_samples': cl.min_samples, 'metric': 'jaccard', 'k1': k1, 'k2': k2, 'n': n,
+          'n_clusters': cl.n_clusters, 'n_noise': cl.n_noise, 'n_edges': cl.n_edges, 'pair_scores': scores,
+          'labels': cl.labels.cpu().tolist()}
+    lines += _silhouette_report(sil, gf, cl.labels, js)
     if grl_dist._rank_world(None, None)[0] == 0:
         with open((path or '') + 'cluster_jaccard.json', 'w') as fh:
-            json.dump({'eps': cl.eps, 'min_samples': cl.min_samples, 'metric': 'jaccard', 'k1': k1, 'k2': k2, 'n': n,
-                       'n_clusters': cl.n_clusters, 'n_noise': cl.n_noise, 'n_edges': cl.n_edges,
-                       'pair_scores': scores, 'labels': cl.labels.cpu().tolist()}, fh, allow_nan=False)
+            json.dump(js, fh, allow_nan=False)
     return lines
 
 
-def _kmeans_report(knob, gf, ids, path):
+def _kmeans_report(knob, gf, ids, path, sil=None):
     """GRL_EVAL_KMEANS: spherical k-means of the query-prepended gallery ``gf`` (engine.kmeans, 'cosine', random
     initial rows) -- the two lines ``_report`` prints last, and ``path + 'kmeans.json'`` (rank 0 alone writes; strict
-    JSON, no centroids).  ``knob`` = (k or 'ids', max_iter, seed); 'ids' is the number of distinct pids in ``gf``."""
+    JSON, no centroids).  ``knob`` = (k or 'ids', max_iter, seed); 'ids' is the number of distinct pids in ``gf``.
+    ``sil`` (GRL_EVAL_SILHOUETTE): a third line and the JSON's "silhouette" entry (``_silhouette_report``)."""
     import json
     k, max_iter, seed = knob
     if k == 'ids':
@@ -123,14 +149,14 @@ def _kmeans_report(knob, gf, ids, path):
                  km.k, n, km.n_iter, 'converged' if km.converged else 'not converged', km.n_empty, km.inertia),
              'Pairwise precision: {:.2%}  recall: {:.2%}  F1: {:.2%}  ARI: {:.4f}'.format(
                  scores['precision'], scores['recall'], scores['f1'], scores['ari'])]
+    js = {'k': km.k, 'max_iter': max_iter, 'seed': seed, 'init': 'random', 'metric': 'cosine', 'n': n,
+          'n_iter': km.n_iter, 'converged': km.converged, 'n_changed': km.n_changed, 'n_empty': km.n_empty,
+          'n_unassigned': km.n_unassigned, 'inertia': km.inertia if math.isfinite(km.inertia) else None,
+          'counts': km.counts.cpu().tolist(), 'pair_scores': scores, 'labels': km.labels.cpu().tolist()}
+    lines += _silhouette_report(sil, gf, km.labels, js)
     if grl_dist._rank_world(None, None)[0] == 0:
         with open((path or '') + 'kmeans.json', 'w') as fh:
-            json.dump({'k': km.k, 'max_iter': max_iter, 'seed': seed, 'init': 'random', 'metric': 'cosine', 'n': n,
-                       'n_iter': km.n_iter, 'converged': km.converged, 'n_changed': km.n_changed,
-                       'n_empty': km.n_empty, 'n_unassigned': km.n_unassigned,
-                       'inertia': km.inertia if math.isfinite(km.inertia) else None,
-                       'counts': km.counts.cpu().tolist(), 'pair_scores': scores, 'labels': km.labels.cpu().tolist()},
-                      fh, allow_nan=False)
+            json.dump(js, fh, allow_nan=False)
     return lines
 
 
@@ -259,6 +285,20 @@ def parse_kmeans_knob(name, value):
     if (k != 'ids' and not 1 <= k <= 2 ** 31 - 1) or not 1 <= max_iter <= 2 ** 31 - 1 or seed < 0:
         raise ValueError('%s: k and max_iter must be >= 1 and seed >= 0 (got %r)' % (name, value))
     return k, max_iter, seed
+
+
+def parse_silhouette_knob(name, value):
+    """``GRL_EVAL_SILHOUETTE``: unset or empty -> None (off); "1" or "cosine", or "euclidean", optionally followed by
+    ",drop" or ",singleton" -> (metric, noise) for engine.silhouette (default noise: 'singleton', the convention of
+    ``pair_scores``).  Anything else is a ValueError that names the variable."""
+    if value is None or not value.strip():
+        return None
+    parts = [p.strip() for p in value.split(',')]
+    metric = {'1': 'cosine', 'cosine': 'cosine', 'euclidean': 'euclidean'}.get(parts[0])
+    if metric is None or len(parts) > 2 or (len(parts) == 2 and parts[1] not in ('drop', 'singleton')):
+        raise ValueError('%s must be "1", "cosine" or "euclidean", optionally followed by ",drop" or ",singleton" '
+                         '(got %r)' % (name, value))
+    return metric, parts[1] if len(parts) == 2 else 'singleton'
 
 
 class ATTEvaluator(object):
@@ -404,6 +444,12 @@ class ATTEvaluator(object):
             raise ValueError('GRL_EVAL_KMEANS cannot be combined with GRL_EVAL_METRIC=%s: k-means runs by cosine on '
                              'the routes that rank by cosine (unset one of them)'
                              % os.environ['GRL_EVAL_METRIC'].strip())
+        # the label-free score of those clusterings, off by default (engine.silhouette): a third line of each report and
+        # a "silhouette" entry of its JSON file
+        sil_knob = parse_silhouette_knob('GRL_EVAL_SILHOUETTE', os.environ.get('GRL_EVAL_SILHOUETTE'))
+        if sil_knob is not None and cluster_knob is None and jaccard_knob is None and kmeans_knob is None:
+            raise ValueError('GRL_EVAL_SILHOUETTE scores the labels of GRL_EVAL_CLUSTER, GRL_EVAL_CLUSTER_JACCARD or '
+                             'GRL_EVAL_KMEANS: set one of them too (or unset GRL_EVAL_SILHOUETTE)')
         qf, q_pids, q_camids = self.extract_feature(query_loader)
         print('Done, obtained {}-by-{} matrix'.format(qf.size(0), qf.size(1)))
         gf, g_pids, g_camids = self.extract_feature(gallery_loader)
@@ -434,11 +480,11 @@ class ATTEvaluator(object):
             """the route's ROC lines, then GRL_EVAL_CLUSTER's, GRL_EVAL_CLUSTER_JACCARD's and GRL_EVAL_KMEANS's (by
             cosine or by the Jaccard distance of the features, whatever the route ranks by)"""
             if cluster_knob is not None:
-                lines = tuple(lines) + tuple(_cluster_report(cluster_knob, qf, gf, ids, path, cosine_roc))
+                lines = tuple(lines) + tuple(_cluster_report(cluster_knob, qf, gf, ids, path, cosine_roc, sil_knob))
             if jaccard_knob is not None:
-                lines = tuple(lines) + tuple(_cluster_jaccard_report(jaccard_knob, gf, ids, path))
+                lines = tuple(lines) + tuple(_cluster_jaccard_report(jaccard_knob, gf, ids, path, sil_knob))
             if kmeans_knob is not None:
-                lines = tuple(lines) + tuple(_kmeans_report(kmeans_knob, gf, ids, path))
+                lines = tuple(lines) + tuple(_kmeans_report(kmeans_knob, gf, ids, path, sil_knob))
             return lines
         if visual:
             self._visualize(query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, rerank)

@@ -42,7 +42,7 @@ const char* grl_last_error(void);
  * re-ranking entry points grl_rrs_*, the CSR / CSC assembly of its sharded form (grl_rrs_expand_rows, grl_rrs_scan,
  * grl_rrs_place, grl_rrs_transpose) among them, grl_topk_block_filtered, grl_expand_rows, the grl_verify_* entry points,
  * grl_pair_hist_block, the clustering entry points grl_cluster_*, the k-means entry points grl_kmeans_* /
- * grl_segment_rowsum and grl_jaccard_edges. */
+ * grl_segment_rowsum, grl_jaccard_edges and the silhouette entry points grl_silhouette_*. */
 #define GRL_ABI_VERSION 10
 int grl_abi_version(void);
 /* `waiter` (a hipStream_t) waits for everything enqueued on `signaler` so far: hipEventRecord + hipStreamWaitEvent on a
@@ -709,6 +709,38 @@ int grl_segment_rowsum(const float* x, int64_t ld, int n, const int64_t* mptr, c
  * stride ldp) or zeros when prev is NULL, and *empty += 1 (int32, zeroed by the caller).  Plain stores. */
 int grl_kmeans_finish(const float* sum, int64_t lds, const int32_t* counts, const float* sq, const float* prev,
                       int64_t ldp, int k, int d, int reduce, float* out, int64_t ldo, int32_t* empty, void* stream);
+
+/* ---- silhouette coefficients over column blocks (silhouette.hip, engine.silhouette / silhouette_matrix) ----
+ * Member order: mem [m] int32 holds cluster 0's samples in ascending sample index, then cluster 1's, ..; mptr [k+1]
+ * int64, mptr[c] = the first position of cluster c, mptr[k] = m (grl_kmeans_label_counts, grl_rrs_scan,
+ * grl_kmeans_members).  labels int32 [n]: a sample whose label is outside 0..k-1 is nobody's -- it is not in mem, and
+ * its row is skipped.  ``d`` [nrows][ld] (ncols used) is a block of the distance matrix: row r is sample row0 + r,
+ * column j is POSITION c0 + j of the member order, that is sample mem[c0 + j]; columns at or beyond mptr[k] are ignored.
+ * Distance of an entry: the value of d as it is (rinv_row = rinv_pos = NULL), or, with rinv_row [n] and rinv_pos [m]
+ * (= rinv_row[mem[p]]) given, the cosine form of d = -dot: v = (d * rinv_row[i]) * rinv_pos[p], dist = 1.0f + v,
+ * dist < 0 ? 0 : dist -- single fp32 operations, no fma; a NaN stays NaN.
+ * Sum of row i towards cluster c, in this fixed order whatever the block cuts: 64 partial sums, partial l = the
+ * sequential fp32 sum from +0.0f, in ascending position, of the distances at the cluster's positions p with
+ * p % 64 == l, the position with mem[p] == i left out (by index, not by value); then part[l] += part[l + s], l < s, for
+ * s = 32, 16, 8, 4, 2, 1.  mean = sum / float(count), count = n_c - 1 for the row's own cluster (n_c = 1: a = 0) and
+ * n_c otherwise.  a[i] = the own cluster's mean; bmin[i] = the minimum of the other non-empty clusters' means (-0 below
+ * +0; from +inf), NaN as soon as one of them is NaN.  Adds only, no atomics of any kind: the same bits on
+ * every run and for every block width.
+ * State between the blocks of a pass, all float32: part [n][64] (the lane partials of the one cluster that straddles
+ * the block edge), a [n], bmin [n]; none needs initialising -- the block with c0 == 0 starts them.  The blocks of a
+ * pass are enqueued in ascending position order on one stream, every row at most once per call.  One wave per row.
+ * GRL_EINVAL, before any launch: a null pointer, a negative size, k < 1, ncols < 1, ld < ncols, one of rinv_row /
+ * rinv_pos without the other. */
+int grl_silhouette_block(const float* d, int64_t ld, int nrows, int row0, int64_t c0, int ncols, const int32_t* mem,
+                         const int64_t* mptr, int k, const int32_t* labels, const float* rinv_row,
+                         const float* rinv_pos, float* part, float* a, float* bmin, void* stream);
+/* After the last block: s[i] = 0 for a sample that is nobody's (a = bmin = 0 are stored) or whose cluster has one
+ * member (counts[label] <= 1; a = 0 is stored: scikit-learn's rule), NaN when a or bmin is NaN, 0 when max(a, bmin)
+ * == 0, otherwise (bmin - a) / max(a, bmin), both operations rounded.  counts int32 [k] = the clusters' sizes. */
+int grl_silhouette_finish(float* a, float* bmin, const int32_t* labels, const int32_t* counts, int n, int k, float* s,
+                          void* stream);
+/* rinv[i] = 1.0f / sqrtf(sq[i]) (sq = grl_row_sqnorm), both correctly rounded: the factors of the cosine form */
+int grl_silhouette_rinv(const float* sq, int n, float* rinv, void* stream);
 
 /* ---- query expansion / database-side augmentation (expand.hip, engine.expand_from_lists / expand_features) ----
  * out[i] = (x[i] + sum_p w_p * bank[j_p]) / (1 + sum_p w_p): a gather and a weighted sum over feature rows, without
