@@ -182,6 +182,8 @@ _SIGNATURES = {
                              C.c_int),
     'grl_silhouette_finish': ([_fp, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp], C.c_int),
     'grl_silhouette_rinv': ([_fp, C.c_int, _fp, _fp], C.c_int),
+    'grl_hdbscan_minedge_block': ([_fp, _i64] + [C.c_int] * 5 + [_fp] * 5 + [_fp], C.c_int),
+    'grl_hdbscan_cosine_block': ([_fp, _i64] + [C.c_int] * 5 + [_fp, _fp], C.c_int),
     'grl_expand_rows': ([_fp, _i64, _fp, _i64, _fp, _fp, _i64] + [C.c_int] * 7 + [_fp, _i64, _fp], C.c_int),
     'grl_verify_fold': ([_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
     'grl_verify_rows': ([_fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, _fp],

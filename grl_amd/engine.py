@@ -2843,3 +2843,409 @@ def cluster_select(xf, eps_list, min_samples=1, metric='cosine', score_metric=No
     if best is None:
         raise ValueError('cluster_select: no eps of %r gives 2 or more clusters with a finite score' % (eps_list,))
     return best[2], rows
+
+
+# ----------------------------------------------------------------------------
+# HDBSCAN: the mutual-reachability minimum spanning forest over the distance GEMM's column blocks and the tree cut on
+# its n - 1 edges (hdbscan.hip)
+# ----------------------------------------------------------------------------
+HDBSCAN_LAMBDA_FLOOR = 2.0 ** -126         # lambda = 1 / max(w, floor): an edge of weight 0 has a finite lambda
+HDBSCAN_METHODS = ('eom', 'leaf')
+
+
+class Hdbscan(object):
+    """The result of ``hdbscan`` / ``hdbscan_matrix`` / ``hdbscan_from_mst``:
+
+      labels       int64 device [n]: cluster id 0, 1, .. in ascending order of each cluster's smallest sample index; -1 = noise
+      n_clusters, n_noise
+      core_dist    float32 device [n]: the core distances (None from ``hdbscan_from_mst``)
+      mst          (lo int32, hi int32, w float32) device [E]: the forest's edges, lo < hi, sorted by (w, lo, hi)
+      stabilities  float64 numpy [n_clusters]: the stability of every selected cluster, in label order
+      rounds       Boruvka rounds (passes over the distance blocks) the forest took; n_dropped: candidate edges dropped
+                   because they would have closed a cycle (0 for a symmetric distance); both None from ``hdbscan_from_mst``
+      min_cluster_size, min_samples, metric, method: the arguments of the call
+      pair_scores(pids), centroids(xf, reduce='unit'), silhouette(xf, metric=None, noise='singleton'): as ``Clustering``'s"""
+
+    def __init__(self, labels, n_clusters, n_noise, core_dist, mst, stabilities, rounds, n_dropped, min_cluster_size,
+                 min_samples, metric, method):
+        self.labels, self.n_clusters, self.n_noise = labels, n_clusters, n_noise
+        self.core_dist, self.mst, self.stabilities = core_dist, mst, stabilities
+        self.rounds, self.n_dropped = rounds, n_dropped
+        self.min_cluster_size, self.min_samples, self.metric, self.method = min_cluster_size, min_samples, metric, method
+
+    def pair_scores(self, pids):
+        """``Clustering.pair_scores``: a noise point is a cluster of its own."""
+        return _pair_scores(self.labels, self.n_clusters, pids)
+
+    def centroids(self, xf, reduce='unit'):
+        """``cluster_centroids(xf, labels, n_clusters, reduce)`` of the rows the labels were computed from."""
+        return cluster_centroids(xf, self.labels, self.n_clusters, reduce)
+
+    def silhouette(self, xf, metric=None, noise='singleton'):
+        """``silhouette(xf, labels, metric, noise)``; ``metric`` defaults to the feature metric of the call ('cosine'
+        for a result that has none)."""
+        if metric is None:
+            metric = self.metric if self.metric in ('cosine', 'euclidean') else 'cosine'
+        return silhouette(xf, self.labels, metric, noise)
+
+
+def _hdbscan_int(v, lo, hi, what, name):
+    import numbers
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= hi:
+        raise ValueError('%s: %s must be an integer in %d..%d (got %r)' % (what, name, lo, hi, v))
+    return int(v)
+
+
+def _hdbscan_method(method, what):
+    if method not in HDBSCAN_METHODS:
+        raise ValueError("%s: method must be 'eom' or 'leaf' (got %r)" % (what, method))
+
+
+def _hdbscan_args(min_cluster_size, min_samples, method, what):
+    """(min_cluster_size, min_samples) as ints: the checks that need neither the device nor n."""
+    mcs = _hdbscan_int(min_cluster_size, 2, 2 ** 31 - 1, what, 'min_cluster_size')
+    ms = mcs if min_samples is None else min_samples
+    if min_samples is None and ms > SEARCH_K_MAX:
+        raise ValueError('%s: min_samples defaults to min_cluster_size = %d, beyond %d; give min_samples' %
+                         (what, ms, SEARCH_K_MAX))
+    ms = _hdbscan_int(ms, 1, SEARCH_K_MAX, what, 'min_samples')
+    _hdbscan_method(method, what)
+    return mcs, ms
+
+
+def _hdbscan_min_samples_n(ms, n, what):
+    if n >= 2 and ms > n:
+        raise ValueError('%s: min_samples must be an integer in 1..min(n, %d) = %d (got %r)'
+                         % (what, SEARCH_K_MAX, min(n, SEARCH_K_MAX), ms))
+
+
+def _hdbscan_core_dist(blocks, n, min_samples, rinv):
+    """The core distances float32 device [n]: one pass over the blocks into ``search``'s running top-min_samples lists
+    (the cosine form applied to a block in place before it is ranked), the sample itself taken out."""
+    dev = blocks.qf.device
+    if min_samples == 1:
+        return torch.zeros(n, dtype=torch.float32, device=dev)
+    k = min_samples
+    run_key = torch.full((n, k), -1, dtype=torch.int64, device=dev)
+    run_val = torch.full((n, k), float('inf'), dtype=torch.float32, device=dev)
+    for c0, c1 in blocks.spans:
+        d = blocks.block(c0, c1)
+        if rinv is not None:
+            _call('grl_hdbscan_cosine_block', ptr(d), d.stride(0), n, n, 0, c0, c1 - c0, ptr(rinv))
+        _call('grl_topk_block', ptr(d), d.stride(0), None, 0, n, c1 - c0, c0, k, ptr(run_key), ptr(run_val))
+    idx = run_key & 0xffffffff
+    own = (idx == torch.arange(n, device=dev).unsqueeze(1)) & (torch.arange(k, device=dev) < k - 1).unsqueeze(0)
+    # the sample is in its list before the last place: the last entry stays; otherwise the last one goes
+    return torch.where(own.any(1), run_val[:, k - 1], run_val[:, k - 2]).contiguous()
+
+
+def _mst_blocks(blocks, n, min_samples, rinv):
+    """``mutual_reachability_mst`` over any block source (``spans``, ``block(c0, c1)`` -> the [n, c1 - c0] columns of
+    the n x n distance matrix, ``qf``); ``rinv``: the factors of the cosine form when the blocks hold -dot."""
+    import numpy as np
+    dev = blocks.qf.device
+    prinv = ptr(rinv) if rinv is not None else None
+    core = _hdbscan_core_dist(blocks, n, min_samples, rinv)
+    # Boruvka rounds: one pass per round folds the blocks into each row's lightest outgoing edge; the per-component
+    # minimum, the union-find and the new component ids run on the host over 2n read-back words
+    comp = np.arange(n, dtype=np.int32)
+    comp_d = torch.from_numpy(comp).to(dev)
+    best_w = torch.empty(n, dtype=torch.float32, device=dev)
+    best_j = torch.empty(n, dtype=torch.int32, device=dev)
+    live = np.isfinite(core.cpu().numpy())
+    parent = list(range(n))                                  # union-find over the samples (a list: scalar access)
+
+    def find(a):
+        root = a
+        while parent[root] != root:
+            root = parent[root]
+        while parent[a] != root:
+            parent[a], a = root, parent[a]
+        return root
+    cap = max(n - 1, 1).bit_length() + 1                     # ceil(log2 n) + 1
+    e_lo, e_hi, e_w = [], [], []
+    rounds = n_dropped = n_edges = 0
+    n_live = int(live.sum())
+    while n_live - n_edges > 1:                              # more than one component among the samples with a core distance
+        if rounds >= cap:
+            raise RuntimeError('mutual_reachability_mst: the forest did not settle in %d rounds' % cap)
+        rounds += 1
+        for c0, c1 in blocks.spans:
+            d = blocks.block(c0, c1)
+            _call('grl_hdbscan_minedge_block', ptr(d), d.stride(0), n, n, 0, c0, c1 - c0, ptr(core), ptr(comp_d), prinv,
+                  ptr(best_w), ptr(best_j))
+        bw, bj = best_w.cpu().numpy(), best_j.cpu().numpy().astype(np.int64)
+        rows = np.flatnonzero(bj >= 0)
+        if rows.size == 0:
+            break
+        lo, hi, w, c = np.minimum(rows, bj[rows]), np.maximum(rows, bj[rows]), bw[rows], comp[rows]
+        order = np.lexsort((hi, lo, w, c))                   # by component, then the edges' total order
+        cs = c[order]
+        pick = order[np.concatenate(([True], cs[1:] != cs[:-1]))]       # every component's lightest outgoing edge
+        pick = pick[np.lexsort((hi[pick], lo[pick], w[pick]))]
+        plo, phi = lo[pick], hi[pick]
+        twice = np.concatenate(([False], (plo[1:] == plo[:-1]) & (phi[1:] == phi[:-1])))     # both ends' components chose it
+        pick, plo, phi = pick[~twice], plo[~twice], phi[~twice]
+        took = []
+        for k, (a, b) in enumerate(zip(plo.tolist(), phi.tolist())):
+            ra, rb = find(a), find(b)
+            if ra == rb:
+                n_dropped += 1
+                continue
+            parent[max(ra, rb)] = min(ra, rb)
+            took.append(k)
+        e_lo.append(plo[took]); e_hi.append(phi[took]); e_w.append(w[pick][took])
+        n_edges += len(took)
+        up = np.asarray(parent, dtype=np.int64)
+        while True:                                          # every sample's root: pointer jumping
+            nxt = up[up]
+            if np.array_equal(nxt, up):
+                break
+            up = nxt
+        comp = up.astype(np.int32)
+        comp_d = torch.from_numpy(comp).to(dev)
+    lo = np.concatenate(e_lo).astype(np.int32) if e_lo else np.empty(0, dtype=np.int32)
+    hi = np.concatenate(e_hi).astype(np.int32) if e_hi else np.empty(0, dtype=np.int32)
+    w = np.concatenate(e_w).astype(np.float32) if e_w else np.empty(0, dtype=np.float32)
+    order = np.lexsort((hi, lo, w))
+    out = tuple(torch.from_numpy(np.ascontiguousarray(a[order])).to(dev) for a in (lo, hi, w))
+    return out + (core, {'rounds': rounds, 'n_dropped': n_dropped})
+
+
+def _mst_empty(n, dev):
+    return (torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+            torch.empty(0, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float32, device=dev),
+            {'rounds': 0, 'n_dropped': 0})
+
+
+def mutual_reachability_mst(xf, min_samples, metric='cosine', block_cols=None, block_bytes=None):
+    """The minimum spanning forest of the mutual-reachability graph of the rows of ``xf`` [n, d], without the n x n
+    matrix: ``(lo int32 [E], hi int32 [E], w float32 [E], core float32 [n], info)`` on the device, lo < hi, the edges
+    sorted by (w, lo, hi); ``info`` = {'rounds', 'n_dropped'}.  Distance of a pair {lo < hi}: 'euclidean' = the
+    ``pairwise_distance_tensor(xf, xf)`` entry; 'cosine' = 1 - cos of the rows, which need not be unit, as
+    max(0, 1 + (D * rinv[lo]) * rinv[hi]) with D = ``cosin_dist(xf, xf)`` and rinv = 1 / sqrt(grl_row_sqnorm), the
+    smaller index first, so that both rows of a pair see the same bits.  core[i] = the distance to the
+    (min_samples - 1)-th nearest other sample (the sample counts as its own neighbour at distance 0: scikit-learn's
+    convention): row i of ``search``'s top-min_samples list with the entry of index i deleted, or the last entry if it
+    is not there; +0 for min_samples = 1.  Edge weight w = max(dist, core[lo], core[hi]); a sample whose core distance
+    is not finite has no edges, a w that is NaN or +inf is no edge.  Under the strict total order (w, lo, hi) the forest
+    is unique.  It is built by Boruvka rounds: one pass over ``_ColumnBlocks``' distance blocks per round, each folded
+    by grl_hdbscan_minedge_block into every row's lightest edge out of its component; the per-component minimum and
+    the union-find run on the host over the 2n read-back words, n component ids go back.  At most ceil(log2 n) + 1
+    rounds (RuntimeError beyond).  The same bits on every run and for every block width.  Not sharded: under
+    torch.distributed every rank computes the full, identical result.  ValueError: a ``verify_metric``, an unknown
+    metric, ``min_samples`` outside 1..min(n, 1024) or not an integer."""
+    _cluster_metric(metric, 'mutual_reachability_mst')
+    min_samples = _hdbscan_int(min_samples, 1, SEARCH_K_MAX, 'mutual_reachability_mst', 'min_samples')
+    if not torch.is_tensor(xf) or xf.dim() < 2:
+        raise ValueError('mutual_reachability_mst: xf must be a tensor [n, d] (got %s)'
+                         % (tuple(xf.shape) if torch.is_tensor(xf) else type(xf).__name__,))
+    n = xf.shape[0]
+    _hdbscan_min_samples_n(min_samples, n, 'mutual_reachability_mst')
+    require_device(xf, 'xf')
+    if n <= 1:                             # (nothing to launch)
+        return _mst_empty(n, xf.device)
+    xf = _pad_features(_kmeans_rows(xf, 'mutual_reachability_mst'))
+    blocks = _ColumnBlocks(xf, xf, metric, block_cols, block_bytes)
+    rinv = None
+    if metric == 'cosine':
+        d = xf.shape[1]
+        sq, rinv = _new((n,), xf), _new((n,), xf)
+        _call('grl_row_sqnorm', ptr(xf), ptr(sq), n, d, d)
+        _call('grl_silhouette_rinv', ptr(sq), n, ptr(rinv))
+    return _mst_blocks(blocks, n, min_samples, rinv)
+
+
+def _hdbscan_cut(lo, hi, w, n, mcs, method):
+    """The cut of DESIGN.md 4x on the host in float64: (labels int64 [n], n_clusters, stabilities float64 [n_clusters])
+    from the forest's edges in their sorted order."""
+    import numpy as np
+    m = len(lo)
+    uf = list(range(n))
+
+    def find(a):
+        root = a
+        while uf[root] != root:
+            root = uf[root]
+        while uf[a] != root:
+            uf[a], a = root, uf[a]
+        return root
+    # single-linkage dendrogram: merge k is node n + k, its children the two current tops
+    top = list(range(n))
+    left, right = [0] * m, [0] * m
+    size = [1] * n + [0] * m
+    for k in range(m):
+        a, b = find(lo[k]), find(hi[k])
+        if a == b:
+            raise ValueError('hdbscan_from_mst: the edges are not a forest (edge %d closes a cycle)' % k)
+        left[k], right[k] = top[a], top[b]
+        size[n + k] = size[top[a]] + size[top[b]]
+        r = min(a, b)
+        uf[max(a, b)] = r
+        top[r] = n + k
+    big = [top[r] for r in range(n) if uf[r] == r and size[top[r]] >= mcs]
+    # condensed tree, top-down; cluster ids are handed out parents first
+    birth, stab, cparent, kids, selectable = [], [], [], [], []
+
+    def new_cluster(lam, par, sel):
+        birth.append(lam); stab.append(0.0); cparent.append(par); kids.append([]); selectable.append(sel)
+        return len(birth) - 1
+    left_in = np.full(n, -1, dtype=np.int64)                # the cluster every point left
+
+    def leave(node, c):
+        todo = [node]
+        while todo:
+            v = todo.pop()
+            if v < n:
+                left_in[v] = c
+            else:
+                todo.append(left[v - n]); todo.append(right[v - n])
+    stack = [(t, new_cluster(0.0, -1, len(big) >= 2)) for t in big]
+    while stack:
+        node, c = stack.pop()
+        while node >= n:
+            k = node - n
+            lam = 1.0 / max(float(w[k]), HDBSCAN_LAMBDA_FLOOR)
+            a, b = left[k], right[k]
+            sa, sb = size[a], size[b]
+            if sa >= mcs and sb >= mcs:                      # a true split: two clusters are born
+                stab[c] += (sa + sb) * (lam - birth[c])
+                for ch in (a, b):
+                    cid = new_cluster(lam, c, True)
+                    kids[c].append(cid)
+                    stack.append((ch, cid))
+                break
+            if sa >= mcs or sb >= mcs:                       # the cluster goes on, the small side's points leave
+                small, node = (b, a) if sa >= mcs else (a, b)
+                stab[c] += size[small] * (lam - birth[c])
+                leave(small, c)
+                continue
+            stab[c] += (sa + sb) * (lam - birth[c])          # the cluster dissolves
+            leave(node, c)
+            break
+    ncl = len(birth)
+    chosen = [False] * ncl
+    if method == 'leaf':
+        chosen = [selectable[c] and not kids[c] for c in range(ncl)]
+    else:
+        value = list(stab)
+        for c in range(ncl - 1, -1, -1):
+            if not kids[c]:
+                chosen[c] = selectable[c]
+                continue
+            tot = value[kids[c][0]] + value[kids[c][1]]
+            if not selectable[c] or tot > stab[c]:
+                value[c] = tot
+            else:
+                chosen[c] = True
+    at = [-1] * ncl                                          # the selected cluster at or above c
+    for c in range(ncl):
+        up = at[cparent[c]] if cparent[c] >= 0 else -1
+        at[c] = up if up >= 0 else (c if chosen[c] else -1)
+    at = np.asarray(at + [-1], dtype=np.int64)               # (left_in == -1 reads the appended -1)
+    raw = at[left_in]
+    labels = np.full(n, -1, dtype=np.int64)
+    keep = raw >= 0
+    ids, first = np.unique(raw[keep], return_index=True)     # first = each cluster's smallest sample index (in keep)
+    rank = np.empty(ids.size, dtype=np.int64)
+    rank[np.argsort(first, kind='stable')] = np.arange(ids.size)
+    labels[keep] = rank[np.searchsorted(ids, raw[keep])]
+    stabilities = np.zeros(ids.size, dtype=np.float64)
+    stabilities[rank] = np.asarray([stab[c] for c in ids.tolist()], dtype=np.float64)
+    return labels, int(ids.size), stabilities
+
+
+def _hdbscan_result(mst, core, info, n, mcs, ms, metric, method, dev):
+    import numpy as np
+    lo, hi, w = (t.cpu().numpy() for t in mst)
+    labels, n_clusters, stabilities = _hdbscan_cut(lo.tolist(), hi.tolist(), w.astype(np.float64), n, mcs, method)
+    return Hdbscan(torch.from_numpy(labels).to(dev), n_clusters, int((labels < 0).sum()), core, mst, stabilities,
+                   info.get('rounds'), info.get('n_dropped'), mcs, ms, metric, method)
+
+
+def hdbscan_from_mst(lo, hi, w, n, min_cluster_size, method='eom'):
+    """HDBSCAN's labels from a mutual-reachability forest (``mutual_reachability_mst``'s device arrays lo int32, hi
+    int32, w float32 [E]) as an ``Hdbscan``.  The forest depends on ``min_samples`` only, so another
+    ``min_cluster_size`` or ``method`` costs no GPU pass.  The cut runs on the host in float64 over the E <= n - 1
+    edges, in the edges' order (w, lo, hi): the single-linkage dendrogram by union-find; condensed top-down at lambda =
+    1 / max(w, 2^-126) -- two children of at least ``min_cluster_size`` samples are two new clusters, one such child
+    goes on as the same cluster while the other's points leave, none dissolves the cluster; stability = the sum over
+    leaving points and child clusters of size * (lambda - lambda_birth); 'eom' selects bottom-up (children whose total
+    exceeds the parent's own stability replace it), 'leaf' the leaves.  A forest of one component of at least
+    ``min_cluster_size`` samples has that component as the never-selected root (scikit-learn's
+    allow_single_cluster=False); with two or more, each is a selectable cluster born at lambda = 0; smaller components
+    are noise.  ValueError: arrays that are not E edges with 0 <= lo < hi < n, edges that close a cycle,
+    ``min_cluster_size`` < 2, an unknown method."""
+    import numbers
+    import numpy as np
+    mcs = _hdbscan_int(min_cluster_size, 2, 2 ** 31 - 1, 'hdbscan_from_mst', 'min_cluster_size')
+    _hdbscan_method(method, 'hdbscan_from_mst')
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 0:
+        raise ValueError('hdbscan_from_mst: n must be an integer >= 0 (got %r)' % (n,))
+    n = int(n)
+    for t, dt, what in ((lo, torch.int32, 'lo'), (hi, torch.int32, 'hi'), (w, torch.float32, 'w')):
+        if not (torch.is_tensor(t) and t.dtype == dt and t.dim() == 1 and t.numel() == lo.numel()):
+            raise ValueError('hdbscan_from_mst: %s must be a 1-d %s device tensor, one entry per edge' % (what, dt))
+    if not (lo.is_cuda and hi.is_cuda and w.is_cuda):
+        raise _lib.GrlHipError('lo, hi and w must live on a HIP device (got %s): grl_amd has no CPU path' % lo.device)
+    a, b, ww = lo.cpu().numpy(), hi.cpu().numpy(), w.cpu().numpy()
+    if a.size and not ((a >= 0) & (a < b) & (b < n)).all():
+        raise ValueError('hdbscan_from_mst: every edge needs 0 <= lo < hi < n = %d' % n)
+    if np.isnan(ww).any():
+        raise ValueError('hdbscan_from_mst: a NaN weight is no edge')
+    order = np.lexsort((b, a, ww))
+    mst = tuple(t[torch.from_numpy(order).to(lo.device)] for t in (lo, hi, w))
+    return _hdbscan_result(mst, None, {}, n, mcs, None, None, method, lo.device)
+
+
+def hdbscan(xf, min_cluster_size=5, min_samples=None, metric='cosine', method='eom', block_cols=None, block_bytes=None):
+    """HDBSCAN of the rows of ``xf`` [n, d] as an ``Hdbscan``: the density clustering that needs no ``eps`` and copes
+    with identities of different spread.  ``hdbscan_from_mst(*mutual_reachability_mst(xf, min_samples, metric, ..),
+    n, min_cluster_size, method)``; ``min_samples=None`` means ``min_cluster_size``.  No n x n matrix exists on the
+    device or the host: 1 + rounds passes over the distance GEMM's column blocks (rounds <= ceil(log2 n) + 1), and the
+    host sees the n - 1 edges and n labels.  On distances without ties among the mutual-reachability weights the
+    partition is scikit-learn's HDBSCAN(metric='precomputed', allow_single_cluster=False); with ties the dendrogram
+    follows the edges' order (w, lo, hi) where scikit-learn's follows its sort.  n = 0 and n = 1 give an
+    empty / all-noise result without a launch.  Not sharded.  ValueError: a ``verify_metric``, an unknown metric or
+    method, ``min_cluster_size`` < 2, ``min_samples`` outside 1..min(n, 1024), bool or non-integer arguments."""
+    _cluster_metric(metric, 'hdbscan')
+    mcs, ms = _hdbscan_args(min_cluster_size, min_samples, method, 'hdbscan')
+    lo, hi, w, core, info = mutual_reachability_mst(xf, ms, metric, block_cols, block_bytes)
+    return _hdbscan_result((lo, hi, w), core, info, xf.shape[0], mcs, ms, metric, method, lo.device)
+
+
+def hdbscan_matrix(distmat, min_cluster_size=5, min_samples=None, method='eom', block_cols=None):
+    """``hdbscan`` on an [n, n] float32 distance matrix that already lives on the device, the entries used as they are;
+    rows may be strided (a column slice of a wider matrix is read in place), and ``block_cols`` cuts it into column
+    slices that are read in place too.  The matrix must be symmetric bit for bit: a row pass sees only row i's view
+    of a pair, and the two views have to agree on the edge.  ``metric`` of the result is 'precomputed'.  ValueError:
+    not square, not float32, not symmetric, and ``hdbscan``'s."""
+    mcs, ms = _hdbscan_args(min_cluster_size, min_samples, method, 'hdbscan_matrix')
+    if not torch.is_tensor(distmat) or distmat.dim() != 2 or distmat.shape[0] != distmat.shape[1]:
+        raise ValueError('hdbscan_matrix: distmat must be square [n, n] (got %s)'
+                         % (tuple(distmat.shape) if torch.is_tensor(distmat) else type(distmat).__name__,))
+    if distmat.dtype != torch.float32:
+        raise ValueError('hdbscan_matrix: distmat must be float32 (got %s)' % distmat.dtype)
+    n = distmat.shape[0]
+    _hdbscan_min_samples_n(ms, n, 'hdbscan_matrix')
+    require_device(distmat, 'distmat')
+    dev = distmat.device
+    if n <= 1:
+        lo, hi, w, core, info = _mst_empty(n, dev)
+        return _hdbscan_result((lo, hi, w), core, info, n, mcs, ms, 'precomputed', method, dev)
+    if distmat.stride(1) != 1 or distmat.stride(0) < n:
+        distmat = distmat.contiguous()
+    bits = distmat.view(torch.int32)
+    if not torch.equal(bits, bits.t()):
+        raise ValueError('hdbscan_matrix: distmat must be symmetric bit for bit (a row pass sees one view of a pair)')
+    width = n if block_cols is None else max(1, min(int(block_cols), n))
+
+    class _Slices(object):                          # a block source of column slices of the matrix itself
+        spans = [(c, min(c + width, n)) for c in range(0, n, width)]
+        qf = distmat
+
+        @staticmethod
+        def block(c0, c1):
+            return distmat[:, c0:c1]
+    lo, hi, w, core, info = _mst_blocks(_Slices, n, ms, None)
+    return _hdbscan_result((lo, hi, w), core, info, n, mcs, ms, 'precomputed', method, dev)

@@ -160,6 +160,31 @@ def _kmeans_report(knob, gf, ids, path, sil=None):
     return lines
 
 
+def _hdbscan_report(knob, gf, ids, path, sil=None):
+    """GRL_EVAL_HDBSCAN: HDBSCAN of the query-prepended gallery ``gf`` by cosine (engine.hdbscan) -- the two lines
+    ``_report`` prints after GRL_EVAL_KMEANS's, and ``path + 'hdbscan.json'`` (rank 0 alone writes; strict JSON, no
+    edges).  ``knob`` = (min_cluster_size, min_samples or None, method).  ``sil`` (GRL_EVAL_SILHOUETTE): a third line and
+    the JSON's "silhouette" entry (``_silhouette_report``)."""
+    import json
+    mcs, ms, method = knob
+    n = int(gf.size(0))
+    hd = engine.hdbscan(gf, mcs, ms, 'cosine', method)
+    scores = hd.pair_scores(ids[1])
+    lines = ['HDBSCAN: {} clusters ({} noise of {}) at min_cluster_size = {}, min_samples = {}, {} ({} rounds)'.format(
+                 hd.n_clusters, hd.n_noise, n, hd.min_cluster_size, hd.min_samples, hd.method, hd.rounds),
+             'Pairwise precision: {:.2%}  recall: {:.2%}  F1: {:.2%}  ARI: {:.4f}'.format(
+                 scores['precision'], scores['recall'], scores['f1'], scores['ari'])]
+    js = {'min_cluster_size': hd.min_cluster_size, 'min_samples': hd.min_samples, 'method': hd.method,
+          'metric': 'cosine', 'n': n, 'n_clusters': hd.n_clusters, 'n_noise': hd.n_noise, 'n_edges': int(hd.mst[0].numel()),
+          'rounds': hd.rounds, 'n_dropped': hd.n_dropped, 'stabilities': hd.stabilities.tolist(),
+          'pair_scores': scores, 'labels': hd.labels.cpu().tolist()}
+    lines += _silhouette_report(sil, gf, hd.labels, js)
+    if grl_dist._rank_world(None, None)[0] == 0:
+        with open((path or '') + 'hdbscan.json', 'w') as fh:
+            json.dump(js, fh, allow_nan=False)
+    return lines
+
+
 def cosin_dist(qf, gf):
     return engine.cosin_dist(qf, gf)
 
@@ -285,6 +310,31 @@ def parse_kmeans_knob(name, value):
     if (k != 'ids' and not 1 <= k <= 2 ** 31 - 1) or not 1 <= max_iter <= 2 ** 31 - 1 or seed < 0:
         raise ValueError('%s: k and max_iter must be >= 1 and seed >= 0 (got %r)' % (name, value))
     return k, max_iter, seed
+
+
+def parse_hdbscan_knob(name, value):
+    """``GRL_EVAL_HDBSCAN``: unset or empty -> None (off); "min_cluster_size", "min_cluster_size,min_samples" or
+    "min_cluster_size,min_samples,method" -> (min_cluster_size, min_samples or None, method) with an integer
+    min_cluster_size >= 2, an integer min_samples in 1..1024 (default None: min_cluster_size) and method "eom" (the
+    default) or "leaf" (engine.hdbscan).  Anything else is a ValueError that names the variable."""
+    if value is None or not value.strip():
+        return None
+    parts = [p.strip() for p in value.split(',')]
+    try:
+        if len(parts) > 3:
+            raise ValueError
+        mcs = int(parts[0])
+        ms = int(parts[1]) if len(parts) >= 2 else None
+        method = parts[2] if len(parts) == 3 else 'eom'
+    except ValueError:
+        raise ValueError('%s must be "min_cluster_size", "min_cluster_size,min_samples" or '
+                         '"min_cluster_size,min_samples,method" with integers and method "eom" or "leaf" (got %r)'
+                         % (name, value))
+    if not 2 <= mcs <= 2 ** 31 - 1 or (ms is not None and not 1 <= ms <= engine.SEARCH_K_MAX) \
+            or method not in engine.HDBSCAN_METHODS:
+        raise ValueError('%s: min_cluster_size must be >= 2, min_samples in 1..%d and method "eom" or "leaf" (got %r)'
+                         % (name, engine.SEARCH_K_MAX, value))
+    return mcs, ms, method
 
 
 def parse_silhouette_knob(name, value):
@@ -444,12 +494,20 @@ class ATTEvaluator(object):
             raise ValueError('GRL_EVAL_KMEANS cannot be combined with GRL_EVAL_METRIC=%s: k-means runs by cosine on '
                              'the routes that rank by cosine (unset one of them)'
                              % os.environ['GRL_EVAL_METRIC'].strip())
+        # density clustering without an eps, off by default: HDBSCAN of the query-prepended gallery by cosine
+        # (engine.hdbscan), printed after the k-means lines and stored in path + 'hdbscan.json'
+        hdbscan_knob = parse_hdbscan_knob('GRL_EVAL_HDBSCAN', os.environ.get('GRL_EVAL_HDBSCAN'))
+        if hdbscan_knob is not None and knob is not None:
+            raise ValueError('GRL_EVAL_HDBSCAN cannot be combined with GRL_EVAL_METRIC=%s: HDBSCAN runs by cosine on '
+                             'the routes that rank by cosine (unset one of them)'
+                             % os.environ['GRL_EVAL_METRIC'].strip())
         # the label-free score of those clusterings, off by default (engine.silhouette): a third line of each report and
         # a "silhouette" entry of its JSON file
         sil_knob = parse_silhouette_knob('GRL_EVAL_SILHOUETTE', os.environ.get('GRL_EVAL_SILHOUETTE'))
-        if sil_knob is not None and cluster_knob is None and jaccard_knob is None and kmeans_knob is None:
-            raise ValueError('GRL_EVAL_SILHOUETTE scores the labels of GRL_EVAL_CLUSTER, GRL_EVAL_CLUSTER_JACCARD or '
-                             'GRL_EVAL_KMEANS: set one of them too (or unset GRL_EVAL_SILHOUETTE)')
+        if sil_knob is not None and cluster_knob is None and jaccard_knob is None and kmeans_knob is None \
+                and hdbscan_knob is None:
+            raise ValueError('GRL_EVAL_SILHOUETTE scores the labels of GRL_EVAL_CLUSTER, GRL_EVAL_CLUSTER_JACCARD, '
+                             'GRL_EVAL_KMEANS or GRL_EVAL_HDBSCAN: set one of them too (or unset GRL_EVAL_SILHOUETTE)')
         qf, q_pids, q_camids = self.extract_feature(query_loader)
         print('Done, obtained {}-by-{} matrix'.format(qf.size(0), qf.size(1)))
         gf, g_pids, g_camids = self.extract_feature(gallery_loader)
@@ -477,14 +535,16 @@ class ATTEvaluator(object):
         roc_lines = ()
 
         def extra(lines, cosine_roc=None):
-            """the route's ROC lines, then GRL_EVAL_CLUSTER's, GRL_EVAL_CLUSTER_JACCARD's and GRL_EVAL_KMEANS's (by
-            cosine or by the Jaccard distance of the features, whatever the route ranks by)"""
+            """the route's ROC lines, then GRL_EVAL_CLUSTER's, GRL_EVAL_CLUSTER_JACCARD's, GRL_EVAL_KMEANS's and
+            GRL_EVAL_HDBSCAN's (by cosine or by the Jaccard distance of the features, whatever the route ranks by)"""
             if cluster_knob is not None:
                 lines = tuple(lines) + tuple(_cluster_report(cluster_knob, qf, gf, ids, path, cosine_roc, sil_knob))
             if jaccard_knob is not None:
                 lines = tuple(lines) + tuple(_cluster_jaccard_report(jaccard_knob, gf, ids, path, sil_knob))
             if kmeans_knob is not None:
                 lines = tuple(lines) + tuple(_kmeans_report(kmeans_knob, gf, ids, path, sil_knob))
+            if hdbscan_knob is not None:
+                lines = tuple(lines) + tuple(_hdbscan_report(hdbscan_knob, gf, ids, path, sil_knob))
             return lines
         if visual:
             self._visualize(query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, rerank)

@@ -42,7 +42,8 @@ const char* grl_last_error(void);
  * re-ranking entry points grl_rrs_*, the CSR / CSC assembly of its sharded form (grl_rrs_expand_rows, grl_rrs_scan,
  * grl_rrs_place, grl_rrs_transpose) among them, grl_topk_block_filtered, grl_expand_rows, the grl_verify_* entry points,
  * grl_pair_hist_block, the clustering entry points grl_cluster_*, the k-means entry points grl_kmeans_* /
- * grl_segment_rowsum, grl_jaccard_edges and the silhouette entry points grl_silhouette_*. */
+ * grl_segment_rowsum, grl_jaccard_edges, the silhouette entry points grl_silhouette_* and the HDBSCAN entry points
+ * grl_hdbscan_*. */
 #define GRL_ABI_VERSION 10
 int grl_abi_version(void);
 /* `waiter` (a hipStream_t) waits for everything enqueued on `signaler` so far: hipEventRecord + hipStreamWaitEvent on a
@@ -741,6 +742,28 @@ int grl_silhouette_finish(float* a, float* bmin, const int32_t* labels, const in
                           void* stream);
 /* rinv[i] = 1.0f / sqrtf(sq[i]) (sq = grl_row_sqnorm), both correctly rounded: the factors of the cosine form */
 int grl_silhouette_rinv(const float* sq, int n, float* rinv, void* stream);
+
+/* ---- HDBSCAN: the mutual-reachability minimum spanning forest over column blocks (hdbscan.hip,
+ * engine.mutual_reachability_mst / hdbscan / hdbscan_matrix) ----
+ * ``d`` [nrows][ld] (ncols used) is a block of the n x n distance matrix: row r is sample row0 + r, column c is sample
+ * c0 + c.  Distance of the pair {lo < hi}: the entry as it is (rinv = NULL; the matrix must be symmetric bit for bit),
+ * or, with rinv [n] (grl_silhouette_rinv) given, the cosine form of d = -dot made symmetric: v = (d * rinv[lo]) *
+ * rinv[hi], the smaller index first whichever of the two is the row, dist = 1.0f + v, dist < 0 ? 0 : dist (a NaN stays).
+ * Edge weight: w = dist; if (core[lo] > w) w = core[lo]; if (core[hi] > w) w = core[hi], with core [n] the core
+ * distances.  A sample whose core distance is not finite has no edges, and a w that is NaN or +inf is no edge.
+ * One Boruvka round: for every row i, (best_w[i], best_j[i]) = the smallest (w, j) -- w by float <, then j -- over the
+ * columns j with comp[j] != comp[i] (comp int32 [n]: the component ids; this skips j == i), or (+inf, -1) when there is
+ * none.  The block with c0 == 0 starts the pair, every later block folds into it, so the blocks of a round are enqueued
+ * in ascending order on one stream, every row at most once per call; the result does not depend on the cuts.  One wave
+ * per row, no atomics.  GRL_EINVAL, before any launch: a null pointer (rinv may be NULL), a negative size, ncols < 1,
+ * ld < ncols, row0 + nrows > n or c0 + ncols > n. */
+int grl_hdbscan_minedge_block(const float* d, int64_t ld, int n, int nrows, int row0, int c0, int ncols,
+                              const float* core, const int32_t* comp, const float* rinv, float* best_w, int32_t* best_j,
+                              void* stream);
+/* The cosine form above applied to a block of d = -dot in place (before grl_topk_block ranks it for the core
+ * distances): d[r][c] = max(0, 1.0f + (d[r][c] * rinv[lo]) * rinv[hi]) for the pair {row0 + r, c0 + c}. */
+int grl_hdbscan_cosine_block(float* d, int64_t ld, int n, int nrows, int row0, int c0, int ncols, const float* rinv,
+                             void* stream);
 
 /* ---- query expansion / database-side augmentation (expand.hip, engine.expand_from_lists / expand_features) ----
  * out[i] = (x[i] + sum_p w_p * bank[j_p]) / (1 + sum_p w_p): a gather and a weighted sum over feature rows, without
