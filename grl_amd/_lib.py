@@ -184,6 +184,13 @@ _SIGNATURES = {
     'grl_silhouette_rinv': ([_fp, C.c_int, _fp, _fp], C.c_int),
     'grl_hdbscan_minedge_block': ([_fp, _i64] + [C.c_int] * 5 + [_fp] * 5 + [_fp], C.c_int),
     'grl_hdbscan_cosine_block': ([_fp, _i64] + [C.c_int] * 5 + [_fp, _fp], C.c_int),
+    'grl_tsne_square_block': ([_fp, _i64, C.c_int, C.c_int, _fp], C.c_int),
+    'grl_tsne_perplexity': ([_fp, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp, _fp], C.c_int),
+    'grl_tsne_joint': ([_fp, _fp, C.c_int, _fp, _fp, _fp, C.c_int, C.c_float] + [_fp] * 4 + [_fp], C.c_int),
+    'grl_tsne_repulsion': ([_fp, _fp, C.c_int, _fp, _fp, _fp], C.c_int),
+    'grl_tsne_z': ([_fp, C.c_int, _fp, _fp], C.c_int),
+    'grl_tsne_update': ([_fp] * 5 + [C.c_int, C.c_float] + [_fp] * 6 + [C.c_float, C.c_float, _fp], C.c_int),
+    'grl_tsne_kl': ([_fp] * 5 + [C.c_int, _fp, _fp, _fp], C.c_int),
     'grl_expand_rows': ([_fp, _i64, _fp, _i64, _fp, _fp, _i64] + [C.c_int] * 7 + [_fp, _i64, _fp], C.c_int),
     'grl_verify_fold': ([_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
     'grl_verify_rows': ([_fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, _fp],

@@ -3249,3 +3249,327 @@ def hdbscan_matrix(distmat, min_cluster_size=5, min_samples=None, method='eom', 
             return distmat[:, c0:c1]
     lo, hi, w, core, info = _mst_blocks(_Slices, n, ms, None)
     return _hdbscan_result((lo, hi, w), core, info, n, mcs, ms, 'precomputed', method, dev)
+
+
+# ----------------------------------------------------------------------------
+# t-SNE map of a feature set (tsne.hip)
+# ----------------------------------------------------------------------------
+TSNE_METRICS = ('cosine', 'euclidean')
+
+
+class Tsne(object):
+    """The result of ``tsne`` / ``tsne_from_affinities``:
+
+      embedding      float32 device [n, 2]; the row of an isolated sample is NaN
+      kl             the Kullback-Leibler divergence sum P log(P Z / q) over the stored affinities at ``embedding``
+      n_iter         iterations run;  n_isolated: samples without affinities
+      perplexity, metric, seed (None for a given ``init``), learning_rate (the float that was used)
+      affinities     (row_ptr int64 [n + 1], col int32 [E], val float32 [E]): the joint affinities, a CSR on the device
+      beta           float32 device [n]: every sample's precision (None from ``tsne_from_affinities``)
+      isolated       bool device [n]
+      gains, update  float32 device [n, 2]: the optimiser's state after the last iteration"""
+
+    def __init__(self, embedding, kl, n_iter, n_isolated, perplexity, metric, seed, learning_rate, affinities, beta,
+                 isolated, gains, update):
+        self.embedding, self.kl, self.n_iter, self.n_isolated = embedding, kl, n_iter, n_isolated
+        self.perplexity, self.metric, self.seed, self.learning_rate = perplexity, metric, seed, learning_rate
+        self.affinities, self.beta, self.isolated, self.gains, self.update = affinities, beta, isolated, gains, update
+
+
+def _tsne_real(v, what, name):
+    import math
+    import numbers
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v):
+        raise ValueError('%s: %s must be a finite number (got %r)' % (what, name, v))
+    return float(v)
+
+
+def _tsne_rows(xf, perplexity, metric, what):
+    """The checks of ``tsne`` / ``tsne_affinities`` that need no device work: (n, K, perplexity as a float)."""
+    if isinstance(metric, VerifyMetric):
+        raise ValueError('%s: a verify_metric is the signed logit of modified query rows against gallery rows, not a '
+                         "distance between two samples of one set; embed by 'cosine' or 'euclidean'" % what)
+    if metric not in TSNE_METRICS:
+        raise ValueError("%s: metric must be 'cosine' or 'euclidean' (got %r)" % (what, metric))
+    if not (torch.is_tensor(xf) and xf.is_cuda and xf.dtype == torch.float32 and xf.dim() == 2):
+        raise ValueError('%s: xf must be a 2-d float32 tensor [n, d] on a HIP device (got %s)'
+                         % (what, '%s %s on %s' % (tuple(xf.shape), xf.dtype, xf.device) if torch.is_tensor(xf)
+                            else type(xf).__name__))
+    n = int(xf.shape[0])
+    if n < 3 or xf.shape[1] < 1:
+        raise ValueError('%s: needs n >= 3 samples of d >= 1 features (got %s)' % (what, tuple(xf.shape)))
+    perp = _tsne_real(perplexity, what, 'perplexity')
+    K = min(n - 1, int(3.0 * perp) + 1) if perp >= 1.0 else 0
+    if K + 1 > SEARCH_K_MAX:
+        raise ValueError('%s: perplexity = %r needs %d neighbours, search holds %d: perplexity must be below %d'
+                         % (what, perplexity, K, SEARCH_K_MAX - 1, (SEARCH_K_MAX - 1) // 3))
+    if not 1.0 <= perp < K:
+        raise ValueError('%s: perplexity must be a number in [1, K) with K = min(n - 1, floor(3 perplexity) + 1) = %d '
+                         'neighbours, or the target entropy cannot be reached (got %r for n = %d)' % (what, K, perplexity, n))
+    return n, K, perp
+
+
+def _tsne_optimiser(n_iter, learning_rate, early_exaggeration, exaggeration_iter, seed, init, n, what):
+    """The optimiser arguments checked without device work: (n_iter, lr or None for 'auto', alpha, switch, seed)."""
+    import numbers
+    for v, name, lo in ((n_iter, 'n_iter', 1), (exaggeration_iter, 'exaggeration_iter', 0)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < lo:
+            raise ValueError('%s: %s must be an integer >= %d (got %r)' % (what, name, lo, v))
+    lr = None
+    if not (isinstance(learning_rate, str) and learning_rate == 'auto'):
+        lr = _tsne_real(learning_rate, what, 'learning_rate')
+        if lr <= 0:
+            raise ValueError("%s: learning_rate must be 'auto' or a number > 0 (got %r)" % (what, learning_rate))
+    alpha = _tsne_real(early_exaggeration, what, 'early_exaggeration')
+    if alpha <= 0:
+        raise ValueError('%s: early_exaggeration must be > 0 (got %r)' % (what, early_exaggeration))
+    if torch.is_tensor(init):
+        if not (init.is_cuda and init.dtype == torch.float32 and tuple(init.shape) == (n, 2)):
+            raise ValueError('%s: an init tensor must be float32 [n, 2] = [%d, 2] on a HIP device (got %s %s on %s)'
+                             % (what, n, tuple(init.shape), init.dtype, init.device))
+        seed = None
+    elif isinstance(init, str) and init == 'random':
+        if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or seed < 0:
+            raise ValueError('%s: seed must be an integer >= 0 (got %r)' % (what, seed))
+        seed = int(seed)
+    else:
+        raise ValueError("%s: init must be 'random' or a float32 [n, 2] device tensor (got %r)" % (what, init))
+    return int(n_iter), lr, alpha, int(exaggeration_iter), seed
+
+
+def _tsne_csr(row_ptr, col, val, isolated, what, checked=False):
+    """A caller's CSR checked: the shapes and dtypes without device work, then (one read-back) that it is square and
+    that the columns ascend in every row.  Returns (n, isolated as uint8 or None)."""
+    for t, dt, name in ((row_ptr, torch.int64, 'row_ptr'), (col, torch.int32, 'col'), (val, torch.float32, 'val')):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.dim() == 1):
+            raise ValueError('%s: %s must be a 1-d %s tensor on a HIP device' % (what, name, dt))
+    n = row_ptr.numel() - 1
+    if n < 1 or col.numel() != val.numel():
+        raise ValueError('%s: row_ptr must hold n + 1 >= 2 entries, col and val one entry per stored affinity' % what)
+    if isolated is not None:
+        if not (torch.is_tensor(isolated) and isolated.is_cuda and isolated.dtype in (torch.bool, torch.uint8)
+                and tuple(isolated.shape) == (n,)):
+            raise ValueError('%s: isolated must be a bool [n] = [%d] tensor on a HIP device' % (what, n))
+        isolated = isolated.to(torch.uint8).contiguous()
+    if not checked:
+        E = col.numel()
+        lens = row_ptr[1:] - row_ptr[:-1]
+        ok = (row_ptr[0] == 0) & (row_ptr[n] == E) & (lens >= 0).all()
+        if E:
+            ok = ok & (col >= 0).all() & (col < n).all()
+        if not bool(ok):
+            raise ValueError('%s: the CSR is not square: row_ptr must run from 0 to E = %d without a step down and every '
+                             'column lie in 0..n-1 = 0..%d' % (what, E, n - 1))
+        if E > 1:
+            rows = torch.repeat_interleave(torch.arange(n, device=col.device), lens)
+            if bool(((rows[1:] == rows[:-1]) & (col[1:] <= col[:-1])).any()):
+                raise ValueError('%s: the CSR is not sorted: the columns of a row must ascend, each once' % what)
+    return n, isolated
+
+
+def tsne_affinities(xf, perplexity=30.0, metric='cosine', block_cols=None, block_bytes=None):
+    """The joint affinities P of t-SNE for the rows of ``xf`` [n, d] as a CSR on the device, without the n x n matrix:
+    ``(row_ptr int64 [n + 1], col int32 [E], val float32 [E], info)``.  Distance of a pair: 'cosine' = the symmetric
+    chain of ``mutual_reachability_mst`` (for unit rows half the squared Euclidean distance, used as it is),
+    'euclidean' = the square of the ``pairwise_distance_tensor(xf, xf)`` entry.  Every sample keeps its K =
+    min(n - 1, floor(3 perplexity) + 1) nearest neighbours: row i of ``search``'s top-(K + 1) list with the entry of
+    index i deleted, or the last entry if it is not there -- one pass over ``_ColumnBlocks``.  grl_tsne_perplexity then
+    runs scikit-learn's bisection on every row's precision beta in fp32.  A sample whose list holds a distance that is
+    not finite is isolated: it has no affinities in either direction.  P[i][j] = (p(j|i) + p(i|j)) / (2 n_live) over the
+    union pattern, columns ascending, symmetric bit for bit; a row may hold up to n - 1 entries.  ``info``: idx int32
+    [n, K], e and cond float32 [n, K], beta float32 [n], isolated bool [n], K.  The same bits on every run and for every
+    block width.  Not sharded: under torch.distributed every rank computes the identical result, no collective.
+    ValueError, before any device work: a host or non-2-d ``xf``, n < 3, a perplexity outside [1, K) or a bool, an
+    unknown metric, a ``verify_metric``."""
+    import math
+    n, K, perp = _tsne_rows(xf, perplexity, metric, 'tsne_affinities')
+    dev = xf.device
+    xf = _pad_features(xf)
+    blocks = _ColumnBlocks(xf, xf, metric, block_cols, block_bytes)
+    rinv = None
+    if metric == 'cosine':
+        d = xf.shape[1]
+        sq, rinv = _new((n,), xf), _new((n,), xf)
+        _call('grl_row_sqnorm', ptr(xf), ptr(sq), n, d, d)
+        _call('grl_silhouette_rinv', ptr(sq), n, ptr(rinv))
+    k = K + 1
+    run_key = torch.full((n, k), -1, dtype=torch.int64, device=dev)
+    run_val = torch.full((n, k), float('inf'), dtype=torch.float32, device=dev)
+    for c0, c1 in blocks.spans:
+        d = blocks.block(c0, c1)
+        if rinv is not None:
+            _call('grl_hdbscan_cosine_block', ptr(d), d.stride(0), n, n, 0, c0, c1 - c0, ptr(rinv))
+        else:
+            _call('grl_tsne_square_block', ptr(d), d.stride(0), n, c1 - c0)
+        _call('grl_topk_block', ptr(d), d.stride(0), None, 0, n, c1 - c0, c0, k, ptr(run_key), ptr(run_val))
+    del blocks
+    # the sample's own entry goes, or the last one when it is not in the list
+    idx = run_key & 0xffffffff
+    own = idx == torch.arange(n, device=dev).unsqueeze(1)
+    drop = torch.where(own.any(1), own.to(torch.int32).argmax(1), torch.full((n,), K, dtype=torch.int64, device=dev))
+    take = torch.arange(K, device=dev).unsqueeze(0)
+    take = take + (take >= drop.unsqueeze(1)).to(torch.int64)
+    e = run_val.gather(1, take).contiguous()
+    idx = idx.gather(1, take).to(torch.int32).contiguous()
+    del run_key, run_val
+    cond = torch.empty((n, K), dtype=torch.float32, device=dev)
+    beta = torch.empty(n, dtype=torch.float32, device=dev)
+    iso = torch.empty(n, dtype=torch.uint8, device=dev)
+    _call('grl_tsne_perplexity', ptr(e), n, K, float(math.log(perp)), ptr(cond), ptr(beta), ptr(iso))
+    isolated = iso.bool()
+    n_live = n - int(isolated.sum())
+    info = {'idx': idx, 'e': e, 'cond': cond, 'beta': beta, 'isolated': isolated, 'K': K}
+    row_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n_live == 0:
+        return (row_ptr, torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float32, device=dev),
+                info)
+    # the conditional matrix by rows (columns ascending, the pairs with an isolated end marked -1) and by columns
+    acol = torch.where(isolated.unsqueeze(1) | isolated[idx.long()], torch.full_like(idx, -1), idx).contiguous()
+    m = n * K
+    flat_ptr = torch.arange(n + 1, dtype=torch.int64, device=dev) * K
+    csc_ptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    csc_row = torch.zeros(m, dtype=torch.int32, device=dev)
+    csc_val = torch.zeros(m, dtype=torch.float32, device=dev)
+    cnt = torch.empty(n, dtype=torch.int32, device=dev)
+    tmp_row = torch.empty(m, dtype=torch.int32, device=dev)
+    tmp_val = torch.empty(m, dtype=torch.float32, device=dev)
+    _call('grl_rrs_transpose', ptr(flat_ptr), ptr(acol), ptr(cond), 0, n, ptr(cnt), ptr(tmp_row), ptr(tmp_val),
+          ptr(csc_ptr), ptr(csc_row), ptr(csc_val))
+    del tmp_row, tmp_val
+    acol, order = torch.sort(acol, dim=1)                     # (a row's live columns are distinct: one order)
+    acol = acol.contiguous()
+    aval = cond.gather(1, order).contiguous()
+    den = C.c_float(2.0 * n_live)
+
+    def joint(rp, col, val):
+        _call('grl_tsne_joint', ptr(acol), ptr(aval), K, ptr(csc_ptr), ptr(csc_row), ptr(csc_val), n, den, rp, ptr(cnt),
+              col, val)
+    joint(None, None, None)
+    _call('grl_rrs_scan', ptr(cnt), n, ptr(row_ptr))
+    n_entries = int(row_ptr[n])
+    col = torch.empty(max(n_entries, 1), dtype=torch.int32, device=dev)
+    val = torch.empty(max(n_entries, 1), dtype=torch.float32, device=dev)
+    joint(ptr(row_ptr), ptr(col), ptr(val))
+    return row_ptr, col[:n_entries], val[:n_entries], info
+
+
+def _tsne_terms(y, iso, n, rep, rowz, z):
+    """rep, rowz and Z at y: the two launches every gradient starts with."""
+    _call('grl_tsne_repulsion', ptr(y), ptr(iso), n, ptr(rep), ptr(rowz))
+    _call('grl_tsne_z', ptr(rowz), n, ptr(z))
+
+
+def tsne_gradient(row_ptr, col, val, y, exaggeration=1.0, isolated=None):
+    """The exact t-SNE gradient at ``y`` [n, 2] for the joint affinities of a CSR (``tsne_affinities``' or a caller's:
+    row_ptr int64 [n + 1], col int32 ascending in every row, val float32): ``(grad float32 [n, 2], z float32 [1])`` on
+    the device.  For a live i: dx = y[i] - y[j], q = 1 / (1 + |dx|^2); rep[i] = sum over the live j != i of q q dx,
+    Z = sum over i of sum over j of q, att[i] = sum over the row's entries of (exaggeration P) q dx, grad[i] =
+    4 (att[i] - rep[i] / Z).  The repulsive term is the exact n-body sum, computed on the fly; every sum runs in the
+    fixed fp32 order of DESIGN.md 4y, so the result is the same bit for bit on every run.  ``isolated`` bool [n]: samples
+    that exert no force and feel none (their gradient is 0).  ValueError: arrays of the wrong shape, dtype or device, a
+    CSR that is not square or not sorted."""
+    n, iso = _tsne_csr(row_ptr, col, val, isolated, 'tsne_gradient')
+    if not (torch.is_tensor(y) and y.is_cuda and y.dtype == torch.float32 and tuple(y.shape) == (n, 2)):
+        raise ValueError('tsne_gradient: y must be a float32 [n, 2] = [%d, 2] tensor on a HIP device' % n)
+    alpha = _tsne_real(exaggeration, 'tsne_gradient', 'exaggeration')
+    y = y.contiguous()
+    dev = y.device
+    rep, grad = torch.empty_like(y), torch.empty_like(y)
+    rowz = torch.empty(n, dtype=torch.float32, device=dev)
+    z = torch.empty(1, dtype=torch.float32, device=dev)
+    _tsne_terms(y, iso, n, rep, rowz, z)
+    _call('grl_tsne_update', ptr(row_ptr), ptr(col), ptr(val), ptr(y), ptr(iso), n, alpha, ptr(rep), ptr(z), ptr(grad),
+          None, None, None, 0.0, 0.0)
+    return grad, z
+
+
+def _tsne_run(row_ptr, col, val, iso, n, n_iter, lr, alpha, switch, seed, init, first=0, gains=None, update=None):
+    """The loop: three launches an iteration on the current stream, nothing read back inside it.  Returns
+    (y, gains, update, kl)."""
+    import numpy as np
+    dev = row_ptr.device
+    if seed is not None:
+        y0 = np.random.Generator(np.random.PCG64(seed)).standard_normal((n, 2)).astype(np.float32) * np.float32(1e-4)
+        y = torch.from_numpy(y0).to(dev)
+    else:
+        y = init.contiguous().clone()
+    y2, rep = torch.empty_like(y), torch.empty_like(y)
+    gains = torch.ones_like(y) if gains is None else gains.contiguous().clone()
+    update = torch.zeros_like(y) if update is None else update.contiguous().clone()
+    rowz = torch.empty(n, dtype=torch.float32, device=dev)
+    z = torch.empty(1, dtype=torch.float32, device=dev)
+    args = (ptr(row_ptr), ptr(col), ptr(val))
+    for it in range(first, first + n_iter):
+        early = it < switch
+        _tsne_terms(y, iso, n, rep, rowz, z)
+        _call('grl_tsne_update', *args, ptr(y), ptr(iso), n, alpha if early else 1.0, ptr(rep), ptr(z), None,
+              ptr(gains), ptr(update), ptr(y2), 0.5 if early else 0.8, lr)
+        y, y2 = y2, y
+    _tsne_terms(y, iso, n, rep, rowz, z)
+    _call('grl_tsne_kl', *args, ptr(y), ptr(iso), n, ptr(z), ptr(rowz))
+    kl = float(rowz.double().sum())
+    return y, gains, update, kl
+
+
+def _tsne_lr(lr, n_live, alpha):
+    import numpy as np
+    return float(np.float32(max(n_live / alpha / 4.0, 50.0) if lr is None else lr))
+
+
+def tsne_from_affinities(row_ptr, col, val, n_iter=1000, seed=0, init='random', learning_rate='auto',
+                         early_exaggeration=12.0, exaggeration_iter=250, isolated=None, first_iter=0, gains=None,
+                         update=None):
+    """The t-SNE loop on joint affinities that are there already (``tsne_affinities``' CSR or a caller's): a second seed
+    or more iterations cost no distance pass.  The arguments are ``tsne``'s.  ``init`` = an earlier run's ``embedding``
+    (with its NaN rows replaced), ``gains`` / ``update`` its state and ``first_iter`` the iterations it ran continue that
+    run bit for bit.  Returns a ``Tsne`` (``perplexity``, ``metric`` and ``beta`` are None)."""
+    import numbers
+    what = 'tsne_from_affinities'
+    n, iso = _tsne_csr(row_ptr, col, val, isolated, what, checked=True)            # (the checks without device work first)
+    n_iter, lr, alpha, switch, seed = _tsne_optimiser(n_iter, learning_rate, early_exaggeration, exaggeration_iter, seed,
+                                                      init, n, what)
+    if isinstance(first_iter, bool) or not isinstance(first_iter, numbers.Integral) or first_iter < 0:
+        raise ValueError('%s: first_iter must be an integer >= 0 (got %r)' % (what, first_iter))
+    for t, name in ((gains, 'gains'), (update, 'update')):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32
+                                  and tuple(t.shape) == (n, 2)):
+            raise ValueError('%s: %s must be a float32 [n, 2] = [%d, 2] tensor on a HIP device' % (what, name, n))
+    _tsne_csr(row_ptr, col, val, isolated, what)
+    return _tsne_result(row_ptr, col, val, iso, n, n_iter, lr, alpha, switch, seed, init, None, None, None, int(first_iter),
+                        gains, update)
+
+
+def _tsne_result(row_ptr, col, val, iso, n, n_iter, lr, alpha, switch, seed, init, perp, metric, beta, first=0,
+                 gains=None, update=None):
+    dev = row_ptr.device
+    n_iso = int(iso.sum()) if iso is not None else 0
+    lr = _tsne_lr(lr, n - n_iso, alpha)
+    if n_iso == n:                                   # nobody has an affinity: nothing moves, nothing is launched
+        y = torch.full((n, 2), float('nan'), dtype=torch.float32, device=dev)
+        return Tsne(y, 0.0, n_iter, n_iso, perp, metric, seed, lr, (row_ptr, col, val), beta, iso.bool(),
+                    torch.ones_like(y), torch.zeros_like(y))
+    y, gains, update, kl = _tsne_run(row_ptr, col, val, iso, n, n_iter, lr, alpha, switch, seed, init, first, gains, update)
+    isolated = iso.bool() if iso is not None else torch.zeros(n, dtype=torch.bool, device=dev)
+    if n_iso:
+        y[isolated] = float('nan')
+    return Tsne(y, kl, n_iter, n_iso, perp, metric, seed, lr, (row_ptr, col, val), beta, isolated, gains, update)
+
+
+def tsne(xf, perplexity=30.0, metric='cosine', n_iter=1000, seed=0, init='random', learning_rate='auto',
+         early_exaggeration=12.0, exaggeration_iter=250, block_cols=None, block_bytes=None):
+    """The 2-d t-SNE map of the rows of ``xf`` [n, d] on the device as a ``Tsne``: scikit-learn's exact gradient with
+    the affinities restricted to every sample's nearest neighbours (``tsne_affinities``), no n x n matrix, no tree, no
+    approximation.  ``init='random'`` draws Generator(PCG64(seed)).standard_normal((n, 2)) as float32 times 1e-4 on the
+    host; a float32 [n, 2] device tensor is used as it is.  Exactly ``n_iter`` iterations of scikit-learn's update
+    (gains + 0.2 / * 0.8 floored at 0.01, momentum 0.5 and the affinities times ``early_exaggeration`` for the first
+    ``exaggeration_iter`` iterations, then 0.8 and 1): three launches each -- the exact repulsive n-body sum, Z, the
+    sparse attraction with the update -- and no read-back inside the loop.  ``learning_rate='auto'`` = max(n_live /
+    early_exaggeration / 4, 50).  The Kullback-Leibler divergence at the final map is reported and steers nothing: no
+    early stopping.  The same bits on every run and for every block width.  Not sharded.  ValueError, before any device
+    work: ``tsne_affinities``', ``n_iter`` < 1, an ``init`` of the wrong shape, dtype or device, a bad seed."""
+    n, K, perp = _tsne_rows(xf, perplexity, metric, 'tsne')
+    n_iter, lr, alpha, switch, seed = _tsne_optimiser(n_iter, learning_rate, early_exaggeration, exaggeration_iter, seed,
+                                                      init, n, 'tsne')
+    row_ptr, col, val, info = tsne_affinities(xf, perp, metric, block_cols, block_bytes)
+    iso = info['isolated'].to(torch.uint8)
+    return _tsne_result(row_ptr, col, val, iso, n, n_iter, lr, alpha, switch, seed, init, perp, metric, info['beta'])

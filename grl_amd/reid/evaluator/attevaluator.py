@@ -185,6 +185,48 @@ def _hdbscan_report(knob, gf, ids, path, sil=None):
     return lines
 
 
+def _tsne_report(knob, gf, ids, path):
+    """GRL_EVAL_TSNE: the 2-d t-SNE map of the query-prepended gallery ``gf`` by cosine (engine.tsne) -- the line
+    ``_report`` prints after GRL_EVAL_HDBSCAN's, ``path + 'tsne.json'`` (rank 0 alone writes; strict JSON, the NaN
+    coordinates of an isolated sample become null; the rows are in the order of the ``labels`` of clusters.json /
+    hdbscan.json, so a clustering colours the map without a join) and, when matplotlib imports, ``path + 'tsne.png'``: a
+    scatter coloured by pid, the queries ringed.  ``knob`` = (perplexity, n_iter, seed)."""
+    import json
+    perplexity, n_iter, seed = knob
+    n = int(gf.size(0))
+    nq = n - (len(ids[1]) - len(ids[0]))
+    ts = engine.tsne(gf, perplexity, 'cosine', n_iter, seed)
+    lines = ['t-SNE: KL = {:.6g}, perplexity = {:g}, {} iterations, {} isolated of {}'.format(
+                 ts.kl, ts.perplexity, ts.n_iter, ts.n_isolated, n)]
+    if grl_dist._rank_world(None, None)[0] != 0:
+        return lines
+    emb = ts.embedding.cpu().numpy()
+    js = {'perplexity': ts.perplexity, 'n_iter': ts.n_iter, 'seed': ts.seed, 'metric': 'cosine', 'n': n, 'n_queries': nq,
+          'kl': ts.kl if math.isfinite(ts.kl) else None, 'n_isolated': ts.n_isolated,
+          'embedding': [[float(v) if np.isfinite(v) else None for v in row] for row in emb],
+          'pids': [int(p) for p in ids[1]], 'camids': [int(c) for c in ids[3]]}
+    with open((path or '') + 'tsne.json', 'w') as fh:
+        json.dump(js, fh, allow_nan=False)
+    try:
+        import matplotlib
+        matplotlib.use('Agg')
+        import matplotlib.pyplot as plt
+    except ImportError:
+        lines.append('t-SNE: matplotlib does not import, no tsne.png (the map is in tsne.json)')
+        return lines
+    pids = np.asarray(ids[1])
+    colour = np.unique(pids, return_inverse=True)[1]
+    fig, ax = plt.subplots(figsize=(8, 8))
+    ax.scatter(emb[:, 0], emb[:, 1], c=colour, cmap='nipy_spectral', s=6, linewidths=0)
+    ax.scatter(emb[:nq, 0], emb[:nq, 1], s=30, facecolors='none', edgecolors='k', linewidths=0.6)
+    ax.set_title('t-SNE of {} samples ({} queries ringed), perplexity {:g}, KL {:.4g}'.format(n, nq, ts.perplexity, ts.kl))
+    ax.set_xticks([])
+    ax.set_yticks([])
+    fig.savefig((path or '') + 'tsne.png', dpi=150, bbox_inches='tight')
+    plt.close(fig)
+    return lines
+
+
 def cosin_dist(qf, gf):
     return engine.cosin_dist(qf, gf)
 
@@ -335,6 +377,28 @@ def parse_hdbscan_knob(name, value):
         raise ValueError('%s: min_cluster_size must be >= 2, min_samples in 1..%d and method "eom" or "leaf" (got %r)'
                          % (name, engine.SEARCH_K_MAX, value))
     return mcs, ms, method
+
+
+def parse_tsne_knob(name, value):
+    """``GRL_EVAL_TSNE``: unset or empty -> None (off); "perplexity", "perplexity,n_iter" or "perplexity,n_iter,seed" ->
+    (perplexity, n_iter, seed) with a perplexity in [1, 341) ("1" alone means 30), an integer n_iter >= 1 (default
+    1000) and an integer seed >= 0 (default 0; engine.tsne).  Anything else is a ValueError that names the variable."""
+    if value is None or not value.strip():
+        return None
+    parts = [p.strip() for p in value.split(',')]
+    try:
+        if len(parts) > 3:
+            raise ValueError
+        perplexity = 30.0 if parts == ['1'] else float(parts[0])
+        n_iter = int(parts[1]) if len(parts) >= 2 else 1000
+        seed = int(parts[2]) if len(parts) == 3 else 0
+    except ValueError:
+        raise ValueError('%s must be "perplexity", "perplexity,n_iter" or "perplexity,n_iter,seed" with a number and '
+                         'integers ("1" alone: perplexity 30, 1000 iterations, seed 0) (got %r)' % (name, value))
+    if not 1.0 <= perplexity < (engine.SEARCH_K_MAX - 1) // 3 or not 1 <= n_iter <= 2 ** 31 - 1 or seed < 0:
+        raise ValueError('%s: perplexity must be in [1, %d), n_iter >= 1 and seed >= 0 (got %r)'
+                         % (name, (engine.SEARCH_K_MAX - 1) // 3, value))
+    return perplexity, n_iter, seed
 
 
 def parse_silhouette_knob(name, value):
@@ -501,6 +565,13 @@ class ATTEvaluator(object):
             raise ValueError('GRL_EVAL_HDBSCAN cannot be combined with GRL_EVAL_METRIC=%s: HDBSCAN runs by cosine on '
                              'the routes that rank by cosine (unset one of them)'
                              % os.environ['GRL_EVAL_METRIC'].strip())
+        # the 2-d map of the feature space, off by default: t-SNE of the query-prepended gallery by cosine (engine.tsne),
+        # printed after the HDBSCAN lines and stored in path + 'tsne.json' (and 'tsne.png' when matplotlib imports)
+        tsne_knob = parse_tsne_knob('GRL_EVAL_TSNE', os.environ.get('GRL_EVAL_TSNE'))
+        if tsne_knob is not None and knob is not None:
+            raise ValueError('GRL_EVAL_TSNE cannot be combined with GRL_EVAL_METRIC=%s: t-SNE runs by cosine on '
+                             'the routes that rank by cosine (unset one of them)'
+                             % os.environ['GRL_EVAL_METRIC'].strip())
         # the label-free score of those clusterings, off by default (engine.silhouette): a third line of each report and
         # a "silhouette" entry of its JSON file
         sil_knob = parse_silhouette_knob('GRL_EVAL_SILHOUETTE', os.environ.get('GRL_EVAL_SILHOUETTE'))
@@ -535,8 +606,9 @@ class ATTEvaluator(object):
         roc_lines = ()
 
         def extra(lines, cosine_roc=None):
-            """the route's ROC lines, then GRL_EVAL_CLUSTER's, GRL_EVAL_CLUSTER_JACCARD's, GRL_EVAL_KMEANS's and
-            GRL_EVAL_HDBSCAN's (by cosine or by the Jaccard distance of the features, whatever the route ranks by)"""
+            """the route's ROC lines, then GRL_EVAL_CLUSTER's, GRL_EVAL_CLUSTER_JACCARD's, GRL_EVAL_KMEANS's,
+            GRL_EVAL_HDBSCAN's and GRL_EVAL_TSNE's (by cosine or by the Jaccard distance of the features, whatever the
+            route ranks by)"""
             if cluster_knob is not None:
                 lines = tuple(lines) + tuple(_cluster_report(cluster_knob, qf, gf, ids, path, cosine_roc, sil_knob))
             if jaccard_knob is not None:
@@ -545,6 +617,8 @@ class ATTEvaluator(object):
                 lines = tuple(lines) + tuple(_kmeans_report(kmeans_knob, gf, ids, path, sil_knob))
             if hdbscan_knob is not None:
                 lines = tuple(lines) + tuple(_hdbscan_report(hdbscan_knob, gf, ids, path, sil_knob))
+            if tsne_knob is not None:
+                lines = tuple(lines) + tuple(_tsne_report(tsne_knob, gf, ids, path))
             return lines
         if visual:
             self._visualize(query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, rerank)

@@ -42,8 +42,8 @@ const char* grl_last_error(void);
  * re-ranking entry points grl_rrs_*, the CSR / CSC assembly of its sharded form (grl_rrs_expand_rows, grl_rrs_scan,
  * grl_rrs_place, grl_rrs_transpose) among them, grl_topk_block_filtered, grl_expand_rows, the grl_verify_* entry points,
  * grl_pair_hist_block, the clustering entry points grl_cluster_*, the k-means entry points grl_kmeans_* /
- * grl_segment_rowsum, grl_jaccard_edges, the silhouette entry points grl_silhouette_* and the HDBSCAN entry points
- * grl_hdbscan_*. */
+ * grl_segment_rowsum, grl_jaccard_edges, the silhouette entry points grl_silhouette_*, the HDBSCAN entry points
+ * grl_hdbscan_* and the t-SNE entry points grl_tsne_*. */
 #define GRL_ABI_VERSION 10
 int grl_abi_version(void);
 /* `waiter` (a hipStream_t) waits for everything enqueued on `signaler` so far: hipEventRecord + hipStreamWaitEvent on a
@@ -764,6 +764,52 @@ int grl_hdbscan_minedge_block(const float* d, int64_t ld, int n, int nrows, int 
  * distances): d[r][c] = max(0, 1.0f + (d[r][c] * rinv[lo]) * rinv[hi]) for the pair {row0 + r, c0 + c}. */
 int grl_hdbscan_cosine_block(float* d, int64_t ld, int n, int nrows, int row0, int c0, int ncols, const float* rinv,
                              void* stream);
+
+/* ---- t-SNE: the 2-d map of a feature set (tsne.hip, engine.tsne / tsne_affinities / tsne_gradient /
+ * tsne_from_affinities) ----
+ * THE WAVE ORDER of a sum over positions p = 0, 1, ..: 64 partial sums, partial l the sequential fp32 sum from +0.0f, in
+ * ascending p, of the terms with p % 64 == l (a term that is left out is skipped); then part[l] += part[l + s], l < s,
+ * for s = 32, 16, 8, 4, 2, 1.  Every sum of this section runs in it, every operation is rounded to fp32 on its own, a
+ * division is IEEE's.  One wave per row, no atomics, no LDS: the same bits on every run and for every launch geometry.
+ * d[r][c] = d[r][c] * d[r][c] in place on a block [nrows][ld] (ncols used): the squared distance of 'euclidean'. */
+int grl_tsne_square_block(float* d, int64_t ld, int nrows, int ncols, void* stream);
+/* The conditional affinities of every row of e [n][K] (the distances to its K neighbours, 1 <= K <= 1023) by
+ * scikit-learn's bisection on beta, on the distances less the list's first, t_k = e_k - e_0 (the list ascends; the
+ * same p and H as on e_k, without the underflow of every term at once that fp32 meets at e beta > 87): beta = 1, at
+ * most 100 steps of  p_k = expf(-(t_k * beta)), S = sum p_k, p_k = p_k / S, H = logf(S) + beta * sum(t_k * p_k)  (both
+ * sums in the wave order over k), stop when
+ * |H - log_perplexity| <= 1e-5f, otherwise H too large: beta doubles, or halves the way to the upper bound once there is
+ * one; H too small: beta halves, or halves the way to the lower bound.  cond [n][K] = the p_k of the last step, beta [n]
+ * its beta.  A row with a distance that is not finite is ISOLATED: isolated[i] = 1 (0 otherwise), cond = +0, beta = NaN. */
+int grl_tsne_perplexity(const float* e, int n, int K, float log_perplexity, float* cond, float* beta, uint8_t* isolated,
+                        void* stream);
+/* Row i of the joint affinities as a CSR over the union pattern.  acol / aval [n][K]: row i of the conditional matrix,
+ * columns ASCENDING, entries with a column < 0 (in front) are none; csc_ptr / csc_row / csc_val: its transpose
+ * (grl_rrs_transpose with nq = 0: column i's rows ascending).  P[i][j] = (a + b) / den, a = the row's value at j or +0,
+ * b = the column's value at j or +0.  Count pass (row_ptr = NULL): cnt[i] = the entries of row i.  Fill pass (row_ptr
+ * [n+1] = grl_rrs_scan of cnt): col ascending, every pair once per direction, val.  A row may hold up to n - 1 entries. */
+int grl_tsne_joint(const int32_t* acol, const float* aval, int K, const int64_t* csc_ptr, const int32_t* csc_row,
+                   const float* csc_val, int n, float den, const int64_t* row_ptr, int32_t* cnt, int32_t* col, float* val,
+                   void* stream);
+/* The exact repulsive term at y [n][2] (8-byte aligned).  For the pair (i, j): dx = y[i] - y[j], r = dx0 * dx0 + dx1 *
+ * dx1, q = 1.0f / (1.0f + r).  rep[i] = sum over j of (q * q) * dx, rowz[i] = sum over j of q, both in the wave order
+ * over the position j, j = i and the isolated j (isolated [n] uint8, NULL = none) left out; an isolated i gets zeros. */
+int grl_tsne_repulsion(const float* y, const uint8_t* isolated, int n, float* rep, float* rowz, void* stream);
+/* z[0] = the sum of rowz [n] in the wave order over the position i: one wave, whatever n */
+int grl_tsne_z(const float* rowz, int n, float* z, void* stream);
+/* att[i] = sum over the entries p of CSR row i (wave order over the place in the row, entries towards an isolated
+ * sample left out) of ((alpha * val[p]) * q) * dx; g = 4.0f * (att - rep[i] / z[0]); grad[i] = g when grad is not NULL
+ * (an isolated i: +0).  With update [n][2] given, scikit-learn's step per coordinate: gains = update * g < 0 ? gains +
+ * 0.2f : gains * 0.8f, at least 0.01f; update = momentum * update - learning_rate * (gains * g); y_out[i] = y[i] +
+ * update (an isolated i: y_out[i] = y[i], gains and update untouched).  y_out must not be y: other rows read y. */
+int grl_tsne_update(const int64_t* row_ptr, const int32_t* col, const float* val, const float* y, const uint8_t* isolated,
+                    int n, float alpha, const float* rep, const float* z, float* grad, float* gains, float* update,
+                    float* y_out, float momentum, float learning_rate, void* stream);
+/* rowkl[i] = sum over the entries of CSR row i with val > 0 (wave order over the place in the row, isolated ends left
+ * out) of val * (float)log((double)((val * z[0]) / q)) -- the fp32 logarithm correctly rounded, by way of fp64 -- : the
+ * row's share of the Kullback-Leibler divergence */
+int grl_tsne_kl(const int64_t* row_ptr, const int32_t* col, const float* val, const float* y, const uint8_t* isolated,
+                int n, const float* z, float* rowkl, void* stream);
 
 /* ---- query expansion / database-side augmentation (expand.hip, engine.expand_from_lists / expand_features) ----
  * out[i] = (x[i] + sum_p w_p * bank[j_p]) / (1 + sum_p w_p): a gather and a weighted sum over feature rows, without
