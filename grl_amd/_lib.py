@@ -191,6 +191,16 @@ _SIGNATURES = {
     'grl_tsne_z': ([_fp, C.c_int, _fp, _fp], C.c_int),
     'grl_tsne_update': ([_fp] * 5 + [C.c_int, C.c_float] + [_fp] * 6 + [C.c_float, C.c_float, _fp], C.c_int),
     'grl_tsne_kl': ([_fp] * 5 + [C.c_int, _fp, _fp, _fp], C.c_int),
+    # PCA: Cholesky, triangular solve, Jacobi and the rank-one corrections (pca.hip)
+    'grl_pca_cholesky': ([_fp, C.c_int, C.c_int, C.c_float, _fp, _fp], C.c_int),
+    'grl_pca_trsm': ([_fp, C.c_int, _fp, _i64, C.c_int, C.c_int, _fp], C.c_int),
+    'grl_pca_eigh': ([_fp, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp, _fp], C.c_int),
+    'grl_pca_rowsum': ([_fp, _i64, C.c_int, C.c_int, _fp, _fp], C.c_int),
+    'grl_pca_rank1': ([_fp, _i64, C.c_int, C.c_int, _fp, _fp, _fp], C.c_int),
+    'grl_pca_sign': ([_fp, _i64, C.c_int, C.c_int, _fp], C.c_int),
+    'grl_pca_affine': ([_fp, _fp, C.c_int, _fp, _fp, _fp], C.c_int),
+    'grl_pca_colscale': ([_fp, _i64, C.c_int, C.c_int, _fp, _fp, _i64, _fp], C.c_int),
+    'grl_pca_tsne_init': ([_fp, _i64, C.c_int, _fp, _fp], C.c_int),
     'grl_expand_rows': ([_fp, _i64, _fp, _i64, _fp, _fp, _i64] + [C.c_int] * 7 + [_fp, _i64, _fp], C.c_int),
     'grl_verify_fold': ([_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
     'grl_verify_rows': ([_fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, _fp],

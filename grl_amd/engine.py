@@ -3573,3 +3573,375 @@ def tsne(xf, perplexity=30.0, metric='cosine', n_iter=1000, seed=0, init='random
     row_ptr, col, val, info = tsne_affinities(xf, perp, metric, block_cols, block_bytes)
     iso = info['isolated'].to(torch.uint8)
     return _tsne_result(row_ptr, col, val, iso, n, n_iter, lr, alpha, switch, seed, init, perp, metric, info['beta'])
+
+
+# ----------------------------------------------------------------------------
+# PCA and whitening by randomised subspace iteration (pca.hip)
+# ----------------------------------------------------------------------------
+PCA_LMAX = 512                   # GRL_PCA_LMAX of include/grl_hip.h
+PCA_MAX_SWEEPS = 30              # GRL_PCA_MAX_SWEEPS
+PCA_OFF_TOL = 2.0 ** -24         # a Jacobi run counts as converged when off <= PCA_OFF_TOL * |B|_F (it stops at 2^-26)
+_PCA_PIVOT_CAUSE = {1: 'small', 2: 'nonfinite'}       # GRL_PCA_PIVOT_SMALL / _NONFINITE
+
+
+def _pad32(v):
+    return -(-v // 32) * 32
+
+
+def _pca_pivot_tol(L):
+    """A pivot at or below L * 2^-23 of the diagonal entry it started from (the row's own squared length) is within the
+    rounding of the factorisation itself: the row is a combination of the rows before it as far as fp32 can tell."""
+    return float(L) * 2.0 ** -23
+
+
+def _pca_tail(L, dev):
+    """One int32 block that a fit reads back once: the pivot record (8 words, GrlPcaRecord), the Jacobi info (4,
+    GrlPcaEighInfo), sum |x_i|^2 and |mu|^2 (2 + 2 spare), then the L eigenvalues padded to a multiple of 32."""
+    tail = torch.zeros(16 + _pad32(L), dtype=torch.int32, device=dev)
+    tail[:5] = torch.tensor([0x7f800000, 0, -1, -1, 0], dtype=torch.int32)      # {+inf, no failure, no index, no call, 0 calls}
+    return tail
+
+
+def _pca_int(v, lo, what, name):
+    import numbers
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < lo:
+        raise ValueError('%s: %s must be an integer >= %d (got %r)' % (what, name, lo, v))
+    return int(v)
+
+
+def _pca_matrix(t, what, name):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2):
+        raise ValueError('%s: %s must be a 2-d float32 tensor on a HIP device (got %s)'
+                         % (what, name, '%s %s on %s' % (tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t)
+                            else type(t).__name__))
+    return t
+
+
+def _pca_orth(w, L, m, rec):
+    """CholeskyQR2 in place on the rows of w [>= L, ld] (m columns used, ld % 32 == 0, the columns m.. zero): twice
+    G = W W^T (the GEMM), G = R R^T (grl_pca_cholesky into the sticky record ``rec``), W <- R^-1 W (grl_pca_trsm)."""
+    ld, Lp = w.shape[1], _pad32(L)
+    g = _new((L, Lp), w)
+    for _ in range(2):
+        gemm(w, w, g, L, L, ld, lda=ld, ldw=ld, ldy=Lp, math=MATH_F32)
+        _call('grl_pca_cholesky', ptr(g), Lp, L, _pca_pivot_tol(L), ptr(rec))
+        _call('grl_pca_trsm', ptr(g), Lp, ptr(w), ld, L, m)
+
+
+def _pca_shift(mu, c, rows, lam, scale, shift, cm):
+    """The epilogue of a GEMM against the centred rows: cm = C mu (one GEMM row), scale = 1 / sqrt(lam) or 1, shift =
+    -(cm * scale) (grl_pca_affine)."""
+    dp = mu.shape[1]
+    gemm(mu, c, cm, 1, rows, dp, math=MATH_F32)
+    _call('grl_pca_affine', ptr(cm), ptr(lam), rows, ptr(scale), ptr(shift))
+
+
+def _pca_wgrad(z, x, out, n, N, K, ldz):
+    """out [N, K] = z^T x over the n rows: the deterministic slab-reduced weight-gradient GEMM in exact fp32."""
+    d = _lib.GrlWgrad(ptr(z), ptr(x), ptr(out), None, n, N, K, ldz, K, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, MATH_F32, 0)
+    lib = _lib.load()
+    ws = torch.empty(max(int(lib.grl_wgrad_workspace_floats(C.byref(d))), 4), dtype=torch.float32, device=z.device)
+    d.workspace = ptr(ws)
+    check(lib.grl_conv_wgrad_f32(C.byref(d), _lib.stream()), 'grl_conv_wgrad_f32')
+    if _DEBUG_SYNC:
+        _debug_sync('pca wgrad %s' % ((n, N, K),))
+
+
+class _PcaFit(object):
+    """The buffers and stages of one fit; ``tools/pca_rate.py`` times the stages one by one.  Everything is padded with
+    zeros to what the GEMMs take (K % 32 == 0, ld % 4 == 0): q [Lp, dp], z [np, Lp], zt [Lp, np]."""
+
+    def __init__(self, xp, n, d, L, dev):
+        self.xp, self.n, self.d, self.L = xp, n, d, L
+        self.dp, self.np_, self.Lp, self.L4 = xp.shape[1], _pad32(n), _pad32(L), (L + 3) // 4 * 4
+        self.tail = _pca_tail(L, dev)
+        self.rec = self.tail[:8]
+        self.q = torch.zeros((self.Lp, self.dp), dtype=torch.float32, device=dev)
+        self.z = torch.zeros((self.np_, self.Lp), dtype=torch.float32, device=dev)
+        self.zt = torch.empty((self.Lp, self.np_), dtype=torch.float32, device=dev)
+        self.cm, self.one, self.shift = (torch.zeros(self.Lp, dtype=torch.float32, device=dev) for _ in range(3))
+        self.s = torch.empty(self.Lp, dtype=torch.float32, device=dev)
+        self.mu = None
+
+    def mean(self):
+        """mu [1, dp]: cluster_centroids(xf, zeros, 1, 'mean')'s kernels (the padding columns come out +0)."""
+        dev = self.xp.device
+        labels = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        counts = torch.full((1,), self.n, dtype=torch.int32, device=dev)
+        self.mu = _kmeans_update(self.xp, labels, counts, 1, 'mean')[0]
+
+    def orth_q(self):
+        _pca_orth(self.q, self.L, self.d, self.rec)
+
+    def project(self):
+        """z [n, L] = Xc Q^T = X Q^T - 1 (Q mu)^T (the GEMM's shift), and zt = its transpose."""
+        _pca_shift(self.mu, self.q, self.L4, None, self.one, self.shift, self.cm)
+        gemm(self.xp, self.q, self.z, self.n, self.L4, self.dp, ldy=self.Lp, shift=self.shift, math=MATH_F32)
+        _call('grl_transpose', ptr(self.z), ptr(self.zt), self.np_, self.Lp, self.Lp)
+
+    def orth_z(self):
+        _pca_orth(self.zt, self.L, self.n, self.rec)
+
+    def back(self):
+        """q [L, d] = Z^T Xc = Z^T X - (Z^T 1) mu^T: the weight-gradient GEMM and the rank-one term."""
+        _call('grl_pca_rowsum', ptr(self.zt), self.np_, self.L, self.n, ptr(self.s))
+        _call('grl_transpose', ptr(self.zt), ptr(self.z), self.Lp, self.np_, self.np_)
+        _pca_wgrad(self.z, self.xp, self.q, self.n, self.L4, self.dp, self.Lp)
+        _call('grl_pca_rank1', ptr(self.q), self.dp, self.L, self.d, ptr(self.s), ptr(self.mu))
+
+    def ritz_matrix(self):
+        """b [L, Lp] = Z^T Z * (1 / (n - 1)) (after ``project``)."""
+        import numpy as np
+        inv = torch.full((self.Lp,), float(np.float32(1.0) / np.float32(self.n - 1)), dtype=torch.float32,
+                         device=self.xp.device)
+        b = _new((self.L, self.Lp), self.xp)
+        gemm(self.zt, self.zt, b, self.L, self.L, self.np_, lda=self.np_, ldw=self.np_, ldy=self.Lp, scale=inv,
+             math=MATH_F32)
+        return b
+
+    def eigh(self, b):
+        """lam (in the tail block) and vt [Lp, Lp] of b, destroyed (grl_pca_eigh)."""
+        vtw = _new((self.L, self.Lp), b)
+        vt = torch.zeros((self.Lp, self.Lp), dtype=torch.float32, device=b.device)
+        lam = self.tail[16:].view(torch.float32)
+        _call('grl_pca_eigh', ptr(b), self.Lp, ptr(vtw), self.Lp, self.L, ptr(lam), ptr(vt), self.Lp, ptr(self.tail[8:12]))
+        return lam, vt
+
+    def components(self, vt, r):
+        """The first r rows of V^T Q as [r, dp], signs fixed (grl_pca_sign)."""
+        qt = _new((self.dp, self.Lp), self.q)
+        _call('grl_transpose', ptr(self.q), ptr(qt), self.Lp, self.dp, self.dp)
+        c = _new((r, self.dp), self.q)
+        gemm(vt, qt, c, r, self.dp, self.Lp, math=MATH_F32)
+        _call('grl_pca_sign', ptr(c), self.dp, r, self.d)
+        return c
+
+    def sums(self):
+        """sum_i |x_i|^2 and |mu|^2 into the tail block: grl_row_sqnorm, the first folded in the wave order."""
+        sq = _new((self.n,), self.xp)
+        f = self.tail[12:16].view(torch.float32)
+        _call('grl_row_sqnorm', ptr(self.xp), ptr(sq), self.n, self.dp, self.dp)
+        _call('grl_pca_rowsum', ptr(sq), self.n, 1, self.n, ptr(f))
+        _call('grl_row_sqnorm', ptr(self.mu), ptr(f[1:]), 1, self.dp, self.dp)
+
+
+def _pca_raise(what, status, index, call, L):
+    if _PCA_PIVOT_CAUSE.get(status) == 'nonfinite':
+        raise _lib.GrlHipError('%s: a Cholesky pivot is not finite (pivot %d of factorisation %d): the features hold NaN '
+                               'or infinite values -- remove the non-finite rows' % (what, index, call))
+    raise _lib.GrlHipError('%s: Cholesky pivot %d of factorisation %d is not positive in fp32: L = n_components + '
+                           'oversample = %d is above the numerical rank of the centred features -- lower n_components / '
+                           'oversample' % (what, index, call, L))
+
+
+class Pca(object):
+    """The result of ``pca``, everything on the device:
+
+      mean                     float32 [d]: cluster_centroids(xf, zeros, 1, 'mean')[0][0] bit for bit
+      components               float32 [r, d], orthonormal rows, the entry of largest magnitude of each positive
+      explained_variance       float32 [r] descending; explained_variance_ratio = it * float32(1 / total_variance)
+      total_variance           float: (sum |x_i|^2 - n |mean|^2) / (n - 1)
+      n_samples, n_iter, seed, oversample
+      sweeps                   Jacobi sweeps of the Rayleigh-Ritz eigensolve;  off: the off-diagonal norm it left
+      min_pivot                the smallest Cholesky pivot of the fit relative to its Gram matrix's largest diagonal"""
+
+    def __init__(self, mu, cpad, lam, d, total, n, n_iter, seed, oversample, sweeps, off, min_pivot, lam_host):
+        self._mu, self._cpad, self._d, self._lam_host = mu, cpad, d, lam_host
+        self.mean = mu[0, :d]
+        self.components = cpad[:, :d] if cpad.shape[1] == d else cpad[:, :d].contiguous()
+        self.explained_variance = lam
+        self.total_variance, self.n_samples, self.n_iter, self.seed, self.oversample = total, n, n_iter, seed, oversample
+        self.sweeps, self.off, self.min_pivot = sweeps, off, min_pivot
+        self.explained_variance_ratio = None
+        self._aff = {}
+        self._ct = None
+
+    def _rows(self, x, what, width, name):
+        _pca_matrix(x, what, name)
+        if x.shape[1] != width:
+            raise ValueError('%s: %s has %d columns, the fit has %d' % (what, name, x.shape[1], width))
+        return _pad_features(x)
+
+    def affine(self, whiten=False):
+        """(scale, shift) float32 [r] of the transform GEMM: scale_i = 1 / sqrt(lambda_i) with ``whiten`` else 1,
+        shift_i = -(C mu)_i * scale_i.  ValueError: ``whiten`` with a kept variance that is <= 0 or not finite."""
+        import math
+        whiten = bool(whiten)
+        if whiten and not all(math.isfinite(v) and v > 0 for v in self._lam_host):
+            raise ValueError('Pca: whiten needs every kept explained_variance finite and > 0 (the smallest kept one is '
+                             '%r): lower n_components' % (min(self._lam_host),))
+        if whiten not in self._aff:
+            r = self._cpad.shape[0]
+            cm, scale, shift = (_new((r,), self._cpad) for _ in range(3))
+            _pca_shift(self._mu, self._cpad, r, self.explained_variance if whiten else None, scale, shift, cm)
+            self._aff[whiten] = (scale, shift)
+        return self._aff[whiten]
+
+    def transform(self, x, whiten=False):
+        """Y [rows, r] = (x - mean) C^T, column i times 1 / sqrt(lambda_i) with ``whiten``: one
+        ``gemm(x, C, scale=scale, shift=shift)`` with ``affine(whiten)``, exact fp32 whatever the math mode.  Any rows."""
+        xp = self._rows(x, 'Pca.transform', self._d, 'x')
+        scale, shift = self.affine(whiten)
+        rows, r = xp.shape[0], self._cpad.shape[0]
+        y = _new((rows, r), xp)
+        if rows:
+            gemm(xp, self._cpad, y, rows, r, xp.shape[1], scale=scale, shift=shift, math=MATH_F32)
+        return y
+
+    def inverse_transform(self, y, whiten=False):
+        """X^ [rows, d] = y C + mean (y times sqrt(lambda) first when it was whitened): one GEMM with the mean as shift."""
+        r, d = self._cpad.shape[0], self._d
+        y = self._rows(y, 'Pca.inverse_transform', r, 'y')
+        rows, rp = y.shape[0], y.shape[1]
+        if whiten:
+            self.affine(True)
+            yw = torch.zeros_like(y)
+            _call('grl_pca_colscale', ptr(y), rp, rows, r, ptr(self.explained_variance), ptr(yw), rp)
+            y = yw
+        if self._ct is None:
+            dp = self._cpad.shape[1]
+            crows = torch.zeros((rp, dp), dtype=torch.float32, device=y.device)
+            crows[:r] = self._cpad
+            self._ct = _new((dp, rp), y)
+            _call('grl_transpose', ptr(crows), ptr(self._ct), rp, dp, dp)
+        out = _new((rows, d), y)
+        if rows:
+            gemm(y, self._ct, out, rows, d, rp, shift=self._mu, math=MATH_F32)
+        return out
+
+    def tsne_init(self, x):
+        """scikit-learn's ``init='pca'`` start of t-SNE, float32 [rows, 2]: the first two transformed columns divided by
+        the population standard deviation of the first and multiplied by 1e-4 (grl_pca_tsne_init); use as
+        ``tsne(xf, init=pca(xf, 2).tsne_init(xf))``.  Needs n_components >= 2."""
+        if self._cpad.shape[0] < 2:
+            raise ValueError('Pca.tsne_init: needs n_components >= 2 (the fit kept %d)' % self._cpad.shape[0])
+        xp = self._rows(x, 'Pca.tsne_init', self._d, 'x')
+        rows = xp.shape[0]
+        if rows < 1:
+            raise ValueError('Pca.tsne_init: x has no rows')
+        shift = self.affine(False)[1]
+        y = _new((rows, 2), xp)
+        gemm(xp, self._cpad, y, rows, 2, xp.shape[1], shift=shift, math=MATH_F32)
+        out = torch.empty_like(y)
+        _call('grl_pca_tsne_init', ptr(y), 2, rows, ptr(out))
+        return out
+
+
+def _pca_args(xf, n_components, oversample, n_iter, seed, what):
+    """The checks of ``pca`` that need no device work: (n, d, r, p, q, seed)."""
+    _pca_matrix(xf, what, 'xf')
+    n, d = int(xf.shape[0]), int(xf.shape[1])
+    r = _pca_int(n_components, 1, what, 'n_components')
+    p = _pca_int(oversample, 0, what, 'oversample')
+    q = _pca_int(n_iter, 0, what, 'n_iter')
+    seed = _pca_int(seed, 0, what, 'seed')
+    if n < 2:
+        raise ValueError('%s: needs n >= 2 samples (got %s)' % (what, tuple(xf.shape)))
+    if r + p > min(n - 1, d) or r + p > PCA_LMAX:
+        raise ValueError('%s: L = n_components + oversample = %d must be at most min(n - 1, d, %d) = %d: lower '
+                         'n_components / oversample' % (what, r + p, PCA_LMAX, min(n - 1, d, PCA_LMAX)))
+    return n, d, r, p, q, seed
+
+
+def pca(xf, n_components, oversample=10, n_iter=4, seed=0):
+    """PCA of the rows of ``xf`` [n, d] on the device by randomised subspace iteration, as a ``Pca``: the state is
+    O((n + d) L + L^2) with L = n_components + oversample -- no d x d covariance, no n x n Gram matrix, no centred copy
+    (every product with the centred rows is the product with ``xf`` and a rank-one term).  The start is
+    Generator(PCG64(seed)).standard_normal((L, d)) as float32 from the host, orthonormalised by CholeskyQR2; ``n_iter``
+    power iterations with both halves orthonormalised; Rayleigh-Ritz with the Jacobi eigensolver.  The tall products are
+    ``gemm`` and the slab-reduced weight-gradient GEMM in exact fp32 whatever ``set_math`` says; everything between is
+    pca.hip.  One read-back, at the end.  The same bits on every run.  Not sharded: every rank computes the same result
+    and issues no collective.  ValueError, before any device work: ``xf`` not a 2-d float32 device tensor, n < 2,
+    arguments that are not integers (a bool is none) or out of range, L > min(n - 1, d, 512).  GrlHipError: a Cholesky
+    pivot that is not positive (L above the numerical rank: lower n_components / oversample) or not finite (remove the
+    non-finite rows), a Jacobi run that did not converge in 30 sweeps."""
+    import numpy as np
+    what = 'pca'
+    n, d, r, p, q, seed = _pca_args(xf, n_components, oversample, n_iter, seed, what)
+    L, dev = r + p, xf.device
+    fit = _PcaFit(_pad_features(xf), n, d, L, dev)
+    fit.mean()
+    q0 = np.random.Generator(np.random.PCG64(seed)).standard_normal((L, d)).astype(np.float32)
+    fit.q[:L, :d] = torch.from_numpy(q0).to(dev)
+    fit.orth_q()
+    for _ in range(q):
+        fit.project()
+        fit.orth_z()
+        fit.back()
+        fit.orth_q()
+    fit.project()
+    lam, vt = fit.eigh(fit.ritz_matrix())
+    cpad = fit.components(vt, r)
+    fit.sums()
+    host = fit.tail.cpu()                                   # the one read-back
+    status, index, call = int(host[1]), int(host[2]), int(host[3])
+    if status:
+        _pca_raise(what, status, index, call, L)
+    hf = host.view(torch.float32)
+    min_pivot, sweeps, off, fro = float(hf[0]), int(host[8]), float(hf[9]), float(hf[10])
+    if not off <= PCA_OFF_TOL * fro:
+        raise _lib.GrlHipError('%s: the Jacobi eigensolver left an off-diagonal norm of %g on a matrix of norm %g after %d '
+                               'sweeps (converged is <= 2^-24 of the norm): the features hold non-finite values -- remove '
+                               'the non-finite rows -- or the Rayleigh-Ritz matrix is not symmetric' % (what, off, fro, sweeps))
+    total = (float(hf[12]) - n * float(hf[13])) / (n - 1)
+    out = Pca(fit.mu, cpad, lam[:r].clone(), d, total, n, q, seed, p, sweeps, off, min_pivot,
+              [float(v) for v in hf[16:16 + r]])
+    ratio = torch.empty_like(lam)
+    _call('grl_axpby', ptr(lam), None, ptr(ratio), float(np.float32(1.0) / np.float32(total)) if total > 0 else float('nan'),
+          0.0, lam.numel())
+    out.explained_variance_ratio = ratio[:r].clone()
+    return out
+
+
+def pca_eigh(b):
+    """The eigendecomposition of the symmetric ``b`` [L, L], L <= 512, by the fit's cyclic Jacobi kernel (grl_pca_eigh:
+    fixed round-robin pairing, at most 30 sweeps): ``(lam [L] descending, v [L, L] with b = v diag(lam) v^T, sweeps)``.
+    Only the upper triangle of ``b`` is read.  GrlHipError when the run did not converge."""
+    what = 'pca_eigh'
+    _pca_matrix(b, what, 'b')
+    L = int(b.shape[0])
+    if b.shape[1] != L or not 1 <= L <= PCA_LMAX:
+        raise ValueError('%s: b must be square with 1 <= L <= %d (got %s)' % (what, PCA_LMAX, tuple(b.shape)))
+    Lp = _pad32(L)
+    a = torch.zeros((L, Lp), dtype=torch.float32, device=b.device)
+    a[:, :L] = b
+    vtw, vt = _new((L, Lp), b), _new((L, Lp), b)
+    lam = _new((L,), b)
+    info = torch.zeros(4, dtype=torch.int32, device=b.device)
+    _call('grl_pca_eigh', ptr(a), Lp, ptr(vtw), Lp, L, ptr(lam), ptr(vt), Lp, ptr(info))
+    host = info.cpu()
+    sweeps, off, fro = int(host[0]), float(host.view(torch.float32)[1]), float(host.view(torch.float32)[2])
+    if not off <= PCA_OFF_TOL * fro:
+        raise _lib.GrlHipError('%s: off-diagonal norm %g of a matrix of norm %g after %d sweeps: not converged (b must be '
+                               'finite and symmetric)' % (what, off, fro, sweeps))
+    return lam, vt[:, :L].t().contiguous(), sweeps
+
+
+class PcaOrth(tuple):
+    """``(q, min_pivot)`` of ``pca_orthonormalize`` with the pivot record's ``status`` (0 = fine, 'small', 'nonfinite')
+    and the ``index`` and ``call`` (0 or 1) of the first failing pivot."""
+
+    def __new__(cls, q, min_pivot, status, index, call):
+        self = tuple.__new__(cls, (q, min_pivot))
+        self.status, self.index, self.call = status, index, call
+        return self
+
+
+def pca_orthonormalize(w):
+    """The rows of ``w`` [L, m], L <= min(m, 512), orthonormalised by the fit's CholeskyQR2 (twice: Gram matrix by the
+    GEMM, grl_pca_cholesky, grl_pca_trsm): ``(q [L, m], min_pivot)``, q = T w with T lower triangular, min_pivot the
+    smallest pivot relative to the Gram matrix's largest diagonal entry over both passes.  Dependent rows do not raise:
+    the result's ``status`` is 'small' (or 'nonfinite'), ``index`` the first failing pivot (one at or below L * 2^-23 of
+    its row's own squared length), and q is finite for finite input -- the rows from ``index`` on orthogonal to those before, not normalised."""
+    what = 'pca_orthonormalize'
+    _pca_matrix(w, what, 'w')
+    L, m = int(w.shape[0]), int(w.shape[1])
+    if not 1 <= L <= min(m, PCA_LMAX):
+        raise ValueError('%s: w must be [L, m] with 1 <= L <= min(m, %d) (got %s)' % (what, PCA_LMAX, tuple(w.shape)))
+    buf = torch.zeros((L, _pad32(m)), dtype=torch.float32, device=w.device)
+    buf[:, :m] = w
+    tail = _pca_tail(1, w.device)
+    _pca_orth(buf, L, m, tail[:8])
+    host = tail[:8].cpu()
+    return PcaOrth(buf[:, :m].contiguous(), float(host.view(torch.float32)[0]), _PCA_PIVOT_CAUSE.get(int(host[1]), 0),
+                   int(host[2]), int(host[3]))

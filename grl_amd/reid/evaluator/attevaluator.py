@@ -401,6 +401,47 @@ def parse_tsne_knob(name, value):
     return perplexity, n_iter, seed
 
 
+def parse_pca_knob(name, value):
+    """``GRL_EVAL_PCA``: unset or empty -> None (off); "r" or "r,whiten" -> (r, whiten) with an integer r in 1..502 (the
+    components kept; engine.pca adds 10 of oversampling and holds 512 directions) and whiten 0 or 1 (default 0).
+    Anything else is a ValueError that names the variable."""
+    if value is None or not value.strip():
+        return None
+    parts = [p.strip() for p in value.split(',')]
+    try:
+        if len(parts) > 2:
+            raise ValueError
+        r = int(parts[0])
+        whiten = int(parts[1]) if len(parts) == 2 else 0
+    except ValueError:
+        raise ValueError('%s must be "r" or "r,whiten" with an integer r and whiten 0 or 1 (got %r)' % (name, value))
+    if not 1 <= r <= engine.PCA_LMAX - 10 or whiten not in (0, 1):
+        raise ValueError('%s: r must be in 1..%d and whiten 0 or 1 (got %r)' % (name, engine.PCA_LMAX - 10, value))
+    return r, bool(whiten)
+
+
+def _pca_report(knob, qf, gf, path):
+    """GRL_EVAL_PCA: fit engine.pca on the query-prepended gallery ``gf`` and return the transforms of ``qf`` and ``gf``
+    (r columns, whitened or not; zero columns are appended up to a multiple of 32, the width the distance GEMMs take --
+    they add +0 to every dot product and norm) -- one printed line and ``path + 'pca.json'`` (rank 0 alone writes;
+    strict JSON)."""
+    import json
+    r, whiten = knob
+    fit = engine.pca(gf, r)
+    lam = [float(v) for v in fit.explained_variance.cpu()]
+    ratio = float(fit.explained_variance_ratio.double().sum())
+    print('PCA: r = {}, whiten = {}, explained variance ratio = {:.6g}, lambda_1 = {:.6g}, lambda_r = {:.6g}'.format(
+        r, int(whiten), ratio, lam[0], lam[-1]))
+    if grl_dist._rank_world(None, None)[0] == 0:
+        js = {'n_components': r, 'whiten': bool(whiten), 'explained_variance_ratio_sum': ratio, 'lambda_1': lam[0],
+              'lambda_r': lam[-1], 'explained_variance': lam, 'total_variance': fit.total_variance,
+              'n_samples': fit.n_samples, 'oversample': fit.oversample, 'n_iter': fit.n_iter, 'seed': fit.seed,
+              'sweeps': fit.sweeps, 'min_pivot': fit.min_pivot}
+        with open((path or '') + 'pca.json', 'w') as fh:
+            json.dump(js, fh, allow_nan=False)
+    return engine._pad_features(fit.transform(qf, whiten)), engine._pad_features(fit.transform(gf, whiten))
+
+
 def parse_silhouette_knob(name, value):
     """``GRL_EVAL_SILHOUETTE``: unset or empty -> None (off); "1" or "cosine", or "euclidean", optionally followed by
     ",drop" or ",singleton" -> (metric, noise) for engine.silhouette (default noise: 'singleton', the convention of
@@ -579,6 +620,13 @@ class ATTEvaluator(object):
                 and hdbscan_knob is None:
             raise ValueError('GRL_EVAL_SILHOUETTE scores the labels of GRL_EVAL_CLUSTER, GRL_EVAL_CLUSTER_JACCARD, '
                              'GRL_EVAL_KMEANS or GRL_EVAL_HDBSCAN: set one of them too (or unset GRL_EVAL_SILHOUETTE)')
+        # PCA / PCA-whitening of the features, off by default (engine.pca): fitted on the query-prepended gallery and
+        # applied to both before DBA and QE; everything below runs on the r-column tensors unchanged
+        pca_knob = parse_pca_knob('GRL_EVAL_PCA', os.environ.get('GRL_EVAL_PCA'))
+        if pca_knob is not None and knob is not None:
+            raise ValueError('GRL_EVAL_PCA cannot be combined with GRL_EVAL_METRIC=%s: the verification head reads '
+                             'fixed slices of the raw feature rows, which a change of basis does not keep (unset one '
+                             'of them)' % os.environ['GRL_EVAL_METRIC'].strip())
         qf, q_pids, q_camids = self.extract_feature(query_loader)
         print('Done, obtained {}-by-{} matrix'.format(qf.size(0), qf.size(1)))
         gf, g_pids, g_camids = self.extract_feature(gallery_loader)
@@ -590,6 +638,8 @@ class ATTEvaluator(object):
         # gallery row by the weighted mean of itself and its m nearest other rows, query expansion then does the same
         # for the queries against the (augmented) gallery, under the junk rule CMC / mAP apply.  Everything below runs
         # on the new tensors unchanged.
+        if pca_knob is not None:
+            qf, gf = _pca_report(pca_knob, qf, gf, path)
         if dba is not None:
             print('Database-side augmentation: m = {}, alpha = {}'.format(*dba))
             gf = engine.expand_features(gf, gf, dba[0], dba[1], skip_self=True)

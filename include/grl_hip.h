@@ -43,7 +43,7 @@ const char* grl_last_error(void);
  * grl_rrs_place, grl_rrs_transpose) among them, grl_topk_block_filtered, grl_expand_rows, the grl_verify_* entry points,
  * grl_pair_hist_block, the clustering entry points grl_cluster_*, the k-means entry points grl_kmeans_* /
  * grl_segment_rowsum, grl_jaccard_edges, the silhouette entry points grl_silhouette_*, the HDBSCAN entry points
- * grl_hdbscan_* and the t-SNE entry points grl_tsne_*. */
+ * grl_hdbscan_*, the t-SNE entry points grl_tsne_* and the PCA entry points grl_pca_*. */
 #define GRL_ABI_VERSION 10
 int grl_abi_version(void);
 /* `waiter` (a hipStream_t) waits for everything enqueued on `signaler` so far: hipEventRecord + hipStreamWaitEvent on a
@@ -810,6 +810,64 @@ int grl_tsne_update(const int64_t* row_ptr, const int32_t* col, const float* val
  * row's share of the Kullback-Leibler divergence */
 int grl_tsne_kl(const int64_t* row_ptr, const int32_t* col, const float* val, const float* y, const uint8_t* isolated,
                 int n, const float* z, float* rowkl, void* stream);
+
+/* ---- PCA: the small dense linear algebra of the randomised subspace iteration (pca.hip, engine.pca / pca_eigh /
+ * pca_orthonormalize) ----
+ * The tall products of a fit are grl_conv_gemm_f32 and grl_conv_wgrad_f32 in GRL_MATH_F32; these entry points work on
+ * matrices of L <= GRL_PCA_LMAX rows.  A factorisation is one workgroup (no grid-wide barrier, no cooperative launch),
+ * every loop is bounded at launch, every operation is rounded to fp32 on its own, divisions and square roots are IEEE's,
+ * no atomics: the same bits on every run. */
+#define GRL_PCA_LMAX 512
+#define GRL_PCA_MAX_SWEEPS 30
+#define GRL_PCA_PIVOT_SMALL 1        /* a pivot <= rel_tol * (its own diagonal entry of G): the row depends on the rows before it in fp32 */
+#define GRL_PCA_PIVOT_NONFINITE 2    /* a pivot (or the largest diagonal entry) that is NaN or infinite */
+/* The pivot record of grl_pca_cholesky, STICKY over calls: the caller sets {+inf, 0, -1, -1, 0} once and reads it back
+ * after the last call.  min_pivot: the smallest pivot / (largest diagonal entry of that call's input) met so far, a
+ * failing pivot included; status / index / call: 0, or the kind, the pivot index and the call number (from 0) of the
+ * FIRST failure; calls: how many factorisations the record has seen. */
+typedef struct GrlPcaRecord {
+    float   min_pivot;
+    int32_t status, index, call, calls;
+    int32_t reserved[3];
+} GrlPcaRecord;
+/* G = R R^T in place on the lower triangle of g [L][ldg] (the strict upper triangle is neither read nor written):
+ * R[i][k] = (G[i][k] - sum_{j<k} R[i][j] * R[k][j]) / R[k][k], R[k][k] = sqrtf(G[k][k] - sum_{j<k} R[k][j] * R[k][j]), each
+ * sum term by term in ascending j from the G entry.  A pivot that is not finite or not > rel_tol * G[k][k] (the entry it
+ * started from: the test does not depend on the scale of the rows) ENDS the
+ * factorisation and is recorded: its column and all later ones are set to the identity's, so grl_pca_trsm stays finite on
+ * finite input.  One workgroup of 1024, the panel of 32 columns in LDS (2 * L * 33 floats of dynamic LDS). */
+int grl_pca_cholesky(float* g, int ldg, int L, float rel_tol, GrlPcaRecord* record, void* stream);
+/* W <- R^-1 W for w [L][ldw] (m columns used) and the lower triangle R of r [L][ldr]: forward substitution, y_i = (w_i -
+ * sum_{k<i} R[i][k] * y_k) / R[i][i], the sum term by term in ascending k; one lane per column of W. */
+int grl_pca_trsm(const float* r, int ldr, float* w, int64_t ldw, int L, int m, void* stream);
+typedef struct GrlPcaEighInfo {
+    int32_t sweeps;      /* sweeps that rotated at least one pair (<= GRL_PCA_MAX_SWEEPS) */
+    float   off;         /* the Frobenius norm of the off-diagonal part that is left */
+    float   fro;         /* the Frobenius norm of the input */
+    int32_t reserved;
+} GrlPcaEighInfo;
+/* Cyclic Jacobi on the symmetric a [L][lda] (the upper triangle is read; a is destroyed): lam [L] descending (equal ones by
+ * their original index, a NaN last), vt [L][ldvt] with row i the unit eigenvector of lam[i]; vt_work [L][ldv] is scratch.
+ * Round-robin pairing (pca.hip), so the rotation order depends on L alone; a pair with |a_pq| <= (|a|_F * 2^-26) / L is
+ * passed over; the loop ends after the first sweep without a rotation or after GRL_PCA_MAX_SWEEPS.  Converged means
+ * info->off <= 2^-26 |a|_F.  A 1 x 1 or diagonal input: no rotation, sweeps = 0.  One workgroup of 1024. */
+int grl_pca_eigh(float* a, int lda, float* vt_work, int ldv, int L, float* lam, float* vt, int ldvt, GrlPcaEighInfo* info,
+                 void* stream);
+/* out[i] = the sum of the m used columns of row i of w [rows][ld] in the wave order (the t-SNE section above) over the column */
+int grl_pca_rowsum(const float* w, int64_t ld, int rows, int m, float* out, void* stream);
+/* w[i][j] = w[i][j] - s[i] * mu[j] on w [rows][ld] (m columns used): the rank-one term of a product with centred rows */
+int grl_pca_rank1(float* w, int64_t ld, int rows, int m, const float* s, const float* mu, void* stream);
+/* every row of c [rows][ld] (d used) whose entry of largest magnitude -- the lowest column among equals -- is negative is
+ * multiplied by -1 */
+int grl_pca_sign(float* c, int64_t ld, int rows, int d, void* stream);
+/* scale[i] = lam ? 1.0f / sqrtf(lam[i]) : 1.0f; shift[i] = -(cm[i] * scale[i]), i < r: the epilogue of the transform GEMM */
+int grl_pca_affine(const float* cm, const float* lam, int r, float* scale, float* shift, void* stream);
+/* out[i][j] = y[i][j] * sqrtf(lam[j]) (the whitening undone), y [rows][ldy], out [rows][ldo], r columns */
+int grl_pca_colscale(const float* y, int64_t ldy, int rows, int r, const float* lam, float* out, int64_t ldo, void* stream);
+/* scikit-learn's init='pca' of t-SNE: out [rows][2] = y[i][0..1] / sqrtf(var) * 1e-4f, var = sum_i (y[i][0] - mean)^2 / rows,
+ * mean = sum_i y[i][0] / rows; both sums: 1024 partial sums by i % 1024, each sequential from +0.0f, folded part[t] +=
+ * part[t + s], s = 512 .. 1.  One workgroup. */
+int grl_pca_tsne_init(const float* y, int64_t ldy, int rows, float* out, void* stream);
 
 /* ---- query expansion / database-side augmentation (expand.hip, engine.expand_from_lists / expand_features) ----
  * out[i] = (x[i] + sum_p w_p * bank[j_p]) / (1 + sum_p w_p): a gather and a weighted sum over feature rows, without
