@@ -202,6 +202,14 @@ _SIGNATURES = {
     'grl_pca_colscale': ([_fp, _i64, C.c_int, C.c_int, _fp, _fp, _i64, _fp], C.c_int),
     'grl_pca_tsne_init': ([_fp, _i64, C.c_int, _fp, _fp], C.c_int),
     'grl_expand_rows': ([_fp, _i64, _fp, _i64, _fp, _fp, _i64] + [C.c_int] * 7 + [_fp, _i64, _fp], C.c_int),
+    # diffusion on the mutual-kNN graph (diffusion.hip)
+    'grl_diffusion_mutual': ([_fp, _fp, _i64, C.c_int, C.c_int, C.c_int, _fp, _fp, _i64, _fp, _fp], C.c_int),
+    'grl_diffusion_part_rows': ([], C.c_int),
+    'grl_diffusion_apply': ([_fp, _fp, _i64, C.c_int, C.c_int, _fp, C.c_int, C.c_float, _fp, _fp, _fp], C.c_int),
+    'grl_diffusion_seed': ([_fp, _fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp], C.c_int),
+    'grl_diffusion_workspace_floats': ([C.c_int, C.c_int], _i64),
+    'grl_diffusion_solve': ([_fp, _fp, _i64, C.c_int, C.c_int, _fp, C.c_int, C.c_float, C.c_int, _fp, _fp, _fp], C.c_int),
+    'grl_diffusion_transpose': ([_fp, C.c_int, C.c_int, C.c_int, _fp, _i64, _fp], C.c_int),
     'grl_verify_fold': ([_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
     'grl_verify_rows': ([_fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, _fp],
                         C.c_int),

@@ -3945,3 +3945,243 @@ def pca_orthonormalize(w):
     host = tail[:8].cpu()
     return PcaOrth(buf[:, :m].contiguous(), float(host.view(torch.float32)[0]), _PCA_PIVOT_CAUSE.get(int(host[1]), 0),
                    int(host[2]), int(host[3]))
+
+
+# ----------------------------------------------------------------------------
+# diffusion (manifold ranking) on the gallery's mutual-kNN graph (diffusion.hip)
+# ----------------------------------------------------------------------------
+DIFFUSION_K_MAX = 128
+DIFFUSION_GAMMA_MAX = 8
+
+
+class DiffusionGraph(object):
+    """The symmetric, degree-normalised mutual-kNN graph of ``diffusion_graph`` in a fixed-width (ELL) layout: ``idx``
+    int32 [n, k] (row i's k nearest other rows in ``search``'s order, -1 = padding), ``weight`` float32 [n, k] (S of
+    (I - alpha S) f = y: a / (sqrt(deg_i) sqrt(deg_j)) with a = min(w_ij, w_ji) on a mutual edge, 0 elsewhere) and
+    ``deg`` float32 [n] (the row sums of a), all on the device; ``n``, ``k``, ``gamma``; ``n_edges`` = the non-zero slots
+    (every undirected edge counts twice), ``n_isolated`` = the rows without one."""
+
+    def __init__(self, idx, weight, deg, n, k, gamma):
+        self.idx, self.weight, self.deg = idx, weight, deg
+        self.n, self.k, self.gamma = n, k, gamma
+        self.n_edges = int(torch.count_nonzero(weight)) if n else 0
+        self.n_isolated = int((deg == 0).sum()) if n else 0
+
+    def __repr__(self):
+        return 'DiffusionGraph(n=%d, k=%d, gamma=%d, n_edges=%d, n_isolated=%d)' % (self.n, self.k, self.gamma,
+                                                                                    self.n_edges, self.n_isolated)
+
+
+def _diffusion_int(v, lo, hi, what, name):
+    import numbers
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= hi:
+        raise ValueError('%s: %s must be an integer in %d..%s (got %r)' % (what, name, lo, hi if hi < 2 ** 31 - 1 else '', v))
+    return int(v)
+
+
+def _diffusion_graph_args(k, gamma, what):
+    return (_diffusion_int(k, 1, DIFFUSION_K_MAX, what, 'k'), _diffusion_int(gamma, 1, DIFFUSION_GAMMA_MAX, what, 'gamma'))
+
+
+def _diffusion_solve_args(alpha, n_iter, what):
+    import numbers
+    if isinstance(alpha, bool) or not isinstance(alpha, numbers.Real) or not 0.0 <= alpha < 1.0:    # (NaN fails both)
+        raise ValueError('%s: alpha must be a number in [0, 1) (got %r)' % (what, alpha))
+    if not 0.0 <= float(torch.tensor(float(alpha), dtype=torch.float32)) < 1.0:
+        raise ValueError('%s: alpha must stay below 1 in float32 (got %r)' % (what, alpha))
+    return float(alpha), _diffusion_int(n_iter, 0, 2 ** 31 - 1, what, 'n_iter')
+
+
+def _diffusion_kq(kq, k, what):
+    kq = _diffusion_int(kq, 1, DIFFUSION_K_MAX, what, 'kq')
+    if kq > k:
+        raise ValueError('%s: kq must not exceed k (got kq = %d, k = %d)' % (what, kq, k))
+    return kq
+
+
+def _diffusion_rows(t, what, name):
+    """``t`` as a contiguous float32 device matrix, or ValueError."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() >= 2):
+        raise ValueError('%s: %s must be a float32 matrix on a HIP device (got %s)'
+                         % (what, name, getattr(t, 'device', type(t))))
+    return t.contiguous().view(t.shape[0], int(torch.Size(t.shape[1:]).numel()))
+
+
+def _diffusion_metric(metric, what):
+    if isinstance(metric, VerifyMetric):
+        raise ValueError('%s: a verify_metric is the signed logit of modified query rows against gallery rows, not a '
+                         "distance between two samples of one set; the graph is built by 'cosine'" % what)
+    if metric != 'cosine':
+        raise ValueError("%s: metric must be 'cosine' (got %r): the edge weights are powers of the cosine similarity"
+                         % (what, metric))
+
+
+def _diffusion_check_graph(graph, what):
+    if not isinstance(graph, DiffusionGraph):
+        raise ValueError('%s: graph must be the DiffusionGraph of diffusion_graph (got %r)' % (what, type(graph)))
+
+
+def diffusion_graph(gf, k=50, gamma=3, metric='cosine', block_cols=None, block_bytes=None):
+    """The mutual-kNN graph of the rows of ``gf`` [n, d] (unit norm) for ``diffusion_solve`` / ``diffusion_search``, as a
+    ``DiffusionGraph``.  ``search(gf, gf, k + 1)`` by cosine gives every row's list; the row itself is dropped from it
+    (the last entry when duplicates that tie before it pushed the row out of its own list).  Weight of a neighbour:
+    w = max(q . g, 0) ** gamma by gamma - 1 products (``gamma`` an integer in 1..8, as ``expand_features`` restricts its
+    alpha); an edge exists where i and j are in each other's lists and carries min(w_ij, w_ji), which makes the matrix
+    symmetric bit for bit; S = D^-1/2 A D^-1/2.  1 <= k <= 128.  Memory: the lists and O(n k); the n x n matrix is never
+    built (``block_cols`` / ``block_bytes`` are ``search``'s).  Not sharded: under torch.distributed ``search`` is
+    collective and returns identical lists on every rank, and every rank builds the full, identical graph, as ``cluster``
+    does."""
+    what = 'diffusion_graph'
+    k, gamma = _diffusion_graph_args(k, gamma, what)
+    _diffusion_metric(metric, what)
+    gf = _diffusion_rows(gf, what, 'gf')
+    n, dev = gf.shape[0], gf.device
+    sdist = sidx = None
+    if n:
+        sdist, sidx = search(gf, gf, k + 1, block_cols=block_cols, block_bytes=block_bytes)
+    idx = torch.full((n, k), -1, dtype=torch.int32, device=dev)           # (after the search: its block is gone by now)
+    weight = torch.zeros((n, k), dtype=torch.float32, device=dev)
+    deg = torch.zeros((n,), dtype=torch.float32, device=dev)
+    if n:
+        _call('grl_diffusion_mutual', ptr(sidx), ptr(sdist), k + 1, n, k, gamma, ptr(idx), ptr(weight), k, ptr(deg))
+    return DiffusionGraph(idx, weight, deg, n, k, gamma)
+
+
+def _diffusion_block(graph, seed_idx, seed_val, seed_gamma, alpha, n_iter, negate):
+    """One block of queries: scatter the seeds into y [n][B], solve, and return x transposed, [B][n] (negated for the
+    ranking kernels).  seed_gamma 0: ``seed_val`` holds the values; >= 1: search's cosine distances."""
+    n, B, dev = graph.n, seed_idx.shape[0], graph.idx.device
+    lib = _lib.load()
+    y = torch.empty((n, B), dtype=torch.float32, device=dev)
+    x = torch.empty((n, B), dtype=torch.float32, device=dev)
+    ws = torch.empty((lib.grl_diffusion_workspace_floats(n, B),), dtype=torch.float32, device=dev)
+    _call('grl_diffusion_seed', ptr(seed_idx), ptr(seed_val), seed_idx.shape[1], B, seed_idx.shape[1], n, seed_gamma,
+          ptr(y))
+    _call('grl_diffusion_solve', ptr(graph.idx), ptr(graph.weight), graph.k, n, graph.k, ptr(y), B, alpha, n_iter, ptr(x),
+          ptr(ws))
+    del y, ws
+    out = torch.empty((B, n), dtype=torch.float32, device=dev)
+    _call('grl_diffusion_transpose', ptr(x), n, B, 1 if negate else 0, ptr(out), n)
+    return out
+
+
+def diffusion_solve(graph, seed_idx, seed_val, alpha=0.99, n_iter=20):
+    """``f`` float32 [nq_block, n]: row q solves (I - alpha S) f = y_q on ``graph`` for y_q = ``seed_val[q]`` at the nodes
+    ``seed_idx[q]`` (int64 [nq_block, kq] on the device, -1 = padding, distinct per row) and 0 elsewhere, by exactly
+    ``n_iter`` iterations of plain conjugate gradients from x0 = 0 (the matrix is symmetric positive definite: S's
+    spectrum lies in [-1, 1] and 0 <= alpha < 1).  All columns advance together, [n][nq_block] node-major, and are
+    independent; a column whose residual is 0 (or whose p . Ap is not positive and finite) freezes, so a zero seed column
+    stays zero and alpha = 0 returns y exactly.  n_iter = 0 returns zeros.  Every sum has a fixed order
+    (tests/diffusion_ref.py reproduces the result bit for bit, and two calls give the same bits).  This is the low-level
+    solve for one block of queries: memory is 5 n nq_block floats."""
+    what = 'diffusion_solve'
+    _diffusion_check_graph(graph, what)
+    alpha, n_iter = _diffusion_solve_args(alpha, n_iter, what)
+    if not (torch.is_tensor(seed_idx) and seed_idx.is_cuda and seed_idx.dtype == torch.int64 and seed_idx.dim() == 2):
+        raise ValueError('%s: seed_idx must be an int64 device matrix [nq_block, kq]' % what)
+    if not (torch.is_tensor(seed_val) and seed_val.is_cuda and seed_val.dtype == torch.float32
+            and tuple(seed_val.shape) == tuple(seed_idx.shape)):
+        raise ValueError('%s: seed_val must be a float32 device matrix of seed_idx\'s shape' % what)
+    B, n = seed_idx.shape[0], graph.n
+    if B == 0 or n == 0 or seed_idx.shape[1] == 0:
+        return torch.zeros((B, n), dtype=torch.float32, device=graph.idx.device)
+    return _diffusion_block(graph, seed_idx.contiguous(), seed_val.contiguous(), 0, alpha, n_iter, False)
+
+
+def _diffusion_query_block(query_block, block_bytes, n, nq, vectors, what):
+    """Queries per block: ``query_block``, or what fits ``block_bytes`` (GRL_SEARCH_BLOCK_BYTES) counting ``vectors``
+    [n][B] float arrays -- a multiple of 64 from 256 on, which keeps the 16-byte accesses of the state."""
+    if query_block is not None:
+        return _diffusion_int(query_block, 1, 2 ** 31 - 1, what, 'query_block')
+    budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
+    B = max(1, min(nq, budget // (4 * vectors * max(n, 1))))
+    return B // 64 * 64 if B >= 256 else B
+
+
+def _diffusion_prepare(qf, gf, graph, kq, alpha, n_iter, k, gamma, what):
+    if graph is None:
+        k, gamma = _diffusion_graph_args(k, gamma, what)
+    else:
+        _diffusion_check_graph(graph, what)
+        k, gamma = graph.k, graph.gamma
+    kq = _diffusion_kq(kq, k, what)
+    alpha, n_iter = _diffusion_solve_args(alpha, n_iter, what)
+    qf, gf = _diffusion_rows(qf, what, 'qf'), _diffusion_rows(gf, what, 'gf')
+    if qf.shape[1] != gf.shape[1]:
+        raise ValueError('qf and gf have different feature sizes (%d, %d)' % (qf.shape[1], gf.shape[1]))
+    if graph is not None and graph.n != gf.shape[0]:
+        raise ValueError('%s: the graph has %d nodes, gf has %d rows' % (what, graph.n, gf.shape[0]))
+    return qf, gf, kq, alpha, n_iter, k, gamma
+
+
+def _diffusion_blocks(qf, gf, graph, kq, alpha, n_iter, B, block_bytes=None):
+    """(q0, q1, the [q1 - q0][n] block of -f) per block of ``B`` queries.  The seeds are ``search(qf, gf, kq)`` with no
+    junk rule: that rule belongs to the final ranking only, as in re-ranking."""
+    sdist, sidx = search(qf, gf, kq, block_bytes=block_bytes)
+    for q0 in range(0, qf.shape[0], B):
+        q1 = min(q0 + B, qf.shape[0])
+        yield q0, q1, _diffusion_block(graph, sidx[q0:q1].contiguous(), sdist[q0:q1].contiguous(), graph.gamma, alpha,
+                                       n_iter, True)
+
+
+def diffusion_search(qf, gf, k_out, graph=None, kq=10, alpha=0.99, n_iter=20, k=50, gamma=3, exclude=None,
+                     query_block=None, block_bytes=None):
+    """Diffusion re-ranking (Zhou et al., "Ranking on data manifolds"; Iscen et al., CVPR 2017): each query's ``k_out``
+    best gallery entries under the scores f of (I - alpha S) f = y, ``(score [nq, k_out] float32 = -f, idx [nq, k_out]
+    int64)`` on the device, ascending in -f, ties to the smaller gallery index, padded as ``search`` pads (index -1,
+    +inf).  S is ``graph`` (``diffusion_graph(gf, k, gamma)`` when None; a prebuilt graph is reused and brings its own k
+    and gamma); y_q holds max(q . g, 0) ** gamma at the query's ``kq`` nearest gallery rows (kq <= k) and 0 elsewhere; the
+    solve is ``diffusion_solve``'s (``n_iter`` conjugate-gradient iterations; 0 leaves f = 0 and the ranking is the index
+    order).  ``exclude`` has ``search``'s meaning and is applied to the final ranking only.  Queries are processed in
+    blocks of ``query_block`` columns (default: what fits ``block_bytes`` / GRL_SEARCH_BLOCK_BYTES, counting the four
+    CG vectors and the transposed block); every block size gives the same bits.  Memory is O(n k + n B): no nq x n and no
+    n x n tensor is allocated.  Not sharded: under torch.distributed every rank computes the full, identical result, as
+    ``cluster`` does (the ``search`` calls inside are collective)."""
+    what = 'diffusion_search'
+    if not 1 <= int(k_out) <= SEARCH_K_MAX:
+        raise ValueError('%s: k_out must be in 1..%d (got %r)' % (what, SEARCH_K_MAX, k_out))
+    k_out = int(k_out)
+    qf, gf, kq, alpha, n_iter, k, gamma = _diffusion_prepare(qf, gf, graph, kq, alpha, n_iter, k, gamma, what)
+    nq, n, dev = qf.shape[0], gf.shape[0], qf.device
+    junk = _junk_ids(exclude, nq, n, dev)
+    run_key = torch.full((nq, k_out), -1, dtype=torch.int64, device=dev)
+    run_val = torch.full((nq, k_out), float('inf'), dtype=torch.float32, device=dev)
+    if nq and n:
+        B = _diffusion_query_block(query_block, block_bytes, n, nq, 5, what)
+        if graph is None:
+            graph = diffusion_graph(gf, k, gamma, block_bytes=block_bytes)
+        for q0, q1, d in _diffusion_blocks(qf, gf, graph, kq, alpha, n_iter, B, block_bytes):
+            if junk is None:
+                _call('grl_topk_block', ptr(d), n, None, 0, q1 - q0, n, 0, k_out, ptr(run_key[q0:q1]), ptr(run_val[q0:q1]))
+            else:
+                _call('grl_topk_block_filtered', ptr(d), n, None, 0, q1 - q0, n, 0, k_out, ptr(run_key[q0:q1]),
+                      ptr(run_val[q0:q1]), ptr(junk[0][q0:q1]), ptr(junk[1][q0:q1]), ptr(junk[2]), ptr(junk[3]))
+    idx = run_key & 0xffffffff
+    idx[idx == 0xffffffff] = -1
+    return run_val, idx
+
+
+def diffusion_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, graph=None, kq=10, alpha=0.99, n_iter=20,
+                                k=50, gamma=3, max_rank=100, query_block=None, block_bytes=None):
+    """``rank_metrics(rank_rows(-f), ...)`` of the diffusion scores of ``diffusion_search`` without the nq x n matrix:
+    (cmc[max_rank] float32, mAP float) of eva_functions.evaluate.  Per block of ``query_block`` queries the [B][n] block of
+    -f is ranked by ``rank_rows`` and scored by grl_rank_metrics (the junk rule: same pid AND camera); the per-query (first
+    match rank, #matches, AP) are concatenated and averaged once, so every block size gives the same result.  The default
+    block also counts the block's int32 argsort.  Not sharded (see ``diffusion_search``)."""
+    what = 'diffusion_metrics_streaming'
+    qf, gf, kq, alpha, n_iter, k, gamma = _diffusion_prepare(qf, gf, graph, kq, alpha, n_iter, k, gamma, what)
+    nq, n, dev = qf.shape[0], gf.shape[0], qf.device
+    qp, qc = _ids(q_pids, nq, 'q_pids', dev), _ids(q_camids, nq, 'q_camids', dev)
+    gp, gc = _ids(g_pids, n, 'g_pids', dev), _ids(g_camids, n, 'g_camids', dev)
+    first = torch.full((nq,), -1, dtype=torch.int32, device=dev)
+    nhit = torch.zeros(nq, dtype=torch.int32, device=dev)
+    ap = torch.zeros(nq, dtype=torch.float64, device=dev)
+    if nq and n:
+        B = _diffusion_query_block(query_block, block_bytes, n, nq, 6, what)
+        if graph is None:
+            graph = diffusion_graph(gf, k, gamma, block_bytes=block_bytes)
+        for q0, q1, d in _diffusion_blocks(qf, gf, graph, kq, alpha, n_iter, B, block_bytes):
+            order = rank_rows(d)
+            _call('grl_rank_metrics', ptr(order), n, ptr(qp[q0:q1]), ptr(qc[q0:q1]), ptr(gp), ptr(gc), q1 - q0, n,
+                  ptr(first[q0:q1]), ptr(nhit[q0:q1]), ptr(ap[q0:q1]))
+    return _cmc_map(first, nhit, ap, n, max_rank)

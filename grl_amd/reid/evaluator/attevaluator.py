@@ -442,6 +442,48 @@ def _pca_report(knob, qf, gf, path):
     return engine._pad_features(fit.transform(qf, whiten)), engine._pad_features(fit.transform(gf, whiten))
 
 
+def parse_diffusion_knob(name, value):
+    """``GRL_EVAL_DIFFUSION``: unset or empty -> None (off); "k", "k,kq", "k,kq,alpha" or "k,kq,alpha,n_iter" -> (k, kq,
+    alpha, n_iter) with integers k in 1..128 (graph neighbours) and kq in 1..k (query seeds; default 10, or k when k is
+    smaller), a float alpha in [0, 1) (default 0.99) and an integer n_iter >= 0 (default 20; engine.diffusion_search).
+    Anything else is a ValueError that names the variable."""
+    if value is None or not value.strip():
+        return None
+    parts = [p.strip() for p in value.split(',')]
+    try:
+        if len(parts) > 4:
+            raise ValueError
+        k = int(parts[0])
+        kq = int(parts[1]) if len(parts) >= 2 else min(10, k)
+        alpha = float(parts[2]) if len(parts) >= 3 else 0.99
+        n_iter = int(parts[3]) if len(parts) == 4 else 20
+    except ValueError:
+        raise ValueError('%s must be "k[,kq[,alpha[,n_iter]]]" with integers k, kq and n_iter and a float alpha (got %r)'
+                         % (name, value))
+    if not 1 <= k <= engine.DIFFUSION_K_MAX or not 1 <= kq <= k or not 0.0 <= alpha < 1.0 \
+            or not 0 <= n_iter <= 2 ** 31 - 1:              # (a NaN alpha fails both comparisons)
+        raise ValueError('%s: k must be in 1..%d, kq in 1..k, alpha in [0, 1) and n_iter >= 0 (got %r)'
+                         % (name, engine.DIFFUSION_K_MAX, value))
+    return k, kq, alpha, n_iter
+
+
+def _diffusion_report(knob, gf, path):
+    """GRL_EVAL_DIFFUSION: the mutual-kNN graph of the query-prepended gallery ``gf`` (engine.diffusion_graph, gamma = 3)
+    -- one printed line with its edges and isolated rows, and ``path + 'diffusion.json'`` (rank 0 alone writes; strict
+    JSON).  Returns the graph, which the ranking and ``--visual`` reuse."""
+    import json
+    k, kq, alpha, n_iter = knob
+    graph = engine.diffusion_graph(gf, k)
+    print('Diffusion: k = {}, kq = {}, alpha = {:g}, n_iter = {}, gamma = {}: {} edges, {} isolated of {}'.format(
+        k, kq, alpha, n_iter, graph.gamma, graph.n_edges, graph.n_isolated, graph.n))
+    if grl_dist._rank_world(None, None)[0] == 0:
+        js = {'k': k, 'kq': kq, 'alpha': alpha, 'n_iter': n_iter, 'gamma': graph.gamma, 'metric': 'cosine', 'n': graph.n,
+              'n_edges': graph.n_edges, 'n_isolated': graph.n_isolated}
+        with open((path or '') + 'diffusion.json', 'w') as fh:
+            json.dump(js, fh, allow_nan=False)
+    return graph
+
+
 def parse_silhouette_knob(name, value):
     """``GRL_EVAL_SILHOUETTE``: unset or empty -> None (off); "1" or "cosine", or "euclidean", optionally followed by
     ",drop" or ",singleton" -> (metric, noise) for engine.silhouette (default noise: 'singleton', the convention of
@@ -517,7 +559,7 @@ class ATTEvaluator(object):
         return feat, np.asarray(pids_all), np.asarray(cams_all)
 
     def _visualize(self, query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, rerank, topk=10,
-                   metric='cosine'):
+                   metric='cosine', diffusion=None):
         """``visual=1``: the ranked-results folders of visualize_ranked_results in ``path + 'visual'`` for the query
         positions of GRL_VISUAL_QUERIES (comma list; default 4, the reference's visual_id), and ``ranked.json`` in
         the same folder: {query position: [[gallery position, pid, camid, distance], ...]} (a non-finite distance is
@@ -525,7 +567,8 @@ class ATTEvaluator(object):
         ``g_camids`` carry the prepended queries, so gallery positions below nq are queries.  The lists are the
         junk-filtered top-k of engine.search / engine.rerank_search (``exclude=``): no matrix, no argsort.  Those
         calls are collective under torch.distributed; rank 0 alone writes.  ``metric``: engine.search's (the
-        distances of ranked.json are that metric's)."""
+        distances of ranked.json are that metric's).  ``diffusion`` = (graph, kq, alpha, n_iter): the lists are
+        engine.diffusion_search's and the distances of ranked.json its scores -f."""
         import json
         if query is None or gallery is None:
             raise ValueError('visual=1 needs the query and gallery tuple lists (img_path(s), pid, camid)')
@@ -540,7 +583,10 @@ class ATTEvaluator(object):
             raise ValueError('GRL_VISUAL_QUERIES must be a comma list of query positions (got %r)' % spec)
         wanted = [q for q in asked if 0 <= q < nq]
         ids = (q_pids, g_pids, q_camids, g_camids)
-        if rerank:
+        if diffusion is not None:
+            graph, kq, alpha, n_iter = diffusion
+            dist, idx = engine.diffusion_search(qf, gf, topk, graph=graph, kq=kq, alpha=alpha, n_iter=n_iter, exclude=ids)
+        elif rerank:
             dist, idx = engine.rerank_search(qf, gf, topk, exclude=ids)
         else:
             dist, idx = engine.search(qf, gf, topk, metric=metric, exclude=ids)
@@ -627,6 +673,22 @@ class ATTEvaluator(object):
             raise ValueError('GRL_EVAL_PCA cannot be combined with GRL_EVAL_METRIC=%s: the verification head reads '
                              'fixed slices of the raw feature rows, which a change of basis does not keep (unset one '
                              'of them)' % os.environ['GRL_EVAL_METRIC'].strip())
+        # diffusion re-ranking on the gallery's mutual-kNN graph, off by default (engine.diffusion_search): replaces the
+        # plain cosine ranking after PCA / DBA / QE, with GRL_EVAL_STREAM set or not (it never builds the matrix)
+        diffusion_knob = parse_diffusion_knob('GRL_EVAL_DIFFUSION', os.environ.get('GRL_EVAL_DIFFUSION'))
+        if diffusion_knob is not None and rerank:
+            raise ValueError('GRL_EVAL_DIFFUSION cannot re-rank: k-reciprocal re-ranking works on distance matrices, and '
+                             'the diffusion scores are the solution of a linear system on the gallery graph, not a '
+                             'distance (unset GRL_EVAL_DIFFUSION or evaluate with rerank=0)')
+        if diffusion_knob is not None and knob is not None:
+            raise ValueError('GRL_EVAL_DIFFUSION cannot be combined with GRL_EVAL_METRIC=%s: the graph\'s edge weights are '
+                             'powers of the cosine similarity between two samples of one set, and the verification '
+                             'head\'s distance is a signed logit of modified query rows against gallery rows (unset one '
+                             'of them)' % os.environ['GRL_EVAL_METRIC'].strip())
+        if diffusion_knob is not None and roc_bits:
+            raise ValueError('GRL_EVAL_DIFFUSION cannot be combined with GRL_EVAL_ROC: the pair-level figures are taken '
+                             'from distance blocks, and the diffusion scores exist per block of queries only (unset one '
+                             'of them)')
         qf, q_pids, q_camids = self.extract_feature(query_loader)
         print('Done, obtained {}-by-{} matrix'.format(qf.size(0), qf.size(1)))
         gf, g_pids, g_camids = self.extract_feature(gallery_loader)
@@ -670,6 +732,15 @@ class ATTEvaluator(object):
             if tsne_knob is not None:
                 lines = tuple(lines) + tuple(_tsne_report(tsne_knob, gf, ids, path))
             return lines
+        if diffusion_knob is not None:
+            graph = _diffusion_report(diffusion_knob, gf, path)
+            k, kq, alpha, n_iter = diffusion_knob
+            if visual:
+                self._visualize(query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, 0,
+                                diffusion=(graph, kq, alpha, n_iter))
+            return _report(*engine.diffusion_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, graph=graph,
+                                                               kq=kq, alpha=alpha, n_iter=n_iter),
+                           roc_lines=extra(roc_lines))
         if visual:
             self._visualize(query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, rerank)
         if rerank_stream:

@@ -43,7 +43,8 @@ const char* grl_last_error(void);
  * grl_rrs_place, grl_rrs_transpose) among them, grl_topk_block_filtered, grl_expand_rows, the grl_verify_* entry points,
  * grl_pair_hist_block, the clustering entry points grl_cluster_*, the k-means entry points grl_kmeans_* /
  * grl_segment_rowsum, grl_jaccard_edges, the silhouette entry points grl_silhouette_*, the HDBSCAN entry points
- * grl_hdbscan_*, the t-SNE entry points grl_tsne_* and the PCA entry points grl_pca_*. */
+ * grl_hdbscan_*, the t-SNE entry points grl_tsne_*, the PCA entry points grl_pca_* and the diffusion entry points
+ * grl_diffusion_*. */
 #define GRL_ABI_VERSION 10
 int grl_abi_version(void);
 /* `waiter` (a hipStream_t) waits for everything enqueued on `signaler` so far: hipEventRecord + hipStreamWaitEvent on a
@@ -885,6 +886,45 @@ int grl_pca_tsne_init(const float* y, int64_t ldy, int rows, float* out, void* s
 int grl_expand_rows(const float* x, int64_t ldx, const float* bank, int64_t ldb, const int64_t* idx, const float* dist,
                     int64_t ldl, int n, int nb, int d, int L, int m, int alpha, int skip_self, float* out, int64_t ldo,
                     void* stream);
+
+/* ---- diffusion (manifold ranking) on the gallery's mutual-kNN graph (diffusion.hip, engine.diffusion_graph /
+ * diffusion_solve / diffusion_search) ----
+ * The graph is a fixed-width ELL layout: idx int32 / S fp32 [n][ldg] (k used, 1 <= k <= 128).  The solver's state is
+ * [n][B] fp32, node-major, the B query columns of a node contiguous.  Every operation is one of + - x / sqrt, correctly
+ * rounded, no fma; every sum has a prescribed order; tests/diffusion_ref.py is this section in numpy float32, bit for bit.
+ * Dot products over the rows: a wave sums 16 consecutive rows in row order from +0, a workgroup adds its 4 wave sums in
+ * wave order into one partial per grl_diffusion_part_rows() = 64 rows, the partials are added in row order from +0.
+ *
+ * grl_diffusion_mutual: sidx int64 / sdist fp32 [n][ldl] hold the k + 1 entries per row of engine.search(gf, gf, k + 1)
+ * by cosine (distinct indices, -1 = padding).  Slot t of row i is list position t + (t >= selfpos), selfpos = the first
+ * position that holds i (k when there is none: the last entry is dropped); an index outside [0, n), or a further entry
+ * equal to i, is padding (idx -1).  w = s, then gamma - 1 times w = w * s, s = dist < 0 ? -dist : 0 (gamma in 1..8).
+ * a[i][t] = min(w_ij, w_ji), j = idx[i][t], if i occurs in row j's list at a position that row j keeps (its first
+ * occurrence counts), else 0; deg[i] = a[i][0] + a[i][1] + ... from +0; weight[i][t] = a / (sqrt(deg[i]) * sqrt(deg[j])),
+ * 0 where a is 0.  Columns of idx / weight beyond k are left untouched. */
+int grl_diffusion_mutual(const int64_t* sidx, const float* sdist, int64_t ldl, int n, int k, int gamma, int32_t* idx,
+                         float* weight, int64_t ldo, float* deg, void* stream);
+int grl_diffusion_part_rows(void);
+/* Ap[i][b] = p[i][b] - (alpha * acc), acc = the sum over the slots t with S[i][t] != 0 (and 0 <= idx[i][t] < n) in slot
+ * order from +0 of S[i][t] * p[idx[i][t]][b].  part [ceil(n / 64)][B] = the partials of p . Ap per column (see above).
+ * Ap must not be p.  16-byte accesses when B % 4 == 0, B >= 256 and both pointers allow them. */
+int grl_diffusion_apply(const int32_t* idx, const float* S, int64_t ldg, int n, int k, const float* p, int B, float alpha,
+                        float* Ap, float* part, void* stream);
+/* y [n][B] = 0, then per column q and entry t < kq in list order y[seed_idx[q][t]][q] = v (gamma == 0) or
+ * max(-v, 0)^gamma by gamma - 1 products (gamma in 1..8: v is search's cosine distance), v = seed_val[q][t]; an index
+ * outside [0, n) is padding.  seed_idx int64 / seed_val fp32 [B][lds]. */
+int grl_diffusion_seed(const int64_t* seed_idx, const float* seed_val, int64_t lds, int B, int kq, int n, int gamma,
+                       float* y, void* stream);
+/* Plain conjugate gradients on (I - alpha S) x = y per column: x0 = 0, r0 = p0 = y, exactly n_iter iterations of
+ *   Ap (grl_diffusion_apply), a = rr / (p . Ap), x = x + (a * p), r = r - (a * Ap), b = rr' / rr, p = r + (b * p)
+ * with rr = r . r reduced as above.  A column whose rr is not a positive finite number, or whose p . Ap is <= 0 or not
+ * finite, freezes: its x, r and p are no longer written.  y is overwritten (it becomes r); x [n][B] is the result; ws holds
+ * grl_diffusion_workspace_floats(n, B) floats, 16-byte aligned.  alpha in [0, 1), n_iter >= 0 (0: x = 0). */
+int64_t grl_diffusion_workspace_floats(int n, int B);
+int grl_diffusion_solve(const int32_t* idx, const float* S, int64_t ldg, int n, int k, float* y, int B, float alpha,
+                        int n_iter, float* x, float* ws, void* stream);
+/* out [B][ldo] (n used) = x [n][B] transposed, negated when negate != 0: the rows grl_topk_block / grl_row_argsort rank */
+int grl_diffusion_transpose(const float* x, int n, int B, int negate, float* out, int64_t ldo, void* stream);
 
 /* ---- ranking by the Siamese verification head (verify.hip, engine.verify_metric / verify_dist) ----
  * In eval mode classifierBN -> classifierlinear on (p - g)^2 is affine in (p - g)^2; the class-1 minus class-0 logit is
