@@ -210,6 +210,9 @@ _SIGNATURES = {
     'grl_diffusion_workspace_floats': ([C.c_int, C.c_int], _i64),
     'grl_diffusion_solve': ([_fp, _fp, _i64, C.c_int, C.c_int, _fp, C.c_int, C.c_float, C.c_int, _fp, _fp, _fp], C.c_int),
     'grl_diffusion_transpose': ([_fp, C.c_int, C.c_int, C.c_int, _fp, _i64, _fp], C.c_int),
+    # tracklet set distances from a block of clip distances (setdist.hip)
+    'grl_setdist_block': ([_fp, _i64, _fp, _fp, C.c_int, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _i64, _fp],
+                          C.c_int),
     'grl_verify_fold': ([_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
     'grl_verify_rows': ([_fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, _fp],
                         C.c_int),

@@ -4185,3 +4185,203 @@ def diffusion_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, grap
             _call('grl_rank_metrics', ptr(order), n, ptr(qp[q0:q1]), ptr(qc[q0:q1]), ptr(gp), ptr(gc), q1 - q0, n,
                   ptr(first[q0:q1]), ptr(nhit[q0:q1]), ptr(ap[q0:q1]))
     return _cmc_map(first, nhit, ap, n, max_rank)
+
+
+# ----------------------------------------------------------------------------
+# tracklet set distances over clip features (setdist.hip)
+# ----------------------------------------------------------------------------
+SET_REDUCE = {'min': 0, 'mean': 1, 'chamfer': 2, 'hausdorff': 3}     # GRL_SET_* of include/grl_hip.h
+SET_METRICS = ('cosine', 'euclidean')
+SET_MAX_CLIPS = 1024                                                  # GRL_SET_MAX_CLIPS
+
+
+def _set_args(reduce, metric, what):
+    if reduce not in SET_REDUCE:
+        raise ValueError("%s: reduce must be 'min', 'mean', 'chamfer' or 'hausdorff' (got %r)" % (what, reduce))
+    if metric not in SET_METRICS:
+        raise ValueError("%s: metric must be 'cosine' or 'euclidean' (got %r)" % (what, metric))
+
+
+class TrackletSet(object):
+    """``n`` tracklets as their clips: ``clips`` [N, d] float32 on the device, the rows of a tracklet consecutive, and
+    ``counts`` [n], the clips per tracklet (1 .. 1024 each, N in all).  ``ptr`` (numpy int64 [n + 1]) / ``ptr_dev`` (the
+    same on the device): tracklet t owns the rows ptr[t] .. ptr[t + 1].  The rows are zero-padded to a multiple of 32
+    features when d is not one (``_pad_features``: +0 to every dot product and norm); ``d`` stays the width given.
+    ValueError: counts that are not integers in 1..1024 or do not add up to N (checked before the device is looked at)."""
+
+    def __init__(self, clips, counts):
+        import numpy as np
+        if not (torch.is_tensor(clips) and clips.dim() == 2):
+            raise ValueError('TrackletSet: clips must be a 2-d tensor [N, d] (got %s)'
+                             % (tuple(clips.shape) if torch.is_tensor(clips) else type(clips).__name__,))
+        c = np.asarray(counts)
+        if c.ndim != 1 or (c.size and c.dtype.kind not in 'iu'):
+            raise ValueError('TrackletSet: counts must be a list of integers (got %r)' % (counts,))
+        c = c.astype(np.int64)
+        if c.size and c.min() < 1:
+            raise ValueError('TrackletSet: every tracklet needs at least one clip (tracklet %d has %d)'
+                             % (int(c.argmin()), int(c.min())))
+        if c.size and c.max() > SET_MAX_CLIPS:
+            raise ValueError('TrackletSet: a tracklet may have at most %d clips (tracklet %d has %d)'
+                             % (SET_MAX_CLIPS, int(c.argmax()), int(c.max())))
+        if int(c.sum()) != clips.shape[0]:
+            raise ValueError('TrackletSet: the counts add up to %d clips, clips has %d rows' % (int(c.sum()), clips.shape[0]))
+        require_device(clips, 'clips')
+        self.n, self.d = int(c.size), int(clips.shape[1])
+        self.clips = _pad_features(clips)
+        self.counts = c
+        self.ptr = np.zeros(self.n + 1, np.int64)
+        np.cumsum(c, out=self.ptr[1:])
+        self.ptr_dev = torch.from_numpy(self.ptr).to(clips.device)
+
+    def mean_rows(self):
+        """[n, d]: the mean of every tracklet's clips through grl_group_mean, one call per tracklet -- ``rows_mean`` of
+        its rows, the row dense-mode evaluation ranks by today."""
+        x, w = self.clips, self.clips.shape[1]
+        y = _new((self.n, w), x)
+        for t in range(self.n):
+            a, b = int(self.ptr[t]), int(self.ptr[t + 1])
+            _call('grl_group_mean', ptr(x[a:b]), ptr(y[t:]), 1, b - a, w, w, C.c_float(1.0), 0)
+        return y if w == self.d else y[:, :self.d].contiguous()
+
+
+def _set_ranges(ptr_, t0, t1, cap):
+    """[t0, t1) cut into ranges of whole tracklets of at most ``cap`` clips each (one tracklet where it alone has more)."""
+    import numpy as np
+    out = []
+    while t0 < t1:
+        e = int(np.searchsorted(ptr_, ptr_[t0] + cap, side='right')) - 1
+        e = min(max(e, t0 + 1), t1)
+        out.append((t0, e))
+        t0 = e
+    return out
+
+
+class _SetBlocks(object):
+    """Column blocks of the tracklet x tracklet set distance of ``qset`` against the tracklets [lo, hi) of ``gset``: the
+    block-source contract of ``_ColumnBlocks`` (``spans``, ``block(c0, c1)``, ``qf``, ``nq``; a block comes back with the
+    same bits every time it is asked for) with spans in TRACKLET columns.  No tracklet is ever cut.  Without ``block_cols``
+    a span takes as many whole gallery tracklets as keep the [nq, c1 - c0] output block within ``block_bytes``
+    (GRL_SEARCH_BLOCK_BYTES).  Inside ``block`` the clip-level work is tiled over ranges of whole query tracklets and whole
+    gallery tracklets whose clip x clip scratch stays within ``block_bytes`` too (a pair of tracklets that alone exceeds it
+    is one tile: at most 4 MiB): per tile one fp32 distance GEMM of the clip rows into the scratch (NEGDOT / EUCLID, the
+    entries of cosin_dist / pairwise_distance_tensor of the clip tensors, bit for bit) and one grl_setdist_block that folds
+    every tracklet pair's cell into its entry of the block.  A cell's value does not depend on the tiling (include/grl_hip.h),
+    so neither does a block.  The 'euclidean' norms come once per set from grl_row_sqnorm."""
+
+    def __init__(self, qset, gset, reduce='chamfer', metric='cosine', block_cols=None, block_bytes=None, lo=0, hi=None):
+        _set_args(reduce, metric, '_SetBlocks')
+        if qset.clips.shape[1] != gset.clips.shape[1]:
+            raise ValueError('qset and gset have different feature sizes (%d, %d)' % (qset.d, gset.d))
+        hi = gset.n if hi is None else hi
+        self.qset, self.gset, self.reduce, self.metric = qset, gset, SET_REDUCE[reduce], metric
+        self.qf, self.nq, self.ng, self.lo = qset.clips, qset.n, gset.n, lo
+        self.budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
+        if block_cols is None:
+            block_cols = self.budget // (4 * max(self.nq, 1))
+        width = max(1, min(int(block_cols), hi - lo))
+        self.width = width
+        self.spans = [(c, min(c + width, hi)) for c in range(lo, hi, width)]
+        self.buf = _new((self.nq * width,), self.qf) if self.spans and self.nq else None
+        self.scratch = None
+        self.rn = self.cn = None
+        if metric == 'euclidean' and self.spans and self.nq:
+            k = self.qf.shape[1]
+            g0, g1 = int(gset.ptr[lo]), int(gset.ptr[hi])
+            self.rn, self.cn, self.cn0 = _new((qset.clips.shape[0],), self.qf), _new((g1 - g0,), self.qf), g0
+            _call('grl_row_sqnorm', ptr(self.qf), ptr(self.rn), qset.clips.shape[0], k, k)
+            _call('grl_row_sqnorm', ptr(gset.clips[g0:g1]), ptr(self.cn), g1 - g0, k, k)
+
+    def tiles(self, c0, c1):
+        """(a0, a1, b0, b1): the tracklet ranges of the GEMM tiles of the block [c0, c1), query ranges outermost."""
+        import math
+        qp, gp = self.qset.ptr, self.gset.ptr
+        cells = max(1, self.budget // 4)
+        gclips = int(gp[c1] - gp[c0])
+        qcap = max(math.isqrt(cells), cells // max(gclips, 1))
+        qranges = _set_ranges(qp, 0, self.nq, qcap)
+        qmax = max(int(qp[a1] - qp[a0]) for a0, a1 in qranges)
+        granges = _set_ranges(gp, c0, c1, max(1, cells // qmax))
+        return [(a0, a1, b0, b1) for a0, a1 in qranges for b0, b1 in granges]
+
+    def block(self, c0, c1):
+        n, k = c1 - c0, self.qf.shape[1]
+        out = self.buf[:self.nq * n].view(self.nq, n)
+        qs, gs = self.qset, self.gset
+        for a0, a1, b0, b1 in self.tiles(c0, c1):
+            q0, q1, g0, g1 = int(qs.ptr[a0]), int(qs.ptr[a1]), int(gs.ptr[b0]), int(gs.ptr[b1])
+            M, N = q1 - q0, g1 - g0
+            if self.scratch is None or self.scratch.numel() < M * N:
+                self.scratch = _new((M * N,), self.qf)
+            e = self.scratch[:M * N].view(M, N)
+            if self.metric == 'cosine':
+                gemm(qs.clips[q0:q1], gs.clips[g0:g1], e, M, N, k, epilogue=EPI_NEGDOT, math=MATH_F32)
+            else:
+                gemm(qs.clips[q0:q1], gs.clips[g0:g1], e, M, N, k, epilogue=EPI_EUCLID, rnorm=self.rn[q0:q1],
+                     cnorm=self.cn[g0 - self.cn0:g1 - self.cn0], math=MATH_F32)
+            _call('grl_setdist_block', ptr(e), N, qs.ptr.ctypes.data, ptr(qs.ptr_dev), a0, a1 - a0, gs.ptr.ctypes.data,
+                  ptr(gs.ptr_dev), b0, b1 - b0, self.reduce, ptr(out[a0:, b0 - c0:]), n)
+        return out
+
+
+def _set_pair(qset, gset, what):
+    if not (isinstance(qset, TrackletSet) and isinstance(gset, TrackletSet)):
+        raise ValueError('%s: qset and gset must be TrackletSet objects (got %s, %s)'
+                         % (what, type(qset).__name__, type(gset).__name__))
+
+
+def set_dist(qset, gset, reduce='chamfer', metric='cosine'):
+    """The materialised [nq, ng] float32 set distances between the tracklets of two ``TrackletSet``s, for small sets and
+    tests.  With e the clip distances of a tracklet pair (m x p; 'cosine' = the entries of cosin_dist, 'euclidean' = of
+    pairwise_distance_tensor of the clip tensors), rowmin[i] = min_j e[i][j] and colmin[j] = min_i e[i][j]:
+    'min' = the closest clip pair, 'mean' = the mean of e, 'chamfer' = (mean_i rowmin[i] + mean_j colmin[j]) / 2,
+    'hausdorff' = max(max_i rowmin[i], max_j colmin[j]).  min and max select exactly (-0 below +0), a NaN clip distance
+    makes its cell the canonical NaN, the sums run in the fixed fp32 order of include/grl_hip.h: tests/setdist_ref.py
+    gives the same bits from the clip matrix.  Only one clip x clip tile within GRL_SEARCH_BLOCK_BYTES exists at a time."""
+    _set_pair(qset, gset, 'set_dist')
+    _set_args(reduce, metric, 'set_dist')
+    if qset.n == 0 or gset.n == 0:
+        return torch.empty((qset.n, gset.n), dtype=torch.float32, device=qset.clips.device)
+    return _SetBlocks(qset, gset, reduce, metric, block_cols=gset.n).block(0, gset.n).clone()
+
+
+def set_search(qset, gset, k, reduce='chamfer', metric='cosine', exclude=None, block_cols=None, block_bytes=None):
+    """``search`` on the set distances D = set_dist(qset, gset, reduce, metric): ``(dist [nq, k] float32, idx [nq, k]
+    int64)``, bit for bit ``rank_rows(D)[:, :k]`` and D at those indices (search's tie, NaN and padding rules; ``exclude``
+    is search's junk rule over the TRACKLETS' ids), without D and without the clip x clip matrix: blocks of
+    ``block_cols`` gallery tracklets (default: what fits ``block_bytes`` / GRL_SEARCH_BLOCK_BYTES), each made from clip
+    tiles within the same budget.  k <= 1024.  Under torch.distributed the gallery tracklets are sharded over the ranks
+    and only the per-rank top-k lists are exchanged, as in ``search``."""
+    _set_pair(qset, gset, 'set_search')
+    _set_args(reduce, metric, 'set_search')
+    if not 1 <= int(k) <= SEARCH_K_MAX:
+        raise ValueError('set_search: k must be in 1..%d (got %r)' % (SEARCH_K_MAX, k))
+    junk = _junk_ids(exclude, qset.n, gset.n, qset.clips.device)
+    lo, hi, sharded = _shard(gset.n)
+    blocks = _SetBlocks(qset, gset, reduce, metric, block_cols, block_bytes, lo, hi)
+    return _search_blocks(blocks, qset.n, int(k), sharded, junk)
+
+
+def set_metrics_streaming(qset, gset, q_pids, g_pids, q_camids, g_camids, reduce='chamfer', metric='cosine', max_rank=100,
+                          block_cols=None, block_bytes=None):
+    """``rank_metrics(rank_rows(D), ...)`` for D = set_dist(qset, gset, reduce, metric) without D: (cmc[max_rank] float32,
+    mAP float) with rank_metrics_streaming's contract (first hit and #matches exact, CMC equal, mAP within 1e-12, at most
+    8192 gallery tracklets per query pid) and its exchange under torch.distributed (gallery tracklets sharded)."""
+    _set_pair(qset, gset, 'set_metrics_streaming')
+    _set_args(reduce, metric, 'set_metrics_streaming')
+    lo, hi, sharded = _shard(gset.n)
+    blocks = _SetBlocks(qset, gset, reduce, metric, block_cols, block_bytes, lo, hi)
+    first, nhit, ap = _rank_blocks(blocks, qset.n, gset.n, q_pids, g_pids, q_camids, g_camids, sharded)
+    return _cmc_map(first, nhit, ap, gset.n, max_rank)
+
+
+def set_pair_roc(qset, gset, q_pids, g_pids, q_camids, g_camids, reduce='chamfer', metric='cosine', bits=ROC_BITS_DEFAULT,
+                 block_cols=None, block_bytes=None):
+    """``pair_roc`` on the set distances: the ``PairRoc`` of ``pair_roc_matrix(set_dist(qset, gset, reduce, metric), ...)``,
+    bin for bin, without the matrix; sharded under torch.distributed as ``pair_roc`` is."""
+    _set_pair(qset, gset, 'set_pair_roc')
+    _set_args(reduce, metric, 'set_pair_roc')
+    bits = _roc_bits(bits, 'set_pair_roc')
+    lo, hi, sharded = _shard(gset.n)
+    blocks = _SetBlocks(qset, gset, reduce, metric, block_cols, block_bytes, lo, hi)
+    return _roc_blocks(blocks, qset.n, gset.n, q_pids, g_pids, q_camids, g_camids, bits, sharded)

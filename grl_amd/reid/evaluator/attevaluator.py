@@ -498,6 +498,19 @@ def parse_silhouette_knob(name, value):
     return metric, parts[1] if len(parts) == 2 else 'singleton'
 
 
+def parse_set_knob(name, value):
+    """``GRL_EVAL_SET``: unset or empty -> None (off); "min", "mean", "chamfer" or "hausdorff", optionally followed by
+    ",cosine" or ",euclidean" -> (reduce, metric) for engine.set_metrics_streaming (default metric: 'cosine').  Anything
+    else is a ValueError that names the variable."""
+    if value is None or not value.strip():
+        return None
+    parts = [p.strip() for p in value.split(',')]
+    if parts[0] not in engine.SET_REDUCE or len(parts) > 2 or (len(parts) == 2 and parts[1] not in engine.SET_METRICS):
+        raise ValueError('%s must be "min", "mean", "chamfer" or "hausdorff", optionally followed by ",cosine" or '
+                         '",euclidean" (got %r)' % (name, value))
+    return parts[0], parts[1] if len(parts) == 2 else 'cosine'
+
+
 class ATTEvaluator(object):
     def __init__(self, cnn_model, Siamese_model, only_eval):
         self.cnn_model = cnn_model
@@ -516,8 +529,23 @@ class ATTEvaluator(object):
     def _device(self):
         return next(self.cnn_model.parameters()).device
 
-    @torch.no_grad()
     def extract_feature(self, data_loader):
+        return self._extract(data_loader, False)[:3]
+
+    def extract_clip_features(self, data_loader):
+        """Dense mode (only_eval=True) without the clip average: ``(engine.TrackletSet, pids, camids)`` -- the clip rows
+        ``extract_feature`` averages, one tracklet per item of the loader in its order, and the ids that method returns.
+        Under torch.distributed the clip rows travel as the mean rows do (grl_dist.gather_feature_batches), the clip
+        counts in the place of the pids of that call."""
+        if not self.only_eval:
+            raise ValueError('extract_clip_features needs only_eval=True: rrs mode has one clip per tracklet')
+        _, pids, camids, tset = self._extract(data_loader, True)
+        return tset, pids, camids
+
+    @torch.no_grad()
+    def _extract(self, data_loader, want_clips):
+        """(mean-row features, pids, camids, TrackletSet or None) -- the first three are ``extract_feature``'s, made by
+        the same calls whether the clip rows are kept (``want_clips``, dense mode) or not."""
         self.cnn_model.eval()
         self.siamese_model.eval()
         dev = self._device()
@@ -528,6 +556,7 @@ class ATTEvaluator(object):
         own = [i for i in range(len(data_loader)) if i % world == rank]
         batches = grl_dist.shard_loader_batches(data_loader, rank, world)
         mine = []
+        mine_clips = []                     # want_clips: (batch index, clip rows [n, D], [n], [])
         pending, n_pending = [], 0          # dense mode: (batch index, clips [n,s,c,h,w], pids, camids)
 
         def flush():
@@ -537,6 +566,8 @@ class ATTEvaluator(object):
             off = 0
             for i, c, pids, camids in pending:
                 mine.append((i, engine.rows_mean(rows[off:off + c.size(0)]), pids, camids))
+                if want_clips:
+                    mine_clips.append((i, rows[off:off + c.size(0)], [int(c.size(0))], []))
                 off += c.size(0)
             del pending[:]
         # the next batch's host->device copy overlaps this batch's kernels (side HIP stream)
@@ -556,10 +587,15 @@ class ATTEvaluator(object):
         if pending:
             flush()
         feat, pids_all, cams_all = grl_dist.gather_feature_batches(mine, len(data_loader))
-        return feat, np.asarray(pids_all), np.asarray(cams_all)
+        pids_all, cams_all = np.asarray(pids_all), np.asarray(cams_all)
+        tset = None
+        if want_clips:
+            rows, counts, _ = grl_dist.gather_feature_batches(mine_clips, len(data_loader))
+            tset = engine.TrackletSet(rows, counts)
+        return feat, pids_all, cams_all, tset
 
     def _visualize(self, query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, rerank, topk=10,
-                   metric='cosine', diffusion=None):
+                   metric='cosine', diffusion=None, setdist=None):
         """``visual=1``: the ranked-results folders of visualize_ranked_results in ``path + 'visual'`` for the query
         positions of GRL_VISUAL_QUERIES (comma list; default 4, the reference's visual_id), and ``ranked.json`` in
         the same folder: {query position: [[gallery position, pid, camid, distance], ...]} (a non-finite distance is
@@ -568,7 +604,9 @@ class ATTEvaluator(object):
         junk-filtered top-k of engine.search / engine.rerank_search (``exclude=``): no matrix, no argsort.  Those
         calls are collective under torch.distributed; rank 0 alone writes.  ``metric``: engine.search's (the
         distances of ranked.json are that metric's).  ``diffusion`` = (graph, kq, alpha, n_iter): the lists are
-        engine.diffusion_search's and the distances of ranked.json its scores -f."""
+        engine.diffusion_search's and the distances of ranked.json its scores -f.  ``setdist`` = (qset, gset, reduce,
+        metric): the lists are engine.set_search's over the tracklets' clip sets and the distances of ranked.json the set
+        distances."""
         import json
         if query is None or gallery is None:
             raise ValueError('visual=1 needs the query and gallery tuple lists (img_path(s), pid, camid)')
@@ -583,7 +621,9 @@ class ATTEvaluator(object):
             raise ValueError('GRL_VISUAL_QUERIES must be a comma list of query positions (got %r)' % spec)
         wanted = [q for q in asked if 0 <= q < nq]
         ids = (q_pids, g_pids, q_camids, g_camids)
-        if diffusion is not None:
+        if setdist is not None:
+            dist, idx = engine.set_search(setdist[0], setdist[1], topk, reduce=setdist[2], metric=setdist[3], exclude=ids)
+        elif diffusion is not None:
             graph, kq, alpha, n_iter = diffusion
             dist, idx = engine.diffusion_search(qf, gf, topk, graph=graph, kq=kq, alpha=alpha, n_iter=n_iter, exclude=ids)
         elif rerank:
@@ -689,9 +729,39 @@ class ATTEvaluator(object):
             raise ValueError('GRL_EVAL_DIFFUSION cannot be combined with GRL_EVAL_ROC: the pair-level figures are taken '
                              'from distance blocks, and the diffusion scores exist per block of queries only (unset one '
                              'of them)')
-        qf, q_pids, q_camids = self.extract_feature(query_loader)
+        # tracklet set distances over the clips of dense mode, off by default (engine.set_metrics_streaming): the ranking,
+        # --visual and GRL_EVAL_ROC work on a set-to-set distance between the tracklets' clip sets instead of the
+        # distance of their mean rows; the clustering knobs keep running on the mean rows
+        set_knob = parse_set_knob('GRL_EVAL_SET', os.environ.get('GRL_EVAL_SET'))
+        if set_knob is not None:
+            why = None
+            if not self.only_eval:
+                why = 'needs the dense mode (only_eval=True): rrs mode extracts one clip per tracklet, and a set of one ' \
+                      'clip has nothing to choose from'
+            elif rerank:
+                why = 'cannot re-rank: k-reciprocal re-ranking needs set distances of the gallery against itself, which ' \
+                      'this route does not compute (evaluate with rerank=0)'
+            elif knob is not None:
+                why = 'cannot be combined with GRL_EVAL_METRIC=%s: the verification head scores one row per tracklet, ' \
+                      'not a clip pair (unset one of them)' % os.environ['GRL_EVAL_METRIC'].strip()
+            elif qe is not None or dba is not None or pca_knob is not None:
+                why = 'cannot be combined with GRL_EVAL_QE, GRL_EVAL_DBA or GRL_EVAL_PCA: they rewrite one row per ' \
+                      'tracklet, and the set distances are taken between the clip rows (unset one of them)'
+            elif diffusion_knob is not None:
+                why = 'cannot be combined with GRL_EVAL_DIFFUSION: the graph is built on one row per tracklet and its ' \
+                      'scores replace the ranking the set distances would give (unset one of them)'
+            if why is not None:
+                raise ValueError('GRL_EVAL_SET=%s %s' % (os.environ['GRL_EVAL_SET'].strip(), why))
+            qf, q_pids, q_camids, qset = self._extract(query_loader, True)
+        else:
+            qf, q_pids, q_camids = self.extract_feature(query_loader)
         print('Done, obtained {}-by-{} matrix'.format(qf.size(0), qf.size(1)))
-        gf, g_pids, g_camids = self.extract_feature(gallery_loader)
+        if set_knob is not None:
+            gf, g_pids, g_camids, gset = self._extract(gallery_loader, True)
+            # the query clips are prepended to the gallery clips, as the query rows are below
+            gset = engine.TrackletSet(torch.cat((qset.clips, gset.clips), 0), np.append(qset.counts, gset.counts))
+        else:
+            gf, g_pids, g_camids = self.extract_feature(gallery_loader)
         gf = torch.cat((qf, gf), 0)               # query is prepended (attevaluator.py:143-145)
         g_pids = np.append(q_pids, g_pids)
         g_camids = np.append(q_camids, g_camids)
@@ -732,6 +802,18 @@ class ATTEvaluator(object):
             if tsne_knob is not None:
                 lines = tuple(lines) + tuple(_tsne_report(tsne_knob, gf, ids, path))
             return lines
+        if set_knob is not None:
+            reduce, metric = set_knob
+            print('Tracklet set distance: {} ({}), {} clips in {} tracklets'.format(
+                reduce, metric, int(gset.clips.size(0)), gset.n))
+            if visual:
+                self._visualize(query, gallery, qf, gf, q_pids, q_camids, g_pids, g_camids, path, 0,
+                                setdist=(qset, gset, reduce, metric))
+            if roc_bits:
+                roc_lines = _roc_report(engine.set_pair_roc(qset, gset, *ids, reduce=reduce, metric=metric, bits=roc_bits),
+                                        'set({},{})'.format(reduce, metric), path)
+            return _report(*engine.set_metrics_streaming(qset, gset, q_pids, g_pids, q_camids, g_camids, reduce=reduce,
+                                                         metric=metric), roc_lines=extra(roc_lines))
         if diffusion_knob is not None:
             graph = _diffusion_report(diffusion_knob, gf, path)
             k, kq, alpha, n_iter = diffusion_knob

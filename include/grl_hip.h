@@ -43,8 +43,8 @@ const char* grl_last_error(void);
  * grl_rrs_place, grl_rrs_transpose) among them, grl_topk_block_filtered, grl_expand_rows, the grl_verify_* entry points,
  * grl_pair_hist_block, the clustering entry points grl_cluster_*, the k-means entry points grl_kmeans_* /
  * grl_segment_rowsum, grl_jaccard_edges, the silhouette entry points grl_silhouette_*, the HDBSCAN entry points
- * grl_hdbscan_*, the t-SNE entry points grl_tsne_*, the PCA entry points grl_pca_* and the diffusion entry points
- * grl_diffusion_*. */
+ * grl_hdbscan_*, the t-SNE entry points grl_tsne_*, the PCA entry points grl_pca_*, the diffusion entry points
+ * grl_diffusion_* and grl_setdist_block. */
 #define GRL_ABI_VERSION 10
 int grl_abi_version(void);
 /* `waiter` (a hipStream_t) waits for everything enqueued on `signaler` so far: hipEventRecord + hipStreamWaitEvent on a
@@ -925,6 +925,42 @@ int grl_diffusion_solve(const int32_t* idx, const float* S, int64_t ldg, int n, 
                         int n_iter, float* x, float* ws, void* stream);
 /* out [B][ldo] (n used) = x [n][B] transposed, negated when negate != 0: the rows grl_topk_block / grl_row_argsort rank */
 int grl_diffusion_transpose(const float* x, int n, int B, int negate, float* out, int64_t ldo, void* stream);
+
+/* ---- tracklet set distances from a block of clip distances (setdist.hip, engine.set_dist / set_search /
+ * set_metrics_streaming / set_pair_roc) ----
+ * A tracklet set is its clips' rows and a ptr array, int64 [n + 1]: tracklet t owns the clips ptr[t] .. ptr[t + 1].
+ * ``e`` [rows][ld] is a block of the clip x clip distance matrix as the distance GEMM wrote it (GRL_EPI_NEGDOT or
+ * GRL_EPI_EUCLID): row r is query clip qptr[a0] + r, column c is gallery clip gptr[b0] + c, for the query tracklets
+ * a0 .. a0 + na (qptr[a0 + na] - qptr[a0] rows) and the gallery tracklets b0 .. b0 + nb.  out[a - a0][b - b0] (row
+ * stride ldo) is the set distance of the pair.  With e[i][j], i < m, j < p, the cell of a pair, rowmin[i] = min_j e[i][j]
+ * and colmin[j] = min_i e[i][j]:
+ *   GRL_SET_MIN        min_i rowmin[i]                                            (the closest clip pair)
+ *   GRL_SET_MEAN       sum_ij e[i][j] / float(m * p)
+ *   GRL_SET_CHAMFER    0.5f * (sum_i rowmin[i] / float(m) + sum_j colmin[j] / float(p))
+ *   GRL_SET_HAUSDORFF  max(max_i rowmin[i], max_j colmin[j])
+ * min and max are exact selections in the total order of the floats with -0 below +0 (grl_silhouette_block's bmin).  A
+ * NaN anywhere in the cell makes the cell the canonical NaN (0x7fc00000) under all four, and so does a sum that is NaN.
+ * The two sums of CHAMFER: sequential fp32 from +0.0f in ascending index, then the two divisions, one add, one multiply,
+ * each rounded (no fma).  The sum of MEAN: W = 64 for p > 32, else the smallest power of two >= p; R = 64 / W; 64
+ * partials, partial l = the sequential fp32 sum from +0.0f of the elements (i, j) with (i % R) * W + j % 64 == l, in
+ * ascending j / 64, then ascending i; then part[l] += part[l + s], l < s, for s = 32, 16, 8, 4, 2, 1
+ * (grl_silhouette_block's tree); one division.  Adds only, no atomics of any kind.  Every order depends on (m, p) alone --
+ * not on where the scratch was cut, on the launch or on the other tracklets of the block -- so a cell has the same bits
+ * on every run and for every blocking; tests/setdist_ref.py is this paragraph in numpy float32, bit for bit.
+ * The ptr arrays are passed twice: ``qptr_host`` / ``gptr_host`` are read by the argument checks, ``qptr`` / ``gptr`` are
+ * the same values on the device (the kernel's); only the entries a0 .. a0 + na and b0 .. b0 + nb are read.  One wave per
+ * cell; every element of e is read once, coalesced along the columns.
+ * GRL_EINVAL, before any launch: a null pointer, a negative size, a negative ptr, a tracklet without clips or a ptr
+ * that is not ascending, ld smaller than the block's clip columns gptr[b0 + nb] - gptr[b0], ldo < nb, an unknown reduce.
+ * GRL_EUNSUPPORTED, before any launch: a tracklet of more than GRL_SET_MAX_CLIPS clips. */
+#define GRL_SET_MIN        0
+#define GRL_SET_MEAN       1
+#define GRL_SET_CHAMFER    2
+#define GRL_SET_HAUSDORFF  3
+#define GRL_SET_MAX_CLIPS  1024
+int grl_setdist_block(const float* e, int64_t ld, const int64_t* qptr_host, const int64_t* qptr, int a0, int na,
+                      const int64_t* gptr_host, const int64_t* gptr, int b0, int nb, int reduce, float* out, int64_t ldo,
+                      void* stream);
 
 /* ---- ranking by the Siamese verification head (verify.hip, engine.verify_metric / verify_dist) ----
  * In eval mode classifierBN -> classifierlinear on (p - g)^2 is affine in (p - g)^2; the class-1 minus class-0 logit is
