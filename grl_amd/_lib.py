@@ -213,6 +213,11 @@ _SIGNATURES = {
     # tracklet set distances from a block of clip distances (setdist.hip)
     'grl_setdist_block': ([_fp, _i64, _fp, _fp, C.c_int, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _i64, _fp],
                           C.c_int),
+    # product-quantised gallery index: ADC scan, table fix-up, code packing, decode (pq.hip)
+    'grl_pq_scan': ([_fp, _fp, _fp, C.c_int, _i64, C.c_int, C.c_int, _i64, C.c_int, _fp, _fp], C.c_int),
+    'grl_pq_lut_finish': ([_fp, _fp, C.c_int, C.c_int, C.c_int, _fp], C.c_int),
+    'grl_pq_pack': ([_fp, _fp, _fp, _i64, C.c_int, C.c_int, _fp, _fp], C.c_int),
+    'grl_pq_decode': ([_fp, _fp, _fp, _i64, C.c_int, C.c_int, C.c_int, _i64, _fp], C.c_int),
     'grl_verify_fold': ([_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
     'grl_verify_rows': ([_fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, _fp],
                         C.c_int),

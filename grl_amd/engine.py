@@ -4385,3 +4385,303 @@ def set_pair_roc(qset, gset, q_pids, g_pids, q_camids, g_camids, reduce='chamfer
     lo, hi, sharded = _shard(gset.n)
     blocks = _SetBlocks(qset, gset, reduce, metric, block_cols, block_bytes, lo, hi)
     return _roc_blocks(blocks, qset.n, gset.n, q_pids, g_pids, q_camids, g_camids, bits, sharded)
+
+
+# ----------------------------------------------------------------------------
+# product-quantised gallery index and ADC search (pq.hip)
+# ----------------------------------------------------------------------------
+PQ_METRICS = {'cosine': 0, 'euclidean': 1}                            # GRL_PQ_COSINE / GRL_PQ_EUCLIDEAN of include/grl_hip.h
+PQ_M_MAX = 4096                                                       # GRL_PQ_M_MAX
+PQ_LUT_BYTES = int(os.environ.get('GRL_PQ_LUT_BYTES', str(1 << 30)))  # resident query tables: nq * M * ksub * 4 bytes
+
+
+def _pq_int(v, lo, hi, what, name):
+    import numbers
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= hi:
+        raise ValueError('%s: %s must be an integer in %d..%d (got %r)' % (what, name, lo, hi, v))
+    return int(v)
+
+
+def _pq_split(d, M, what):
+    """dsub = d / M, or ValueError naming M (d % M) or dsub (the sub-products go through the fp32 GEMM: K % 32 == 0)."""
+    M = _pq_int(M, 1, PQ_M_MAX, what, 'M')
+    if d % M:
+        raise ValueError('%s: M must divide the feature size (d = %d, got M = %d)' % (what, d, M))
+    if (d // M) % 32:
+        raise ValueError('%s: dsub = d / M must be a multiple of 32 (d = %d, M = %d give dsub = %d)' % (what, d, M, d // M))
+    return M, d // M
+
+
+def _pq_rows(xf, d, what, name):
+    require_device(xf, name)
+    if xf.dim() != 2 or xf.shape[1] != d:
+        raise ValueError('%s: %s must be [rows, d] = [rows, %d] (got %s)' % (what, name, d, tuple(xf.shape)))
+    return xf.contiguous()
+
+
+def _pq_codes(codes, M, what):
+    if not (torch.is_tensor(codes) and codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2
+            and codes.shape[1] == M):
+        raise ValueError('%s: codes must be a uint8 device tensor [n, M] = [n, %d] (got %s)'
+                         % (what, M, (tuple(codes.shape), codes.dtype) if torch.is_tensor(codes) else type(codes).__name__))
+    return codes.contiguous()
+
+
+def _pq_pack(labels, codes, n, M, ksub, what):
+    """grl_pq_pack: the scan layout (uint32 [ceil(M / 4), n]) of int32 labels [M, n] (``codes`` is then written) or of
+    ``codes`` (labels None), and the one-word range check: ValueError for a code outside 0..ksub-1."""
+    scan = torch.empty(((M + 3) // 4, n), dtype=torch.int32, device=codes.device)
+    if n:
+        flag = torch.zeros(1, dtype=torch.int32, device=codes.device)
+        _call('grl_pq_pack', ptr(labels), ptr(codes), ptr(scan), n, M, ksub, ptr(flag))
+        if int(flag):
+            raise ValueError('%s: codes must be in 0..ksub-1 = 0..%d' % (what, ksub - 1))
+    return scan
+
+
+class PqCodebook(object):
+    """The codebooks of a product quantiser: ``codebooks`` [M, ksub, dsub] float32 on the device, subspace
+    m = the feature columns [m * dsub, (m + 1) * dsub), ksub = 2**nbits centroids each (16, 32, 64, 128 or 256), dsub a
+    multiple of 32; ``d`` = M * dsub.  ``metric`` ('cosine' = cosin_dist, 'euclidean' = pairwise_distance_tensor) is the
+    distance the tables approximate; the codes are Euclidean-nearest centroids under both.  A caller may wrap codebooks of
+    its own; ``pq_train`` fills them by k-means and then sets ``n_iter`` / ``converged`` / ``inertia`` (one entry per
+    subspace; None otherwise).  ValueError names the argument that is wrong."""
+
+    def __init__(self, codebooks, metric='cosine'):
+        _cluster_metric(metric, 'PqCodebook')
+        require_device(codebooks, 'codebooks')
+        if codebooks.dim() != 3:
+            raise ValueError('PqCodebook: codebooks must be [M, ksub, dsub] (got %s)' % (tuple(codebooks.shape),))
+        M, ksub, dsub = (int(v) for v in codebooks.shape)
+        if ksub not in (16, 32, 64, 128, 256):
+            raise ValueError('PqCodebook: ksub must be 2**nbits with nbits in 4..8 (got ksub = %d)' % ksub)
+        _pq_split(M * dsub, M, 'PqCodebook')
+        self.M, self.ksub, self.dsub, self.d, self.metric = M, ksub, dsub, M * dsub, metric
+        self.codebooks = codebooks.contiguous()
+        self.n_iter = self.converged = self.inertia = None
+        self._cn = None
+
+    def _labels(self, xf):
+        """int32 [M, n]: row m = the labels of kmeans_assign(xf[:, sub(m)].contiguous(), codebooks[m], 'euclidean')."""
+        n = xf.shape[0]
+        lab = torch.empty((self.M, n), dtype=torch.int32, device=xf.device)
+        for m in range(self.M):
+            sub = xf[:, m * self.dsub:(m + 1) * self.dsub].contiguous()
+            run_key, run_val = _kmeans_top1(sub, self.codebooks[m], 'euclidean', None, None)
+            lab[m] = _kmeans_relabel(run_key, run_val, self.ksub)[0]
+        return lab
+
+    def _encode(self, xf):
+        xf = _pq_rows(xf, self.d, 'PqCodebook.encode', 'xf')
+        n = xf.shape[0]
+        codes = torch.empty((n, self.M), dtype=torch.uint8, device=xf.device)
+        if n == 0:
+            return codes, torch.empty(((self.M + 3) // 4, 0), dtype=torch.int32, device=xf.device)
+        return codes, _pq_pack(self._labels(xf), codes, n, self.M, self.ksub, 'PqCodebook.encode')
+
+    def encode(self, xf):
+        """uint8 [n, M]: codes[i, m] = kmeans_assign(xf[:, sub(m)].contiguous(), codebooks[m], 'euclidean')[0][i], bit
+        for bit -- the Euclidean-nearest centroid of the sub-row, ties to the smaller centroid index -- one byte per code
+        whatever nbits is.  The clamp of pairwise_distance_tensor turns a NaN distance into 1e-12, so a NaN row ties at
+        every centroid and encodes to code 0 everywhere: a consequence of that clamp, not a special case."""
+        return self._encode(xf)[0]
+
+    def decode(self, codes):
+        """float32 [n, d]: decode(codes)[i, sub(m)] = codebooks[m, codes[i, m]], exact copies.  ValueError for a code
+        >= ksub (one device-side check, skipped where ksub = 256 cannot be exceeded)."""
+        codes = _pq_codes(codes, self.M, 'PqCodebook.decode')
+        n = codes.shape[0]
+        if self.ksub < 256:
+            _pq_pack(None, codes, n, self.M, self.ksub, 'PqCodebook.decode')
+        out = _new((n, self.d), self.codebooks)
+        if n:
+            _call('grl_pq_decode', ptr(self.codebooks), ptr(codes), ptr(out), n, self.M, self.ksub, self.dsub, self.d)
+        return out
+
+    def lut(self, qf):
+        """The query tables [nq, M, ksub] float32.  With g = cosin_dist(qf[:, sub(m)].contiguous(), codebooks[m]) (the
+        NEGDOT GEMM's bits; the GEMM reads the slice in place and writes into the table): 'cosine' lut[q, m] = g[q];
+        'euclidean' lut[q, m, c] = cn[m, c] + 2 * g[q, c], cn[m] = grl_row_sqnorm of codebooks[m] (one exact multiply,
+        one rounded add; the query's own norm is added by the scan)."""
+        qf = _pq_rows(qf, self.d, 'PqCodebook.lut', 'qf')
+        nq, M, ksub, dsub = qf.shape[0], self.M, self.ksub, self.dsub
+        lut = _new((nq, M, ksub), qf)
+        if nq == 0:
+            return lut
+        for m in range(M):
+            gemm(qf[:, m * dsub:], self.codebooks[m], lut[:, m], nq, ksub, dsub, lda=self.d, ldy=M * ksub,
+                 epilogue=EPI_NEGDOT, math=MATH_F32)
+        if self.metric == 'euclidean':
+            if self._cn is None:
+                self._cn = _new((M, ksub), qf)
+                _call('grl_row_sqnorm', ptr(self.codebooks), ptr(self._cn), M * ksub, dsub, dsub)
+            _call('grl_pq_lut_finish', ptr(lut), ptr(self._cn), nq, M, ksub)
+        return lut
+
+
+def pq_train(xf, M, nbits=8, metric='cosine', max_iter=25, seed=0):
+    """A ``PqCodebook`` trained on the rows of ``xf`` [n, d]: subspace m holds ``kmeans(xf[:, sub(m)].contiguous(),
+    2**nbits, 'euclidean', 'random', seed + m, max_iter).centroids``, bit for bit (Euclidean k-means under both metrics, as
+    is usual for product quantisation; ``metric`` only selects the tables' form).  ``n_iter``, ``converged`` and
+    ``inertia`` of the result list the M runs.  Not sharded: every rank trains the full, identical codebooks.
+    ValueError: a ``verify_metric``, M not dividing d, dsub = d / M not a multiple of 32, nbits outside 4..8,
+    n < 2**nbits (k-means' own rule), max_iter < 1, seed < 0."""
+    _cluster_metric(metric, 'pq_train')
+    xf = _kmeans_rows(xf, 'pq_train')
+    n, d = xf.shape
+    M, dsub = _pq_split(d, M, 'pq_train')
+    nbits = _pq_int(nbits, 4, 8, 'pq_train', 'nbits')
+    max_iter = _kmeans_int(max_iter, 1, 'pq_train', 'max_iter')
+    seed = _kmeans_int(seed, 0, 'pq_train', 'seed')
+    ksub = 1 << nbits
+    if n < ksub:
+        raise ValueError('pq_train: xf needs at least ksub = 2**nbits = %d rows (n = %d)' % (ksub, n))
+    runs = [kmeans(xf[:, m * dsub:(m + 1) * dsub].contiguous(), ksub, 'euclidean', 'random', seed + m, max_iter)
+            for m in range(M)]
+    book = PqCodebook(torch.stack([r.centroids for r in runs]), metric)
+    book.n_iter, book.converged, book.inertia = [r.n_iter for r in runs], [r.converged for r in runs], [r.inertia for r in runs]
+    return book
+
+
+class PqIndex(object):
+    """A gallery as product-quantiser codes: ``codebook``, ``codes`` (uint8 [n, M] on the device, the public layout),
+    ``n``, and ``nbytes`` = everything the index keeps on the device: the codes, their scan-layout copy (uint32
+    [ceil(M / 4), n], what grl_pq_scan reads coalesced) and the codebooks.  The constructor checks once that every code is
+    below ksub (ValueError), so the scan never has to."""
+
+    def __init__(self, codebook, codes, _scan=None):
+        if not isinstance(codebook, PqCodebook):
+            raise ValueError('PqIndex: codebook must be a PqCodebook (got %s)' % type(codebook).__name__)
+        self.codebook, self.codes = codebook, _pq_codes(codes, codebook.M, 'PqIndex')
+        self.n = int(self.codes.shape[0])
+        self._scan = _pq_pack(None, self.codes, self.n, codebook.M, codebook.ksub, 'PqIndex') if _scan is None else _scan
+        self.nbytes = self.codes.numel() + 4 * self._scan.numel() + 4 * codebook.codebooks.numel()
+
+
+def pq_index(xf, codebook):
+    """``PqIndex(codebook, codebook.encode(xf))`` with the scan layout written by the same launch as the codes."""
+    if not isinstance(codebook, PqCodebook):
+        raise ValueError('pq_index: codebook must be a PqCodebook (got %s)' % type(codebook).__name__)
+    codes, scan = codebook._encode(xf)
+    return PqIndex(codebook, codes, scan)
+
+
+def _pq_check(index, what):
+    if not isinstance(index, PqIndex):
+        raise ValueError('%s: index must be a PqIndex (got %s)' % (what, type(index).__name__))
+
+
+class _PqBlocks(object):
+    """Column blocks of the ADC distance matrix of ``qf`` against the code rows of ``index``: the block-source contract of
+    ``_ColumnBlocks`` (``spans``, ``block(c0, c1)``, ``qf``, ``nq``, ``ng``; widths chosen the same way; one reused
+    buffer).  The constructor makes the tables of all its queries (``codebook.lut``) and, for 'euclidean', their
+    grl_row_sqnorm; a block is one grl_pq_scan over the code rows [c0, c1).  An entry's bits depend on its codes and its
+    query's table alone (include/grl_hip.h), so a block holds the full matrix's bits whatever its width."""
+
+    def __init__(self, qf, index, block_cols=None, block_bytes=None):
+        _pq_check(index, '_PqBlocks')
+        book = index.codebook
+        self.qf = _pq_rows(qf, book.d, '_PqBlocks', 'qf')
+        self.index, self.nq, self.ng = index, self.qf.shape[0], index.n
+        nq, hi = self.nq, index.n
+        if block_cols is None:
+            budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
+            block_cols = max(256, budget // (4 * max(nq, 1)) // 256 * 256)
+        width = max(1, min(int(block_cols), hi))
+        self.width = width
+        self.spans = [(c, min(c + width, hi)) for c in range(0, hi, width)]
+        self.buf = _new((nq * width,), self.qf) if self.spans and nq else None
+        self.lut = self.rn = None
+        if self.spans and nq:
+            self.lut = book.lut(self.qf)
+            if book.metric == 'euclidean':
+                self.rn = _new((nq,), self.qf)
+                _call('grl_row_sqnorm', ptr(self.qf), ptr(self.rn), nq, book.d, book.d)
+
+    def block(self, c0, c1):
+        n, book = c1 - c0, self.index.codebook
+        out = self.buf[:self.nq * n].view(self.nq, n)
+        scan = self.index._scan
+        if n != self.ng:                                   # the kernel's row stride is its column count
+            scan = scan[:, c0:c1].contiguous()
+        _call('grl_pq_scan', ptr(self.lut), ptr(scan), ptr(out), self.nq, n, book.M, book.ksub, n,
+              PQ_METRICS[book.metric], ptr(self.rn))
+        return out
+
+
+def pq_dist(qf, index, block_cols=None, block_bytes=None):
+    """The materialised [nq, n] float32 ADC distances of ``qf`` against ``index``, for small cases and tests: per pair the
+    sum S of the M table entries its codes select, in the fixed fp32 order of include/grl_hip.h (four partials, adds only);
+    'cosine': S; 'euclidean': sqrt(max(|q|^2 + S, 1e-12)), a NaN argument giving 1e-12 as in pairwise_distance_tensor.
+    tests/pq_ref.py gives the same bits from the tables.  The same bits for every ``block_cols``."""
+    _pq_check(index, 'pq_dist')
+    blocks = _PqBlocks(qf, index, index.n if block_cols is None and block_bytes is None else block_cols, block_bytes)
+    out = _new((blocks.nq, index.n), blocks.qf)
+    if blocks.nq:
+        for c0, c1 in blocks.spans:
+            out[:, c0:c1] = blocks.block(c0, c1)
+    return out
+
+
+def pq_search(qf, index, k, exclude=None, block_cols=None, block_bytes=None):
+    """``search`` on the ADC distances D = pq_dist(qf, index): ``(dist [nq, k] float32, idx [nq, k] int64)``, bit for bit
+    ``rank_rows(D)[:, :k]`` and D at those indices, without D: blocks of code rows through grl_pq_scan, ranked by
+    search's running top-k.  Identical code rows give identical distances, so ties are the rule here: they go to the
+    smaller gallery index.  ``exclude`` is search's junk rule; padding is index -1, distance +inf; k <= 1024.  The tables
+    of the queries are resident (nq * M * ksub * 4 bytes); beyond GRL_PQ_LUT_BYTES (1 GiB) the queries are served in row
+    blocks, whose results are independent and concatenated.  Not sharded: every rank computes the full result."""
+    _pq_check(index, 'pq_search')
+    if not 1 <= int(k) <= SEARCH_K_MAX:
+        raise ValueError('pq_search: k must be in 1..%d (got %r)' % (SEARCH_K_MAX, k))
+    k, book = int(k), index.codebook
+    qf = _pq_rows(qf, book.d, 'pq_search', 'qf')
+    nq = qf.shape[0]
+    junk = _junk_ids(exclude, nq, index.n, qf.device)
+    rows = max(1, PQ_LUT_BYTES // (4 * book.M * book.ksub))          # queries whose tables fit (at least one)
+    dist, idx = [], []
+    for q0 in range(0, max(nq, 1), rows):
+        q1 = min(q0 + rows, nq)
+        blocks = _PqBlocks(qf[q0:q1], index, block_cols, block_bytes)
+        j = None if junk is None else (junk[0][q0:q1], junk[1][q0:q1], junk[2], junk[3])
+        dv, di = _search_blocks(blocks, q1 - q0, k, False, j)
+        dist.append(dv)
+        idx.append(di)
+    return (dist[0], idx[0]) if len(dist) == 1 else (torch.cat(dist), torch.cat(idx))
+
+
+def pq_metrics_streaming(qf, index, q_pids, g_pids, q_camids, g_camids, max_rank=100, block_cols=None, block_bytes=None):
+    """``rank_metrics(rank_rows(D), ...)`` for D = pq_dist(qf, index) without D: (cmc[max_rank] float32, mAP float) with
+    rank_metrics_streaming's contract.  The tables of ALL queries must fit GRL_PQ_LUT_BYTES: ValueError otherwise, naming
+    the bytes (the two passes walk every query's matches together).  Not sharded."""
+    _pq_check(index, 'pq_metrics_streaming')
+    book = index.codebook
+    qf = _pq_rows(qf, book.d, 'pq_metrics_streaming', 'qf')
+    need = 4 * qf.shape[0] * book.M * book.ksub
+    if need > PQ_LUT_BYTES:
+        raise ValueError('pq_metrics_streaming: the query tables take %d bytes (nq * M * ksub * 4 = %d * %d * %d * 4), above '
+                         'GRL_PQ_LUT_BYTES = %d' % (need, qf.shape[0], book.M, book.ksub, PQ_LUT_BYTES))
+    blocks = _PqBlocks(qf, index, block_cols, block_bytes)
+    first, nhit, ap = _rank_blocks(blocks, blocks.nq, index.n, q_pids, g_pids, q_camids, g_camids, False)
+    return _cmc_map(first, nhit, ap, index.n, max_rank)
+
+
+def topk_recall(approx_idx, exact_idx, ks):
+    """Host helper: for each k of ``ks``, the mean over the queries of |approx[:k] & exact[:k]| / (number of valid entries
+    of exact[:k]), as a list of floats.  The index lists are ``search``'s ([nq, L] tensors or arrays, -1 = padding, which
+    matches nothing); a query whose exact[:k] is all padding is left out of the mean (nan when none is left)."""
+    import numpy as np
+    a = np.asarray(approx_idx.cpu() if torch.is_tensor(approx_idx) else approx_idx).astype(np.int64)
+    e = np.asarray(exact_idx.cpu() if torch.is_tensor(exact_idx) else exact_idx).astype(np.int64)
+    if a.ndim != 2 or e.ndim != 2 or a.shape[0] != e.shape[0]:
+        raise ValueError('topk_recall: approx_idx and exact_idx must be [nq, L] lists of the same queries (got %s, %s)'
+                         % (a.shape, e.shape))
+    out = []
+    for k in ks:
+        k = _pq_int(k, 1, 2 ** 31 - 1, 'topk_recall', 'k')
+        part = []
+        for ra, re_ in zip(a[:, :k], e[:, :k]):
+            valid = re_[re_ >= 0]
+            if valid.size:
+                part.append(np.intersect1d(ra[ra >= 0], valid).size / float(valid.size))
+        out.append(float(np.mean(part)) if part else float('nan'))
+    return out

@@ -511,6 +511,68 @@ def parse_set_knob(name, value):
     return parts[0], parts[1] if len(parts) == 2 else 'cosine'
 
 
+def parse_pq_knob(name, value):
+    """``GRL_EVAL_PQ``: unset or empty -> None (off); "M", "M,nbits", "M,nbits,max_iter" or "M,nbits,max_iter,seed" -> (M,
+    nbits, max_iter, seed) with an integer M >= 1 (the subspaces; it must divide the feature size into parts of a multiple
+    of 32 columns, which engine.pq_train checks against the features), nbits in 4..8 (default 8), max_iter >= 1 (default
+    25) and seed >= 0 (default 0).  Anything else is a ValueError that names the variable."""
+    if value is None or not value.strip():
+        return None
+    parts = [p.strip() for p in value.split(',')]
+    try:
+        if len(parts) > 4:
+            raise ValueError
+        M = int(parts[0])
+        nbits = int(parts[1]) if len(parts) >= 2 else 8
+        max_iter = int(parts[2]) if len(parts) >= 3 else 25
+        seed = int(parts[3]) if len(parts) == 4 else 0
+    except ValueError:
+        raise ValueError('%s must be "M", "M,nbits", "M,nbits,max_iter" or "M,nbits,max_iter,seed" with integers (got %r)'
+                         % (name, value))
+    if not 1 <= M <= engine.PQ_M_MAX or not 4 <= nbits <= 8 or not 1 <= max_iter <= 2 ** 31 - 1 \
+            or not 0 <= seed <= 2 ** 31 - 1:
+        raise ValueError('%s: M must be in 1..%d, nbits in 4..8, max_iter >= 1 and seed >= 0 (got %r)'
+                         % (name, engine.PQ_M_MAX, value))
+    return M, nbits, max_iter, seed
+
+
+def _pq_report(knob, qf, gf, ids, path):
+    """GRL_EVAL_PQ: a product-quantised index of the query-prepended gallery ``gf`` (engine.pq_train + engine.pq_index, by
+    cosine) -- the lines ``_report`` prints last: CMC / mAP under ADC next to the exact ones, recall@1 / 10 / 100 of
+    engine.pq_search against engine.search under the same junk rule, the index bytes against the feature bytes -- and
+    ``path + 'pq.json'`` (rank 0 alone writes; strict JSON).  A report only: the route's ranking is not touched."""
+    import json
+    M, nbits, max_iter, seed = knob
+    q_pids, g_pids, q_camids, g_camids = ids
+    book = engine.pq_train(gf, M, nbits, 'cosine', max_iter, seed)
+    index = engine.pq_index(gf, book)
+    cmc, mAP = engine.pq_metrics_streaming(qf, index, q_pids, g_pids, q_camids, g_camids)
+    cmc_x, mAP_x = engine.rank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids)
+    k = min(100, engine.SEARCH_K_MAX, int(gf.size(0)))
+    approx = engine.pq_search(qf, index, k, exclude=ids)[1]
+    exact = engine.search(qf, gf, k, exclude=ids)[1]
+    ks = (1, 10, 100)
+    recall = engine.topk_recall(approx, exact, ks)
+    feature_bytes = 4 * int(gf.size(0)) * int(gf.size(1))
+    ranks = [r for r in (1, 5, 10, 20) if r <= len(cmc)]
+    lines = ['PQ: M = {}, nbits = {} ({} bytes per row of {}), {} rows'.format(M, nbits, M, 4 * int(gf.size(1)), index.n),
+             'ADC Mean AP: {:4.1%} (exact {:4.1%})'.format(mAP, mAP_x)]
+    lines += ['ADC Rank-{:<3}: {:.1%} (exact {:.1%})'.format(r, cmc[r - 1], cmc_x[r - 1]) for r in ranks]
+    lines += ['ADC recall@1: {:.2%}  @10: {:.2%}  @100: {:.2%}'.format(*recall),
+              'Index: {} bytes against {} bytes of features ({:.1f}x smaller)'.format(
+                  index.nbytes, feature_bytes, feature_bytes / float(index.nbytes))]
+    if grl_dist._rank_world(None, None)[0] == 0:
+        js = {'M': M, 'nbits': nbits, 'ksub': book.ksub, 'dsub': book.dsub, 'max_iter': max_iter, 'seed': seed,
+              'metric': 'cosine', 'n': index.n, 'n_queries': int(qf.size(0)), 'n_iter': book.n_iter,
+              'converged': book.converged, 'adc': {'mAP': float(mAP), 'cmc': [float(v) for v in cmc]},
+              'exact': {'mAP': float(mAP_x), 'cmc': [float(v) for v in cmc_x]},
+              'recall': {str(kk): (r if math.isfinite(r) else None) for kk, r in zip(ks, recall)},
+              'index_bytes': int(index.nbytes), 'code_bytes': int(index.codes.numel()), 'feature_bytes': feature_bytes}
+        with open((path or '') + 'pq.json', 'w') as fh:
+            json.dump(js, fh, allow_nan=False)
+    return lines
+
+
 class ATTEvaluator(object):
     def __init__(self, cnn_model, Siamese_model, only_eval):
         self.cnn_model = cnn_model
@@ -733,6 +795,25 @@ class ATTEvaluator(object):
         # --visual and GRL_EVAL_ROC work on a set-to-set distance between the tracklets' clip sets instead of the
         # distance of their mean rows; the clustering knobs keep running on the mean rows
         set_knob = parse_set_knob('GRL_EVAL_SET', os.environ.get('GRL_EVAL_SET'))
+        # a product-quantised index of the gallery, off by default (engine.pq_train / pq_search): a report next to the
+        # exact figures of the routes that rank by cosine, after PCA / DBA / QE; the route's ranking is not replaced
+        pq_knob = parse_pq_knob('GRL_EVAL_PQ', os.environ.get('GRL_EVAL_PQ'))
+        if pq_knob is not None:
+            why = None
+            if rerank:
+                why = 'cannot re-rank: the tables approximate the cosine distance of a query to a gallery row, and ' \
+                      'k-reciprocal re-ranking ranks by a Jaccard blend of whole neighbourhoods (evaluate with rerank=0)'
+            elif knob is not None:
+                why = 'cannot be combined with GRL_EVAL_METRIC=%s: the verification head\'s distance is not a sum over ' \
+                      'column groups of the rows (unset one of them)' % os.environ['GRL_EVAL_METRIC'].strip()
+            elif set_knob is not None:
+                why = 'cannot be combined with GRL_EVAL_SET: the set distances are taken between clip rows, and the ' \
+                      'index holds one code row per tracklet (unset one of them)'
+            elif diffusion_knob is not None:
+                why = 'cannot be combined with GRL_EVAL_DIFFUSION: the diffusion scores replace the cosine ranking the ' \
+                      'index approximates (unset one of them)'
+            if why is not None:
+                raise ValueError('GRL_EVAL_PQ=%s %s' % (os.environ['GRL_EVAL_PQ'].strip(), why))
         if set_knob is not None:
             why = None
             if not self.only_eval:
@@ -801,6 +882,8 @@ class ATTEvaluator(object):
                 lines = tuple(lines) + tuple(_hdbscan_report(hdbscan_knob, gf, ids, path, sil_knob))
             if tsne_knob is not None:
                 lines = tuple(lines) + tuple(_tsne_report(tsne_knob, gf, ids, path))
+            if pq_knob is not None:
+                lines = tuple(lines) + tuple(_pq_report(pq_knob, qf, gf, ids, path))
             return lines
         if set_knob is not None:
             reduce, metric = set_knob

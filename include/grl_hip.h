@@ -44,7 +44,7 @@ const char* grl_last_error(void);
  * grl_pair_hist_block, the clustering entry points grl_cluster_*, the k-means entry points grl_kmeans_* /
  * grl_segment_rowsum, grl_jaccard_edges, the silhouette entry points grl_silhouette_*, the HDBSCAN entry points
  * grl_hdbscan_*, the t-SNE entry points grl_tsne_*, the PCA entry points grl_pca_*, the diffusion entry points
- * grl_diffusion_* and grl_setdist_block. */
+ * grl_diffusion_*, grl_setdist_block and the product-quantisation entry points grl_pq_*. */
 #define GRL_ABI_VERSION 10
 int grl_abi_version(void);
 /* `waiter` (a hipStream_t) waits for everything enqueued on `signaler` so far: hipEventRecord + hipStreamWaitEvent on a
@@ -961,6 +961,41 @@ int grl_diffusion_transpose(const float* x, int n, int B, int negate, float* out
 int grl_setdist_block(const float* e, int64_t ld, const int64_t* qptr_host, const int64_t* qptr, int a0, int na,
                       const int64_t* gptr_host, const int64_t* gptr, int b0, int nb, int reduce, float* out, int64_t ldo,
                       void* stream);
+
+/* ---- product-quantised gallery index: ADC scan, table fix-up, code packing, decode (pq.hip, engine.pq_* / PqCodebook /
+ * PqIndex) ----
+ * d feature columns in M subspaces of dsub = d / M columns, ksub = 2^nbits centroids per subspace (nbits 4..8: ksub 16,
+ * 32, 64, 128 or 256); a gallery row is M codes, one byte each whatever nbits is.  A query's table lut [M][ksub] holds its
+ * distance term to every centroid (GRL_PQ_COSINE: the NEGDOT GEMM's -q_m . C[m][c]; GRL_PQ_EUCLIDEAN: cn[m][c] + 2 * that,
+ * cn = grl_row_sqnorm of the centroids).  The ADC sum of a pair with codes c_m, normative: four partials p_0 .. p_3, p_w
+ * the sequential fp32 sum from +0.0f of lut[m][c_m] over m = w, w + 4, w + 8, .. ascending (+0.0f when M <= w), and
+ * S = (p_0 + p_1) + (p_2 + p_3).  Adds only (no fma, no atomics); NaN and infinities follow IEEE through the adds.
+ * GRL_PQ_COSINE: dist = S.  GRL_PQ_EUCLIDEAN: t = rn[q] + S, dist = sqrtf(t > 1e-12f ? t : 1e-12f) (a NaN t gives
+ * 1e-12f, as GRL_EPI_EUCLID does).  The order depends on M alone: the same bits on every run, for every n, nq, ldo and
+ * launch; tests/pq_ref.py is this paragraph in numpy float32.
+ * grl_pq_scan: out[q][g] (row stride ldo >= n; only the first n columns of a row are written), q < nq, g < n, from the
+ * tables lut [nq][M][ksub] and the SCAN LAYOUT of the codes: uint32 [ceil(M / 4)][n], byte b (bits 8b .. 8b + 7) of word
+ * [w][g] = the code of subspace 4w + b of gallery row g, bytes of subspaces >= M zero (grl_pq_pack writes it).  rn [nq]
+ * is read by GRL_PQ_EUCLIDEAN only.  The codes must be < ksub (grl_pq_pack's flag); a larger byte reads some other entry
+ * of the staged tables, never outside them.  64 KiB of LDS per workgroup.
+ * grl_pq_lut_finish: lut[q][m][c] = cn[m][c] + 2.0f * lut[q][m][c] in place (the multiply is exact, one rounded add).
+ * grl_pq_pack: labels int32 [M][n] (the top-1 centroid of every row per subspace) -> codes uint8 [n][M] and the scan
+ * layout codes4; with labels == NULL, codes is the INPUT and only codes4 is written.  *flag (int32, zeroed by the
+ * caller) is set to 1 when a label or code is outside 0..ksub-1 (stored as 0).
+ * grl_pq_decode: out[i][m * dsub + j] = codebooks[m][codes[i][m]][j] (codebooks [M][ksub][dsub]), 16-byte copies.
+ * GRL_EINVAL, before any launch: a null pointer, a negative size, M outside 1..GRL_PQ_M_MAX, ksub not one of the five,
+ * an unknown metric, GRL_PQ_EUCLIDEAN without rn, ldo too small, a pointer that is not aligned (4 bytes: lut, out,
+ * codes4; 16 bytes: codebooks and out of grl_pq_decode, whose dsub and ldo must be multiples of 4), nq > 262140. */
+#define GRL_PQ_COSINE     0
+#define GRL_PQ_EUCLIDEAN  1
+#define GRL_PQ_M_MAX      4096
+int grl_pq_scan(const float* lut, const uint32_t* codes4, float* out, int nq, int64_t n, int M, int ksub, int64_t ldo,
+                int metric, const float* rn, void* stream);
+int grl_pq_lut_finish(float* lut, const float* cn, int nq, int M, int ksub, void* stream);
+int grl_pq_pack(const int32_t* labels, uint8_t* codes, uint32_t* codes4, int64_t n, int M, int ksub, int32_t* flag,
+                void* stream);
+int grl_pq_decode(const float* codebooks, const uint8_t* codes, float* out, int64_t n, int M, int ksub, int dsub,
+                  int64_t ldo, void* stream);
 
 /* ---- ranking by the Siamese verification head (verify.hip, engine.verify_metric / verify_dist) ----
  * In eval mode classifierBN -> classifierlinear on (p - g)^2 is affine in (p - g)^2; the class-1 minus class-0 logit is
