@@ -218,6 +218,11 @@ _SIGNATURES = {
     'grl_pq_lut_finish': ([_fp, _fp, C.c_int, C.c_int, C.c_int, _fp], C.c_int),
     'grl_pq_pack': ([_fp, _fp, _fp, _i64, C.c_int, C.c_int, _fp, _fp], C.c_int),
     'grl_pq_decode': ([_fp, _fp, _fp, _i64, C.c_int, C.c_int, C.c_int, _i64, _fp], C.c_int),
+    'grl_ivf_scan': ([_fp, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, C.c_int, _i64,
+                      C.c_int, C.c_int, C.c_int, C.c_int, _fp], C.c_int),
+    'grl_ivf_residual': ([_fp, _i64, _fp, _fp, C.c_int, _fp, _i64, _i64, C.c_int, _fp], C.c_int),
+    'grl_ivf_reconstruct': ([_fp, _fp, _fp, _fp, _fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _i64, _fp], C.c_int),
+    'grl_ivf_check_labels': ([_fp, _i64, C.c_int, _fp, _fp], C.c_int),
     'grl_verify_fold': ([_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
     'grl_verify_rows': ([_fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, _fp],
                         C.c_int),

@@ -4685,3 +4685,342 @@ def topk_recall(approx_idx, exact_idx, ks):
                 part.append(np.intersect1d(ra[ra >= 0], valid).size / float(valid.size))
         out.append(float(np.mean(part)) if part else float('nan'))
     return out
+
+
+# ----------------------------------------------------------------------------
+# IVF-PQ index: inverted lists over residual product-quantiser codes (ivf.hip)
+# ----------------------------------------------------------------------------
+IVF_NLIST_MAX, IVF_NPROBE_MAX = 65536, 1024                           # GRL_IVF_NLIST_MAX / GRL_IVF_NPROBE_MAX
+
+
+class IvfPqCodebook(object):
+    """The quantisers of an IVFADC index: ``coarse`` [nlist, d] float32 on the device, the centroids of the
+    inverted lists (1 <= nlist <= 65536), and ``pq``, a ``PqCodebook`` over the RESIDUALS row - coarse[list] whose own
+    metric is 'cosine', so that its tables are the plain NEGDOT tables lut[q, m, c] = -q_m . R[m][c] under both index
+    metrics.  ``metric`` ('cosine' = cosin_dist, 'euclidean' = pairwise_distance_tensor) is the distance the index
+    approximates.  A caller may wrap tensors of its own; ``ivf_train`` fills them by k-means and then sets
+    ``coarse_n_iter`` / ``coarse_converged`` / ``coarse_inertia`` (None otherwise; the product quantiser's are on ``pq``).
+    ValueError names the argument that is wrong."""
+
+    def __init__(self, coarse, pq, metric='cosine'):
+        _cluster_metric(metric, 'IvfPqCodebook')
+        require_device(coarse, 'coarse')
+        if coarse.dim() != 2:
+            raise ValueError('IvfPqCodebook: coarse must be [nlist, d] (got %s)' % (tuple(coarse.shape),))
+        nlist, d = (int(v) for v in coarse.shape)
+        if not 1 <= nlist <= IVF_NLIST_MAX:
+            raise ValueError('IvfPqCodebook: coarse must hold nlist in 1..%d centroids (got nlist = %d)' % (IVF_NLIST_MAX, nlist))
+        if not isinstance(pq, PqCodebook):
+            raise ValueError('IvfPqCodebook: pq must be a PqCodebook (got %s)' % type(pq).__name__)
+        if pq.metric != 'cosine':
+            raise ValueError("IvfPqCodebook: pq must be a PqCodebook whose metric is 'cosine' (the residual tables are the "
+                             'NEGDOT tables under both index metrics; got %r)' % (pq.metric,))
+        if pq.d != d:
+            raise ValueError('IvfPqCodebook: pq.d must equal the feature size of coarse (pq.d = %d, d = %d)' % (pq.d, d))
+        self.coarse, self.pq, self.metric, self.nlist, self.d = coarse.contiguous(), pq, metric, nlist, d
+        self.coarse_n_iter = self.coarse_converged = self.coarse_inertia = None
+
+
+def _ivf_book(book, what):
+    if not isinstance(book, IvfPqCodebook):
+        raise ValueError('%s: book must be an IvfPqCodebook (got %s)' % (what, type(book).__name__))
+
+
+def _ivf_residual(xf, labels32, coarse, out):
+    rows, d = xf.shape
+    if rows:
+        _call('grl_ivf_residual', ptr(xf), xf.stride(0), ptr(labels32), ptr(coarse), coarse.shape[0], ptr(out), d, rows, d)
+    return out
+
+
+def ivf_train(xf, nlist, M, nbits=8, metric='cosine', max_iter=25, seed=0):
+    """An ``IvfPqCodebook`` trained on the rows of ``xf`` [n, d], in three steps, bit for bit:
+      coarse = kmeans(xf, nlist, 'euclidean', 'random', seed, max_iter).centroids
+      lab    = kmeans_assign(xf, coarse, 'euclidean')[0]
+      pq     = pq_train(r, M, nbits, 'cosine', max_iter, seed + 1),  r[i][c] = xf[i][c] - coarse[lab_i][c] (one rounded
+               subtraction, grl_ivf_residual)
+    Both quantisers are Euclidean under both metrics; ``metric`` only selects the distance the index
+    approximates.  The residual copy r (n * d * 4 bytes) lives for the call: train on a subsample.  Not sharded.
+    ValueError: a ``verify_metric``, pq_train's rules on M, dsub and nbits, nlist outside 1..65536, max_iter < 1,
+    seed < 0, n < max(nlist, 2**nbits)."""
+    _cluster_metric(metric, 'ivf_train')
+    xf = _kmeans_rows(xf, 'ivf_train')
+    n, d = xf.shape
+    M, dsub = _pq_split(d, M, 'ivf_train')
+    nbits = _pq_int(nbits, 4, 8, 'ivf_train', 'nbits')
+    nlist = _pq_int(nlist, 1, IVF_NLIST_MAX, 'ivf_train', 'nlist')
+    max_iter = _kmeans_int(max_iter, 1, 'ivf_train', 'max_iter')
+    seed = _kmeans_int(seed, 0, 'ivf_train', 'seed')
+    if n < max(nlist, 1 << nbits):
+        raise ValueError('ivf_train: xf needs at least max(nlist, 2**nbits) = %d rows (n = %d)' % (max(nlist, 1 << nbits), n))
+    run = kmeans(xf, nlist, 'euclidean', 'random', seed, max_iter)
+    lab = kmeans_assign(xf, run.centroids, 'euclidean')[0]
+    res = _ivf_residual(xf, lab.to(torch.int32), run.centroids, _new((n, d), xf))
+    pq = pq_train(res, M, nbits, 'cosine', max_iter, seed + 1)
+    del res
+    book = IvfPqCodebook(run.centroids, pq, metric)
+    book.coarse_n_iter, book.coarse_converged, book.coarse_inertia = run.n_iter, run.converged, run.inertia
+    return book
+
+
+class IvfPqIndex(object):
+    """A gallery as inverted lists of residual product-quantiser codes.  ``IvfPqIndex(book, labels,
+    codes)`` builds it from caller-supplied ``labels`` (an integer device tensor [n], the list of every gallery row) and
+    ``codes`` (uint8 device [n, M], the codes of the residuals, gallery order); one device-side range check each: labels
+    in 0..nlist-1, codes < ksub (ValueError).  Empty lists are legal; n < 2**31.  It keeps
+
+      list_ptr  int64 [nlist + 1]   list l = the list positions list_ptr[l] .. list_ptr[l + 1]
+      ids       int32 [n]           the gallery index at every list position, ASCENDING inside a list (grl_kmeans_members)
+      codes     uint8 [n, M]        the public layout, gallery order
+      xn        float32 [n]         'euclidean' only: grl_row_sqnorm of the reconstructed row, list order
+      n, nbytes                     nbytes counts everything resident: the above, the scan layout (uint32 [ceil(M / 4), n],
+                                    list order), the labels (int32 [n]), coarse and the codebooks
+
+    ``labels()`` returns the list of every gallery row (int64), ``reconstruct(rows)`` the approximation
+    x^[i][sub(m)] = coarse[lab_i][sub(m)] + R[m][code[i, m]] (one rounded add per element) of the given gallery indices."""
+
+    def __init__(self, book, labels, codes):
+        self._build(book, labels, codes, True)
+
+    @classmethod
+    def _from_assigned(cls, book, labels, codes):
+        """the index of labels that kmeans_assign made: they are inside 0..nlist-1 already, so the label check is skipped"""
+        index = cls.__new__(cls)
+        index._build(book, labels, codes, False)
+        return index
+
+    def _build(self, book, labels, codes, check_labels):
+        _ivf_book(book, 'IvfPqIndex')
+        pq = book.pq
+        codes = _pq_codes(codes, pq.M, 'IvfPqIndex')
+        n = int(codes.shape[0])
+        if not (torch.is_tensor(labels) and labels.is_cuda and labels.dim() == 1 and labels.numel() == n
+                and not labels.dtype.is_floating_point and not labels.dtype.is_complex and labels.dtype != torch.bool):
+            raise ValueError('IvfPqIndex: labels must be an integer device tensor with one entry per row of codes (%d)' % n)
+        if n >= 2 ** 31:
+            raise ValueError('IvfPqIndex: n must be below 2**31 (got %d)' % n)
+        dev, nlist = codes.device, book.nlist
+        lab32 = labels.to(torch.int64).clamp(min=-1, max=IVF_NLIST_MAX).to(torch.int32).contiguous()
+        if n and check_labels:
+            flag = torch.zeros(1, dtype=torch.int32, device=dev)
+            _call('grl_ivf_check_labels', ptr(lab32), n, nlist, ptr(flag))
+            if int(flag):
+                raise ValueError('IvfPqIndex: labels must be in 0..nlist-1 = 0..%d' % (nlist - 1))
+        counts = torch.zeros(nlist, dtype=torch.int32, device=dev)
+        self.list_ptr = torch.zeros(nlist + 1, dtype=torch.int64, device=dev)
+        self.ids = torch.empty(n, dtype=torch.int32, device=dev)
+        if n:
+            _call('grl_kmeans_label_counts', ptr(lab32), n, nlist, ptr(counts))
+            _call('grl_rrs_scan', ptr(counts), nlist, ptr(self.list_ptr))
+            cursor = torch.zeros(nlist, dtype=torch.int32, device=dev)
+            tmp = torch.empty(n, dtype=torch.int32, device=dev)
+            _call('grl_kmeans_members', ptr(lab32), n, nlist, ptr(self.list_ptr), ptr(cursor), ptr(tmp), ptr(self.ids))
+        order = self.ids.to(torch.int64)
+        self._scan = _pq_pack(None, codes[order].contiguous(), n, pq.M, pq.ksub, 'IvfPqIndex')   # (the codes' range check)
+        self.book, self.codes, self.n, self._labels = book, codes, n, lab32
+        self._lens = counts.to(torch.int64)
+        lens = sorted((int(v) for v in counts.cpu().tolist()), reverse=True)     # the build's one read-back of the lengths
+        self.list_len_min, self.list_len_max = (lens[-1], lens[0])
+        self._longest = [0]                                # _longest[c] = the sum of the c longest lists: a chunk's width bound
+        for v in lens[:IVF_NPROBE_MAX]:
+            self._longest.append(self._longest[-1] + v)
+        self.xn = None
+        if book.metric == 'euclidean':
+            self.xn = _new((n,), book.coarse)
+            rows = max(1, SEARCH_BLOCK_BYTES // (4 * book.d))
+            for b0 in range(0, n, rows):
+                pos = order[b0:b0 + rows]
+                x = self._reconstruct(lab32[pos].contiguous(), codes[pos].contiguous())
+                _call('grl_row_sqnorm', ptr(x), ptr(self.xn[b0:]), x.shape[0], book.d, book.d)
+        self.nbytes = (8 * (nlist + 1) + 4 * n + codes.numel() + 4 * self._scan.numel() + 4 * n
+                       + (4 * n if self.xn is not None else 0) + 4 * book.coarse.numel() + 4 * pq.codebooks.numel())
+
+    def _reconstruct(self, lab32, codes):
+        book, pq = self.book, self.book.pq
+        rows = codes.shape[0]
+        out = _new((rows, book.d), book.coarse)
+        if rows:
+            _call('grl_ivf_reconstruct', ptr(book.coarse), ptr(pq.codebooks), ptr(lab32), ptr(codes), ptr(out), rows, book.nlist,
+                  pq.M, pq.ksub, pq.dsub, book.d)
+        return out
+
+    def labels(self):
+        return self._labels.to(torch.int64)
+
+    def reconstruct(self, rows):
+        if not (torch.is_tensor(rows) and rows.is_cuda and rows.dim() == 1 and not rows.dtype.is_floating_point
+                and not rows.dtype.is_complex and rows.dtype != torch.bool):
+            raise ValueError('IvfPqIndex.reconstruct: rows must be a 1-d integer device tensor of gallery indices')
+        rows = rows.to(torch.int64)
+        if rows.numel() and bool(((rows < 0) | (rows >= self.n)).any()):
+            raise ValueError('IvfPqIndex.reconstruct: rows must be in 0..n-1 = 0..%d' % (self.n - 1))
+        return self._reconstruct(self._labels[rows].contiguous(), self.codes[rows].contiguous())
+
+
+def ivf_index(xf, book):
+    """The ``IvfPqIndex`` of the rows of ``xf`` [n, d]: labels = kmeans_assign(xf, book.coarse, 'euclidean')[0] (a NaN row
+    lands in list 0 with code 0 everywhere: pairwise_distance_tensor's clamp, not a special case), the residuals encoded
+    by ``book.pq`` in row blocks whose residual buffer fits GRL_SEARCH_BLOCK_BYTES -- an n x d residual is never built."""
+    _ivf_book(book, 'ivf_index')
+    xf = _pq_rows(xf, book.d, 'ivf_index', 'xf')
+    n, d, pq = xf.shape[0], book.d, book.pq
+    if n >= 2 ** 31:
+        raise ValueError('ivf_index: n must be below 2**31 (got %d)' % n)
+    codes = torch.empty((n, pq.M), dtype=torch.uint8, device=xf.device)
+    if n == 0:
+        return IvfPqIndex._from_assigned(book, torch.empty(0, dtype=torch.int64, device=xf.device), codes)
+    lab = kmeans_assign(xf, book.coarse, 'euclidean')[0]
+    lab32 = lab.to(torch.int32)
+    rows = max(1, min(n, SEARCH_BLOCK_BYTES // (4 * d)))
+    res = _new((rows, d), xf)
+    for b0 in range(0, n, rows):
+        b1 = min(b0 + rows, n)
+        codes[b0:b1] = pq._encode(_ivf_residual(xf[b0:b1], lab32[b0:b1], book.coarse, res[:b1 - b0]))[0]
+    return IvfPqIndex._from_assigned(book, lab, codes)
+
+
+def _ivf_args(qf, index, nprobe, what):
+    if not isinstance(index, IvfPqIndex):
+        raise ValueError('%s: index must be an IvfPqIndex (got %s)' % (what, type(index).__name__))
+    hi = min(index.book.nlist, IVF_NPROBE_MAX)
+    nprobe = _pq_int(nprobe, 1, hi, what, 'nprobe')
+    return _pq_rows(qf, index.book.d, what, 'qf'), nprobe
+
+
+def _ivf_probe(qf, book, nprobe):
+    """(probe int64 [nq, nprobe], g0 float32 [nq, nprobe]): the index list of search(qf, coarse, nprobe, metric), unsharded
+    (every rank probes alike), and G0 = cosin_dist(qf, coarse) [nq, nlist] gathered there."""
+    probe = _ivf_probe_lists(qf, book, nprobe)
+    return probe, cosin_dist(qf, book.coarse).gather(1, probe).contiguous()
+
+
+def _ivf_probe_lists(qf, book, nprobe):
+    return _search_blocks(_ColumnBlocks(qf, book.coarse, book.metric), qf.shape[0], nprobe, False)[1]
+
+
+class _IvfQueries(object):
+    """What a block of query rows needs for its scans: the residual tables (``book.pq.lut``), the probes = the index
+    list of search(qf, coarse, nprobe, metric) (unsharded: every rank probes alike), G0 = cosin_dist(qf, coarse)
+    gathered at the probes, the probed lists' lengths and, for 'euclidean', grl_row_sqnorm of the queries.
+    ``chunk(j0, j1, width)`` is one grl_ivf_scan over the probe ranks [j0, j1): (dist [nq, width], cidx [nq, width])."""
+
+    def __init__(self, qf, index, nprobe):
+        book = index.book
+        self.index, self.qf, self.nq = index, qf, qf.shape[0]
+        nq = self.nq
+        self.lut = book.pq.lut(qf)
+        probe, self.g0 = _ivf_probe(qf, book, nprobe)
+        self.plen = index._lens[probe]
+        self.probe = probe.to(torch.int32).contiguous()
+        self.rn = None
+        if book.metric == 'euclidean':
+            self.rn = _new((nq,), qf)
+            _call('grl_row_sqnorm', ptr(qf), ptr(self.rn), nq, book.d, book.d)
+        self.buf = self.cbuf = None
+
+    def chunk(self, j0, j1, width):
+        index, nq, c = self.index, self.nq, j1 - j0
+        book, pq = index.book, index.book.pq
+        if self.buf is None or self.buf.numel() < nq * width:
+            self.buf = _new((nq * width,), self.qf)
+            self.cbuf = torch.empty(nq * width, dtype=torch.int32, device=self.qf.device)
+        out, cidx = self.buf[:nq * width].view(nq, width), self.cbuf[:nq * width].view(nq, width)
+        off = torch.zeros((nq, c + 1), dtype=torch.int32, device=self.qf.device)
+        off[:, 1:] = self.plen[:, j0:j1].cumsum(1)
+        probe, g0 = self.probe, self.g0
+        if c != probe.shape[1]:
+            probe, g0 = probe[:, j0:j1].contiguous(), g0[:, j0:j1].contiguous()
+        _call('grl_ivf_scan', ptr(self.lut), ptr(index._scan), ptr(index.ids), ptr(index.list_ptr), ptr(probe), ptr(g0), c, c,
+              ptr(off), ptr(index.xn), ptr(self.rn), ptr(out), ptr(cidx), width, width, nq, index.n, book.nlist, pq.M, pq.ksub,
+              PQ_METRICS[book.metric])
+        return out, cidx
+
+
+def _ivf_plan(index, nq, nprobe, block_bytes):
+    """(query rows per block, probes per chunk): a chunk row is at most the sum of the chunk's longest lists wide (known
+    from the build, no read-back), and the distance block plus the cidx block (8 bytes per entry) fit the budget; a chunk
+    holds at least one probe, and where one probe already exceeds the budget the queries go in row blocks.  The tables
+    obey GRL_PQ_LUT_BYTES and a launch serves at most 65535 queries."""
+    pq = index.book.pq
+    budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
+    rows = max(1, min(65535, PQ_LUT_BYTES // (4 * pq.M * pq.ksub), max(nq, 1)))
+    one = max(index._longest[1], 1)
+    if 8 * rows * one > budget:
+        rows = max(1, budget // (8 * one))
+    per = 1
+    while per < nprobe and 8 * rows * max(index._longest[per + 1], 1) <= budget:
+        per += 1
+    return rows, per
+
+
+def ivf_search(qf, index, k, nprobe, exclude=None, block_bytes=None):
+    """Each query's ``k`` nearest among the rows of the ``nprobe`` inverted lists nearest to it: ``(dist [nq, k] float32,
+    idx [nq, k] int64)``.  The probes are the index list of search(qf, coarse, nprobe, metric) (ties to the smaller list);
+    a candidate's distance is the normative one of include/grl_hip.h (g0 + the ADC sum over its residual codes; for
+    'euclidean' the reconstructed row's and the query's norms added and the clamped square root); the result is the
+    first k candidates in grl_row_argsort's order (canonical NaN, -0 == +0, ties to the smaller GALLERY index) with those
+    distances.  ``exclude`` is search's junk rule, applied through grl_topk_block_filtered and the scan's cidx: no mask is
+    built.  Fewer than k candidates leave padding: index -1, distance +inf.  k <= 1024; 1 <= nprobe <= min(nlist, 1024).
+    The candidates are served in chunks of probe ranks sized by ``block_bytes`` (default GRL_SEARCH_BLOCK_BYTES), the
+    queries in row blocks where one probe exceeds it or the tables exceed GRL_PQ_LUT_BYTES: the same bits for every
+    chunking.  Not sharded: every rank computes the full result."""
+    if not isinstance(index, IvfPqIndex):
+        raise ValueError('ivf_search: index must be an IvfPqIndex (got %s)' % type(index).__name__)
+    if not 1 <= int(k) <= SEARCH_K_MAX:
+        raise ValueError('ivf_search: k must be in 1..%d (got %r)' % (SEARCH_K_MAX, k))
+    qf, nprobe = _ivf_args(qf, index, nprobe, 'ivf_search')
+    k, nq, dev = int(k), qf.shape[0], qf.device
+    junk = _junk_ids(exclude, nq, index.n, dev)
+    run_key = torch.full((nq, k), -1, dtype=torch.int64, device=dev)          # all-ones composite = empty slot
+    run_val = torch.full((nq, k), float('inf'), dtype=torch.float32, device=dev)
+    if nq and index.n:
+        rows, per = _ivf_plan(index, nq, nprobe, block_bytes)
+        for q0 in range(0, nq, rows):
+            q1 = min(q0 + rows, nq)
+            qs = _IvfQueries(qf[q0:q1], index, nprobe)
+            for j0 in range(0, nprobe, per):
+                j1 = min(j0 + per, nprobe)
+                width = min(index._longest[j1 - j0], index.n)
+                if width == 0:
+                    continue
+                d, cidx = qs.chunk(j0, j1, width)
+                if junk is None:
+                    _call('grl_topk_block', ptr(d), width, ptr(cidx), width, q1 - q0, width, 0, k, ptr(run_key[q0:]),
+                          ptr(run_val[q0:]))
+                else:
+                    _call('grl_topk_block_filtered', ptr(d), width, ptr(cidx), width, q1 - q0, width, 0, k, ptr(run_key[q0:]),
+                          ptr(run_val[q0:]), ptr(junk[0][q0:]), ptr(junk[1][q0:]), ptr(junk[2]), ptr(junk[3]))
+    idx = run_key & 0xffffffff
+    idx[idx == 0xffffffff] = -1
+    return run_val, idx
+
+
+def ivf_dist(qf, index, nprobe):
+    """The materialised form of ``ivf_search``'s candidates, for small cases and tests: ``(D [nq, n] float32, cand [nq, n]
+    bool)`` in gallery order; cand[q, i] = row i is in one of q's probed lists, D[q, i] its normative distance (defined
+    where cand is set, 0 elsewhere)."""
+    qf, nprobe = _ivf_args(qf, index, nprobe, 'ivf_dist')
+    nq, n = qf.shape[0], index.n
+    D = torch.zeros((nq, n), dtype=torch.float32, device=qf.device)
+    cand = torch.zeros((nq, n), dtype=torch.bool, device=qf.device)
+    width = min(index._longest[nprobe], n)
+    if nq and width:
+        for q0 in range(0, nq, 65535):
+            qs = _IvfQueries(qf[q0:q0 + 65535], index, nprobe)
+            d, cidx = qs.chunk(0, nprobe, width)
+            live = cidx >= 0
+            row = (torch.arange(qs.nq, device=qf.device) + q0).view(-1, 1).expand_as(cidx)[live]
+            col = cidx[live].to(torch.int64)
+            D[row, col] = d[live]
+            cand[row, col] = True
+    return D, cand
+
+
+def ivf_probe_stats(qf, index, nprobe):
+    """int64 [nq] on the device: the number of candidates (the summed lengths of the probed lists) of every query; their
+    sum / (nq * n) is the scanned fraction."""
+    qf, nprobe = _ivf_args(qf, index, nprobe, 'ivf_probe_stats')
+    nq = qf.shape[0]
+    if nq == 0:
+        return torch.zeros(0, dtype=torch.int64, device=qf.device)
+    return index._lens[_ivf_probe_lists(qf, index.book, nprobe)].sum(1)

@@ -536,7 +536,7 @@ def parse_pq_knob(name, value):
     return M, nbits, max_iter, seed
 
 
-def _pq_report(knob, qf, gf, ids, path):
+def _pq_report(knob, qf, gf, ids, path, keep=None):
     """GRL_EVAL_PQ: a product-quantised index of the query-prepended gallery ``gf`` (engine.pq_train + engine.pq_index, by
     cosine) -- the lines ``_report`` prints last: CMC / mAP under ADC next to the exact ones, recall@1 / 10 / 100 of
     engine.pq_search against engine.search under the same junk rule, the index bytes against the feature bytes -- and
@@ -553,6 +553,8 @@ def _pq_report(knob, qf, gf, ids, path):
     exact = engine.search(qf, gf, k, exclude=ids)[1]
     ks = (1, 10, 100)
     recall = engine.topk_recall(approx, exact, ks)
+    if keep is not None:                                   # (GRL_EVAL_IVF reports next to these)
+        keep.update(k=k, exact=exact, recall=recall)
     feature_bytes = 4 * int(gf.size(0)) * int(gf.size(1))
     ranks = [r for r in (1, 5, 10, 20) if r <= len(cmc)]
     lines = ['PQ: M = {}, nbits = {} ({} bytes per row of {}), {} rows'.format(M, nbits, M, 4 * int(gf.size(1)), index.n),
@@ -569,6 +571,64 @@ def _pq_report(knob, qf, gf, ids, path):
               'recall': {str(kk): (r if math.isfinite(r) else None) for kk, r in zip(ks, recall)},
               'index_bytes': int(index.nbytes), 'code_bytes': int(index.codes.numel()), 'feature_bytes': feature_bytes}
         with open((path or '') + 'pq.json', 'w') as fh:
+            json.dump(js, fh, allow_nan=False)
+    return lines
+
+
+def parse_ivf_knob(name, value):
+    """``GRL_EVAL_IVF``: unset or empty -> None (off); "nlist" or "nlist,nprobe" -> (nlist, nprobe) with integers nlist in
+    1..65536 (the inverted lists; at most the gallery rows, which engine.ivf_train checks) and nprobe in 1..min(nlist, 1024)
+    (default max(1, nlist // 8), capped at 1024).  Anything else is a ValueError that names the variable."""
+    if value is None or not value.strip():
+        return None
+    parts = [p.strip() for p in value.split(',')]
+    try:
+        if len(parts) > 2:
+            raise ValueError
+        nlist = int(parts[0])
+        nprobe = int(parts[1]) if len(parts) == 2 else min(max(1, nlist // 8), engine.IVF_NPROBE_MAX)
+    except ValueError:
+        raise ValueError('%s must be "nlist" or "nlist,nprobe" with integers (got %r)' % (name, value))
+    if not 1 <= nlist <= engine.IVF_NLIST_MAX or not 1 <= nprobe <= min(nlist, engine.IVF_NPROBE_MAX):
+        raise ValueError('%s: nlist must be in 1..%d and nprobe in 1..min(nlist, %d) (got %r)'
+                         % (name, engine.IVF_NLIST_MAX, engine.IVF_NPROBE_MAX, value))
+    return nlist, nprobe
+
+
+def _ivf_report(knob, pq_knob, pq_kept, qf, gf, ids, path):
+    """GRL_EVAL_IVF: an IVF-PQ index of the query-prepended gallery ``gf`` (engine.ivf_train + engine.ivf_index, by cosine,
+    with GRL_EVAL_PQ's M, nbits, max_iter and seed) -- the lines printed after GRL_EVAL_PQ's: the lists, the mean scanned
+    fraction, recall@1 / 10 / 100 of engine.ivf_search against engine.search under the same junk rule next to
+    engine.pq_search's, the index bytes -- and ``path + 'ivf.json'`` (rank 0 alone writes; strict JSON).  A report only."""
+    import json
+    nlist, nprobe = knob
+    M, nbits, max_iter, seed = pq_knob
+    book = engine.ivf_train(gf, nlist, M, nbits, 'cosine', max_iter, seed)
+    index = engine.ivf_index(gf, book)
+    k, ks = pq_kept['k'], (1, 10, 100)
+    approx = engine.ivf_search(qf, index, k, nprobe, exclude=ids)[1]
+    recall = engine.topk_recall(approx, pq_kept['exact'], ks)
+    nq = int(qf.size(0))
+    scanned = float(engine.ivf_probe_stats(qf, index, nprobe).sum()) / max(nq * index.n, 1)
+    mean_len = index.n / float(nlist)
+    feature_bytes = 4 * int(gf.size(0)) * int(gf.size(1))
+    lines = ['IVF: nlist = {}, nprobe = {}, list length min / mean / max = {} / {:.1f} / {}'.format(
+                 nlist, nprobe, index.list_len_min, mean_len, index.list_len_max),
+             'IVF scanned fraction: {:.2%}'.format(scanned),
+             'IVF recall@1: {:.2%}  @10: {:.2%}  @100: {:.2%}  (PQ {:.2%}  {:.2%}  {:.2%})'.format(
+                 *(tuple(recall) + tuple(pq_kept['recall']))),
+             'IVF index: {} bytes against {} bytes of features ({:.1f}x smaller)'.format(
+                 index.nbytes, feature_bytes, feature_bytes / float(index.nbytes))]
+    if grl_dist._rank_world(None, None)[0] == 0:
+        def fin(v):
+            return v if math.isfinite(v) else None
+        js = {'nlist': nlist, 'nprobe': nprobe, 'M': M, 'nbits': nbits, 'max_iter': max_iter, 'seed': seed, 'metric': 'cosine',
+              'n': index.n, 'n_queries': nq, 'list_len': {'min': index.list_len_min, 'mean': mean_len, 'max': index.list_len_max},
+              'scanned_fraction': scanned, 'coarse_n_iter': book.coarse_n_iter, 'coarse_converged': book.coarse_converged,
+              'recall': {str(kk): fin(r) for kk, r in zip(ks, recall)},
+              'pq_recall': {str(kk): fin(r) for kk, r in zip(ks, pq_kept['recall'])},
+              'index_bytes': int(index.nbytes), 'feature_bytes': feature_bytes}
+        with open((path or '') + 'ivf.json', 'w') as fh:
             json.dump(js, fh, allow_nan=False)
     return lines
 
@@ -798,6 +858,11 @@ class ATTEvaluator(object):
         # a product-quantised index of the gallery, off by default (engine.pq_train / pq_search): a report next to the
         # exact figures of the routes that rank by cosine, after PCA / DBA / QE; the route's ranking is not replaced
         pq_knob = parse_pq_knob('GRL_EVAL_PQ', os.environ.get('GRL_EVAL_PQ'))
+        # inverted lists over residual codes on top of it, off by default (engine.ivf_train / ivf_search): one more report
+        ivf_knob = parse_ivf_knob('GRL_EVAL_IVF', os.environ.get('GRL_EVAL_IVF'))
+        if ivf_knob is not None and pq_knob is None:
+            raise ValueError('GRL_EVAL_IVF=%s needs GRL_EVAL_PQ: the index encodes its residuals with GRL_EVAL_PQ\'s M, nbits, '
+                             'max_iter and seed (set GRL_EVAL_PQ too)' % os.environ['GRL_EVAL_IVF'].strip())
         if pq_knob is not None:
             why = None
             if rerank:
@@ -883,7 +948,10 @@ class ATTEvaluator(object):
             if tsne_knob is not None:
                 lines = tuple(lines) + tuple(_tsne_report(tsne_knob, gf, ids, path))
             if pq_knob is not None:
-                lines = tuple(lines) + tuple(_pq_report(pq_knob, qf, gf, ids, path))
+                kept = {} if ivf_knob is not None else None
+                lines = tuple(lines) + tuple(_pq_report(pq_knob, qf, gf, ids, path, kept))
+                if ivf_knob is not None:
+                    lines = tuple(lines) + tuple(_ivf_report(ivf_knob, pq_knob, kept, qf, gf, ids, path))
             return lines
         if set_knob is not None:
             reduce, metric = set_knob

@@ -997,6 +997,42 @@ int grl_pq_pack(const int32_t* labels, uint8_t* codes, uint32_t* codes4, int64_t
 int grl_pq_decode(const float* codebooks, const uint8_t* codes, float* out, int64_t n, int M, int ksub, int dsub,
                   int64_t ldo, void* stream);
 
+/* ---- IVF-PQ gallery index: inverted lists over residual product-quantiser codes (ivf.hip, engine.ivf_* / IvfPqCodebook /
+ * IvfPqIndex).  Additive: GRL_ABI_VERSION stays 10. ----
+ * A coarse quantiser coarse [nlist][d] splits the gallery into nlist inverted lists; list l holds the rows at the LIST
+ * POSITIONS list_ptr[l] .. list_ptr[l + 1] (int64 [nlist + 1]) in ascending gallery index, ids [n] (int32) is the gallery
+ * index at every position, and the codes -- of the residual row - coarse[list], by a product quantiser as above -- sit in
+ * the scan layout uint32 [ceil(M / 4)][n] in list order.  The query tables lut [nq][M][ksub] are the GRL_PQ_COSINE ones
+ * (-q_m . R[m][c]) under both metrics.
+ * grl_ivf_scan serves the probe ranks of one chunk: probe [nq][ldp] (np used) are the probed lists of every query, g0
+ * [nq][ldp] the query's coarse term -q . coarse[list] of each, off [nq][np + 1] (int32) the prefix sums of the probed lists'
+ * lengths (off[q][0] = 0).  Query q's VIRTUAL ROW is its probed lists one after the other in probe-rank order; column col
+ * with off[q][j] <= col < off[q][j + 1] is list position p = list_ptr[probe[q][j]] + col - off[q][j].  Normative distance:
+ * S = the ADC sum above over the codes at p; t = g0[q][j] + S; GRL_PQ_COSINE: dist = t; GRL_PQ_EUCLIDEAN: u = xn[p] +
+ * 2.0f * t (the multiply is exact), w = rn[q] + u, dist = sqrtf(w > 1e-12f ? w : 1e-12f) (xn [n] = grl_row_sqnorm of the
+ * reconstructed rows in list order, rn [nq] that of the queries).  out[q][col] = dist and cidx[q][col] = ids[p] for col <
+ * off[q][np]; the columns from there to width get +inf and -1 (grl_topk_block skips them).  Rows of out and cidx have
+ * stride ldo >= width.  Adds only, no atomics: the same bits on every run and for every chunking of the probes.  20 KiB of
+ * LDS per workgroup.
+ * grl_ivf_residual: out[i][c] = x[i][c] - coarse[labels[i]][c] for a block of rows (one rounded subtraction).
+ * grl_ivf_reconstruct: out[i][m * dsub + j] = coarse[labels[i]][m * dsub + j] + codebooks[m][codes[i][m]][j] (one rounded
+ * add) for the given labels int32 [rows] and codes uint8 [rows][M].
+ * grl_ivf_check_labels: *flag (int32, zeroed by the caller) is set to 1 when a label is outside 0..nlist-1.
+ * GRL_EINVAL, before any launch: a null pointer, a negative size, n >= 2^31, nlist outside 1..GRL_IVF_NLIST_MAX, np outside
+ * 1..min(nlist, GRL_IVF_NPROBE_MAX), M, ksub or metric as grl_pq_scan refuses them, GRL_PQ_EUCLIDEAN without xn and rn, a
+ * stride that is too small, a pointer that is not aligned (8 bytes: list_ptr; 4 bytes: every other array), nq > 65535. */
+#define GRL_IVF_NLIST_MAX   65536
+#define GRL_IVF_NPROBE_MAX  1024
+int grl_ivf_scan(const float* lut, const uint32_t* codes4, const int32_t* ids, const int64_t* list_ptr, const int32_t* probe,
+                 const float* g0, int64_t ldp, int np, const int32_t* off, const float* xn, const float* rn, float* out,
+                 int32_t* cidx, int64_t ldo, int width, int nq, int64_t n, int nlist, int M, int ksub, int metric,
+                 void* stream);
+int grl_ivf_residual(const float* x, int64_t ldx, const int32_t* labels, const float* coarse, int nlist, float* out,
+                     int64_t ldo, int64_t rows, int d, void* stream);
+int grl_ivf_reconstruct(const float* coarse, const float* codebooks, const int32_t* labels, const uint8_t* codes, float* out,
+                        int64_t rows, int nlist, int M, int ksub, int dsub, int64_t ldo, void* stream);
+int grl_ivf_check_labels(const int32_t* labels, int64_t n, int nlist, int32_t* flag, void* stream);
+
 /* ---- ranking by the Siamese verification head (verify.hip, engine.verify_metric / verify_dist) ----
  * In eval mode classifierBN -> classifierlinear on (p - g)^2 is affine in (p - g)^2; the class-1 minus class-0 logit is
  * s(p, g) = sum_d w_d (p_d - g_d)^2 + c.  The ranking distance F = (1 - beta)(-q.g) + beta(-s), p / g = columns
