@@ -223,6 +223,10 @@ _SIGNATURES = {
     'grl_ivf_residual': ([_fp, _i64, _fp, _fp, C.c_int, _fp, _i64, _i64, C.c_int, _fp], C.c_int),
     'grl_ivf_reconstruct': ([_fp, _fp, _fp, _fp, _fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _i64, _fp], C.c_int),
     'grl_ivf_check_labels': ([_fp, _i64, C.c_int, _fp, _fp], C.c_int),
+    # exact refinement of a shortlist from a feature store (refine.hip)
+    'grl_refine_scan': ([_fp, _i64, _fp, _i64, C.c_int, _fp, _i64, _fp, _fp, _i64, C.c_int, C.c_int, _i64, C.c_int, C.c_int,
+                         _fp], C.c_int),
+    'grl_refine_pack_bf16': ([_fp, _fp, _i64, _fp], C.c_int),
     'grl_verify_fold': ([_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
     'grl_verify_rows': ([_fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, _fp],
                         C.c_int),

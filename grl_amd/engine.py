@@ -5024,3 +5024,154 @@ def ivf_probe_stats(qf, index, nprobe):
     if nq == 0:
         return torch.zeros(0, dtype=torch.int64, device=qf.device)
     return index._lens[_ivf_probe_lists(qf, index.book, nprobe)].sum(1)
+
+
+# ----------------------------------------------------------------------------
+# exact refinement of a shortlist from a feature store (refine.hip)
+# ----------------------------------------------------------------------------
+REFINE_D_MAX = 16384                                                  # GRL_REFINE_D_MAX
+REFINE_TYPES = {'f32': 0, 'bf16': 1}                                  # GRL_REFINE_F32 / GRL_REFINE_BF16 of include/grl_hip.h
+
+
+def _refine_d(d, what, name):
+    if d % 4 or not 1 <= d <= REFINE_D_MAX:
+        raise ValueError('%s: %s must have d columns with d a multiple of 4 in 1..%d (got d = %d)' % (what, name, REFINE_D_MAX, d))
+
+
+class RefineStore(object):
+    """The feature rows a shortlist is refined against: ``RefineStore(xf, dtype='f32' | 'bf16')`` of the
+    contiguous float32 device tensor ``xf`` [n, d], d a multiple of 4 in 1..16384, n < 2**31.  'f32' wraps ``xf`` without
+    a copy; 'bf16' makes an [n, d] copy with grl_refine_pack_bf16 (round to nearest even, every NaN 0x7fc0, infinities
+    and zeros preserved): half the bytes.  A row's VALUE is the float32 widening of what is stored, and every distance of
+    ``refine_dist`` is defined on the values.  ``n``, ``d``, ``dtype``, ``nbytes``; ``rows(ids)`` returns the values of
+    the given rows as float32.  ValueError names the argument that is wrong."""
+
+    def __init__(self, xf, dtype='f32'):
+        if dtype not in REFINE_TYPES:
+            raise ValueError("RefineStore: dtype must be 'f32' or 'bf16' (got %r)" % (dtype,))
+        if not torch.is_tensor(xf) or xf.dim() != 2:
+            raise ValueError('RefineStore: xf must be a [n, d] tensor (got %s)'
+                             % (tuple(xf.shape) if torch.is_tensor(xf) else type(xf).__name__,))
+        n, d = (int(v) for v in xf.shape)
+        _refine_d(d, 'RefineStore', 'xf')
+        if n >= 2 ** 31:
+            raise ValueError('RefineStore: xf must have fewer than 2**31 rows (got %d)' % n)
+        require_device(xf, 'xf')
+        if not xf.is_contiguous():
+            raise ValueError('RefineStore: xf must be contiguous (got strides %s)' % (tuple(xf.stride()),))
+        self.n, self.d, self.dtype = n, d, dtype
+        if dtype == 'f32':
+            self.data = xf
+        else:
+            self.data = torch.empty((n, d), dtype=torch.bfloat16, device=xf.device)
+            if n:
+                _call('grl_refine_pack_bf16', ptr(xf), ptr(self.data), n * d)
+        self.nbytes = n * d * (4 if dtype == 'f32' else 2)
+
+    def rows(self, ids):
+        if not (torch.is_tensor(ids) and ids.is_cuda and ids.dim() == 1 and not ids.dtype.is_floating_point
+                and not ids.dtype.is_complex and ids.dtype != torch.bool):
+            raise ValueError('RefineStore.rows: ids must be a 1-d integer device tensor of row indices')
+        ids = ids.to(torch.int64)
+        if ids.numel() and bool(((ids < 0) | (ids >= self.n)).any()):
+            raise ValueError('RefineStore.rows: ids must be in 0..n-1 = 0..%d' % (self.n - 1))
+        return self.data[ids].to(torch.float32)
+
+
+def _refine_args(qf, store, cand, metric, what):
+    _cluster_metric(metric, what)
+    if not isinstance(store, RefineStore):
+        raise ValueError('%s: store must be a RefineStore (got %s)' % (what, type(store).__name__))
+    if not torch.is_tensor(qf) or qf.dim() != 2 or qf.shape[1] != store.d:
+        raise ValueError('%s: qf must be [rows, d] = [rows, %d] (got %s)'
+                         % (what, store.d, tuple(qf.shape) if torch.is_tensor(qf) else type(qf).__name__))
+    if not (torch.is_tensor(cand) and cand.dim() == 2 and cand.dtype == torch.int64 and cand.shape[0] == qf.shape[0]):
+        raise ValueError('%s: cand must be an int64 device tensor [nq, L] = [%d, L] (got %s)'
+                         % (what, qf.shape[0], (tuple(cand.shape), cand.dtype) if torch.is_tensor(cand) else type(cand).__name__))
+    require_device(qf, 'qf')
+    if not cand.is_cuda:
+        raise ValueError('%s: cand must be an int64 device tensor [nq, L] (got a tensor on %s)' % (what, cand.device))
+    return qf.contiguous(), cand.contiguous()
+
+
+def _refine_scan(qf, store, cand, metric, out, cidx):
+    """one grl_refine_scan: out / cidx [rows, L] of the (at most 65535) query rows ``qf`` and their lists ``cand``"""
+    rows, L = cand.shape
+    _call('grl_refine_scan', ptr(qf), store.d, ptr(store.data), store.d, REFINE_TYPES[store.dtype], ptr(cand), L, ptr(out),
+          ptr(cidx), L, rows, L, store.n, store.d, PQ_METRICS[metric])
+
+
+def refine_dist(qf, store, cand, metric='cosine'):
+    """The [nq, L] float32 distance block of the index lists ``cand`` (int64 [nq, L] on the device: ``search``'s,
+    ``pq_search``'s or ``ivf_search``'s index lists as they come) against the rows of ``store``, for tests and small
+    cases: entry (q, j) is the normative pair distance of include/grl_hip.h between qf[q] and the value of store row
+    cand[q, j] -- 'cosine' the negated dot product, 'euclidean' sqrt(max(sum (q - x)^2, 1e-12)) with the difference taken
+    first -- in a fixed fp32 order (no fma, no atomics): tests/refine_ref.py gives the same bits.  An entry < 0 or >= n is
+    padding: never dereferenced, +inf."""
+    qf, cand = _refine_args(qf, store, cand, metric, 'refine_dist')
+    nq, L = cand.shape
+    out = torch.full((nq, L), float('inf'), dtype=torch.float32, device=qf.device)
+    if nq and L and store.n:
+        cidx = torch.empty((min(nq, 65535), L), dtype=torch.int32, device=qf.device)
+        for q0 in range(0, nq, 65535):
+            q1 = min(q0 + 65535, nq)
+            _refine_scan(qf[q0:q1], store, cand[q0:q1], metric, out[q0:q1], cidx[:q1 - q0])
+    return out
+
+
+def refine_lists(qf, store, cand, k, metric='cosine', block_bytes=None):
+    """The candidates ``cand`` (int64 [nq, L] on the device, any L; an entry < 0 or >= n is padding, a repeated id is a
+    candidate twice) of every query re-sorted by their exact distances to the rows of ``store``: ``(dist [nq, k] float32,
+    idx [nq, k] int64)``, the first k of each row's candidates in grl_row_argsort's order (canonical NaN, -0 == +0, ties to
+    the smaller gallery index) with the normative distances of ``refine_dist``; padding is index -1, distance +inf.
+    1 <= k <= 1024.  The distance block and the id block (8 bytes per pair) are served in query row blocks that fit
+    ``block_bytes`` (default GRL_SEARCH_BLOCK_BYTES), each ranked by grl_topk_block with the id block as its cidx: the
+    same bits for every blocking.  A ``verify_metric`` is refused.  Not sharded: every rank computes the full result."""
+    k = _pq_int(k, 1, SEARCH_K_MAX, 'refine_lists', 'k')
+    qf, cand = _refine_args(qf, store, cand, metric, 'refine_lists')
+    nq, L = cand.shape
+    dev = qf.device
+    run_key = torch.full((nq, k), -1, dtype=torch.int64, device=dev)          # all-ones composite = empty slot
+    run_val = torch.full((nq, k), float('inf'), dtype=torch.float32, device=dev)
+    if nq and L and store.n:
+        budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
+        rows = max(1, min(65535, nq, budget // (8 * L)))
+        d = _new((rows, L), qf)
+        cidx = torch.empty((rows, L), dtype=torch.int32, device=dev)
+        for q0 in range(0, nq, rows):
+            q1 = min(q0 + rows, nq)
+            _refine_scan(qf[q0:q1], store, cand[q0:q1], metric, d, cidx)
+            _call('grl_topk_block', ptr(d), L, ptr(cidx), L, q1 - q0, L, 0, k, ptr(run_key[q0:]), ptr(run_val[q0:]))
+    idx = run_key & 0xffffffff
+    idx[idx == 0xffffffff] = -1
+    return run_val, idx
+
+
+def refine_search(qf, index, store, k, R, nprobe=None, exclude=None, block_bytes=None):
+    """Two-stage search: a shortlist of ``R`` candidates per query from the codes of ``index`` (a ``PqIndex``: pq_search;
+    an ``IvfPqIndex``: ivf_search with ``nprobe``, which is required there and refused for the flat index), re-sorted by
+    the exact distances to the rows of ``store`` -- exactly ``refine_lists(qf, store, S(qf, index, R, ..., exclude=exclude)[1],
+    k, index metric)``.  The junk rule ``exclude`` is applied in the first stage and nowhere else.  k <= R <= 1024;
+    store.n and store.d must be the index's.  ValueError names the argument that is wrong."""
+    if isinstance(index, PqIndex):
+        flat, metric, d = True, index.codebook.metric, index.codebook.d
+        if nprobe is not None:
+            raise ValueError('refine_search: nprobe is for an IvfPqIndex; a PqIndex scans every row (got nprobe = %r)' % (nprobe,))
+    elif isinstance(index, IvfPqIndex):
+        flat, metric, d = False, index.book.metric, index.book.d
+        if nprobe is None:
+            raise ValueError('refine_search: nprobe is required for an IvfPqIndex')
+    else:
+        raise ValueError('refine_search: index must be a PqIndex or an IvfPqIndex (got %s)' % type(index).__name__)
+    if not isinstance(store, RefineStore):
+        raise ValueError('refine_search: store must be a RefineStore (got %s)' % type(store).__name__)
+    if store.n != index.n or store.d != d:
+        raise ValueError('refine_search: store must hold the rows of the index: store is [%d, %d], the index [%d, %d]'
+                         % (store.n, store.d, index.n, d))
+    k = _pq_int(k, 1, SEARCH_K_MAX, 'refine_search', 'k')
+    R = _pq_int(R, k, SEARCH_K_MAX, 'refine_search', 'R (k <= R <= %d)' % SEARCH_K_MAX)
+    if flat:
+        cand = pq_search(qf, index, R, exclude=exclude, block_bytes=block_bytes)[1]
+    else:
+        cand = ivf_search(qf, index, R, nprobe, exclude=exclude, block_bytes=block_bytes)[1]
+    return refine_lists(qf, store, cand, k, metric, block_bytes)

@@ -554,7 +554,7 @@ def _pq_report(knob, qf, gf, ids, path, keep=None):
     ks = (1, 10, 100)
     recall = engine.topk_recall(approx, exact, ks)
     if keep is not None:                                   # (GRL_EVAL_IVF reports next to these)
-        keep.update(k=k, exact=exact, recall=recall)
+        keep.update(k=k, exact=exact, recall=recall, index=index)
     feature_bytes = 4 * int(gf.size(0)) * int(gf.size(1))
     ranks = [r for r in (1, 5, 10, 20) if r <= len(cmc)]
     lines = ['PQ: M = {}, nbits = {} ({} bytes per row of {}), {} rows'.format(M, nbits, M, 4 * int(gf.size(1)), index.n),
@@ -608,6 +608,7 @@ def _ivf_report(knob, pq_knob, pq_kept, qf, gf, ids, path):
     k, ks = pq_kept['k'], (1, 10, 100)
     approx = engine.ivf_search(qf, index, k, nprobe, exclude=ids)[1]
     recall = engine.topk_recall(approx, pq_kept['exact'], ks)
+    pq_kept.update(ivf_index=index, ivf_nprobe=nprobe, ivf_recall=recall)      # (GRL_EVAL_REFINE reports next to these)
     nq = int(qf.size(0))
     scanned = float(engine.ivf_probe_stats(qf, index, nprobe).sum()) / max(nq * index.n, 1)
     mean_len = index.n / float(nlist)
@@ -629,6 +630,63 @@ def _ivf_report(knob, pq_knob, pq_kept, qf, gf, ids, path):
               'pq_recall': {str(kk): fin(r) for kk, r in zip(ks, pq_kept['recall'])},
               'index_bytes': int(index.nbytes), 'feature_bytes': feature_bytes}
         with open((path or '') + 'ivf.json', 'w') as fh:
+            json.dump(js, fh, allow_nan=False)
+    return lines
+
+
+def parse_refine_knob(name, value):
+    """``GRL_EVAL_REFINE``: unset or empty -> None (off); "R", "R,bf16" or "R,f32" -> (R, dtype) with an integer R in
+    1..1024 (the shortlist taken from the codes and re-sorted by exact distances, engine.refine_search) and the type of
+    the feature store (default 'f32').  Anything else is a ValueError that names the variable."""
+    if value is None or not value.strip():
+        return None
+    parts = [p.strip() for p in value.split(',')]
+    try:
+        if len(parts) > 2:
+            raise ValueError
+        R = int(parts[0])
+        dtype = parts[1] if len(parts) == 2 else 'f32'
+        if dtype not in ('f32', 'bf16'):
+            raise ValueError
+    except ValueError:
+        raise ValueError('%s must be "R", "R,bf16" or "R,f32" with an integer R (got %r)' % (name, value))
+    if not 1 <= R <= engine.SEARCH_K_MAX:
+        raise ValueError('%s: R must be in 1..%d (got %r)' % (name, engine.SEARCH_K_MAX, value))
+    return R, dtype
+
+
+def _refine_report(knob, kept, qf, gf, ids, path):
+    """GRL_EVAL_REFINE: a feature store of the query-prepended gallery ``gf`` (engine.RefineStore) and the two-stage search
+    engine.refine_search over GRL_EVAL_PQ's index and, when GRL_EVAL_IVF is set, over its index -- the lines printed after
+    theirs: the store bytes, recall@1 / 10 / 100 of the refined lists against engine.search under the same junk rule next
+    to the unrefined figures -- and ``path + 'refine.json'`` (rank 0 alone writes; strict JSON).  A report only."""
+    import json
+    R, dtype = knob
+    store = engine.RefineStore(gf.contiguous(), dtype)
+    ks = (1, 10, 100)
+    k = min(kept['k'], R)
+    feature_bytes = 4 * int(gf.size(0)) * int(gf.size(1))
+    lines = ['Refine: R = {}, k = {}, {} store of {} bytes against {} bytes of features'.format(
+        R, k, dtype, store.nbytes, feature_bytes)]
+
+    def fin(v):
+        return v if math.isfinite(v) else None
+    js = {'R': R, 'k': k, 'store': dtype, 'store_bytes': int(store.nbytes), 'feature_bytes': feature_bytes, 'metric': 'cosine',
+          'n': store.n, 'n_queries': int(qf.size(0))}
+    pq_recall = engine.topk_recall(engine.refine_search(qf, kept['index'], store, k, R, exclude=ids)[1], kept['exact'], ks)
+    lines.append('Refined PQ recall@1: {:.2%}  @10: {:.2%}  @100: {:.2%}  (ADC {:.2%}  {:.2%}  {:.2%})'.format(
+        *(tuple(pq_recall) + tuple(kept['recall']))))
+    js['pq'] = {'refined_recall': {str(kk): fin(r) for kk, r in zip(ks, pq_recall)},
+                'recall': {str(kk): fin(r) for kk, r in zip(ks, kept['recall'])}}
+    if 'ivf_index' in kept:
+        recall = engine.topk_recall(engine.refine_search(qf, kept['ivf_index'], store, k, R, nprobe=kept['ivf_nprobe'],
+                                                         exclude=ids)[1], kept['exact'], ks)
+        lines.append('Refined IVF recall@1: {:.2%}  @10: {:.2%}  @100: {:.2%}  (IVF {:.2%}  {:.2%}  {:.2%})'.format(
+            *(tuple(recall) + tuple(kept['ivf_recall']))))
+        js['ivf'] = {'nprobe': kept['ivf_nprobe'], 'refined_recall': {str(kk): fin(r) for kk, r in zip(ks, recall)},
+                     'recall': {str(kk): fin(r) for kk, r in zip(ks, kept['ivf_recall'])}}
+    if grl_dist._rank_world(None, None)[0] == 0:
+        with open((path or '') + 'refine.json', 'w') as fh:
             json.dump(js, fh, allow_nan=False)
     return lines
 
@@ -863,6 +921,11 @@ class ATTEvaluator(object):
         if ivf_knob is not None and pq_knob is None:
             raise ValueError('GRL_EVAL_IVF=%s needs GRL_EVAL_PQ: the index encodes its residuals with GRL_EVAL_PQ\'s M, nbits, '
                              'max_iter and seed (set GRL_EVAL_PQ too)' % os.environ['GRL_EVAL_IVF'].strip())
+        # exact refinement of the indexes' shortlists from a feature store, off by default (engine.refine_search): one more report
+        refine_knob = parse_refine_knob('GRL_EVAL_REFINE', os.environ.get('GRL_EVAL_REFINE'))
+        if refine_knob is not None and pq_knob is None:
+            raise ValueError('GRL_EVAL_REFINE=%s needs GRL_EVAL_PQ: the shortlists come from GRL_EVAL_PQ\'s index (and '
+                             'GRL_EVAL_IVF\'s, when set); set GRL_EVAL_PQ too' % os.environ['GRL_EVAL_REFINE'].strip())
         if pq_knob is not None:
             why = None
             if rerank:
@@ -948,10 +1011,12 @@ class ATTEvaluator(object):
             if tsne_knob is not None:
                 lines = tuple(lines) + tuple(_tsne_report(tsne_knob, gf, ids, path))
             if pq_knob is not None:
-                kept = {} if ivf_knob is not None else None
+                kept = {} if ivf_knob is not None or refine_knob is not None else None
                 lines = tuple(lines) + tuple(_pq_report(pq_knob, qf, gf, ids, path, kept))
                 if ivf_knob is not None:
                     lines = tuple(lines) + tuple(_ivf_report(ivf_knob, pq_knob, kept, qf, gf, ids, path))
+                if refine_knob is not None:
+                    lines = tuple(lines) + tuple(_refine_report(refine_knob, kept, qf, gf, ids, path))
             return lines
         if set_knob is not None:
             reduce, metric = set_knob

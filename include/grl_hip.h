@@ -1033,6 +1033,41 @@ int grl_ivf_reconstruct(const float* coarse, const float* codebooks, const int32
                         int64_t rows, int nlist, int M, int ksub, int dsub, int64_t ldo, void* stream);
 int grl_ivf_check_labels(const int32_t* labels, int64_t n, int nlist, int32_t* flag, void* stream);
 
+/* ---- exact refinement of a shortlist from a feature store (refine.hip, engine.RefineStore / refine_dist / refine_lists /
+ * refine_search).  Additive: GRL_ABI_VERSION stays 10. ----
+ * The store holds the n gallery rows of d columns, d % 4 == 0, 1 <= d <= GRL_REFINE_D_MAX (the query row is staged in
+ * LDS: d * 4 bytes, 64 KiB at the maximum), as fp32 (GRL_REFINE_F32, row stride lds floats) or as bf16 (GRL_REFINE_BF16,
+ * uint16 [n][lds]); a row's VALUE is the fp32 widening of what is stored.  With u = 2^-24:
+ * Pair distance, normative.  For query row q and store row x, per column c: GRL_PQ_COSINE p_c = fl(q_c * x_c);
+ * GRL_PQ_EUCLIDEAN e_c = fl(q_c - x_c), p_c = fl(e_c * e_c).  Every rounding is kept (no fma).  Lane l (0..63) owns the
+ * columns 256 t + 4 l + e, e = 0..3, t = 0, 1, ..:
+ *   1. its four partials a_e are the sequential fp32 sums from +0.0f of p_c over t ascending; columns >= d are skipped
+ *      (the same as adding +0.0f: a partial that starts at +0.0f is never -0.0f, so a model may pad with zeros);
+ *   2. v_l = (a_0 + a_1) + (a_2 + a_3);
+ *   3. v_l = v_l + v_{l xor o} for o = 32, 16, 8, 4, 2, 1 (common.h's wave_sum): every lane ends with the same bits S;
+ *   4. GRL_PQ_COSINE: dist = -S.  GRL_PQ_EUCLIDEAN: dist = sqrtf(S > 1e-12f ? S : 1e-12f) (a NaN S gives 1e-12f, as
+ *      GRL_EPI_EUCLID does); the difference is taken first, so no norm arrays are needed and nothing cancels;
+ *   5. a NaN result is stored as 0x7fc00000.
+ * No atomics of any kind: the same bits on every run, for every nq, L, slab and launch; tests/refine_ref.py is this
+ * paragraph in numpy float32, bit for bit.
+ * grl_refine_scan: cand int64 [nq][ldc] (L used) are index lists as grl_topk_block's callers return them; out[q][j] =
+ * dist(q, cand[q][j]) and cidx[q][j] = (int32) cand[q][j], rows of stride ldo >= L.  An entry < 0 or >= n is padding: it
+ * is never dereferenced, out = +inf and cidx = -1 (grl_topk_block skips it).  A repeated id is a candidate twice.
+ * grl_refine_pack_bf16: out[i] = bf16(x[i]), i < count: round to nearest even on the upper 16 bits, every NaN becomes
+ * 0x7fc0, +-inf and +-0 keep their bits, a finite value beyond the bf16 range rounds to infinity.  One lane per 8 elements
+ * (16-byte accesses when both pointers are 16-byte aligned), the ragged end element by element.
+ * GRL_EINVAL, before any launch: a null pointer, a negative size, n >= 2^31, d outside 1..GRL_REFINE_D_MAX or no multiple of
+ * 4, an unknown store type or metric, a stride that is too small or (ldq, lds) no multiple of 4, a pointer that is not
+ * aligned (16 bytes: q and an fp32 store; 8 bytes: a bf16 store and cand; 4 bytes: out, cidx and x; 2 bytes: the bf16
+ * output), nq > 65535. */
+#define GRL_REFINE_F32    0
+#define GRL_REFINE_BF16   1
+#define GRL_REFINE_D_MAX  16384
+int grl_refine_scan(const float* q, int64_t ldq, const void* store, int64_t lds, int store_type, const int64_t* cand,
+                    int64_t ldc, float* out, int32_t* cidx, int64_t ldo, int nq, int L, int64_t n, int d, int metric,
+                    void* stream);
+int grl_refine_pack_bf16(const float* x, uint16_t* out, int64_t count, void* stream);
+
 /* ---- ranking by the Siamese verification head (verify.hip, engine.verify_metric / verify_dist) ----
  * In eval mode classifierBN -> classifierlinear on (p - g)^2 is affine in (p - g)^2; the class-1 minus class-0 logit is
  * s(p, g) = sum_d w_d (p_d - g_d)^2 + c.  The ranking distance F = (1 - beta)(-q.g) + beta(-s), p / g = columns
