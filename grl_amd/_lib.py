@@ -227,6 +227,12 @@ _SIGNATURES = {
     'grl_refine_scan': ([_fp, _i64, _fp, _i64, C.c_int, _fp, _i64, _fp, _fp, _i64, C.c_int, C.c_int, _i64, C.c_int, C.c_int,
                          _fp], C.c_int),
     'grl_refine_pack_bf16': ([_fp, _fp, _i64, _fp], C.c_int),
+    # kNN-graph index and beam search (nng.hip)
+    'grl_nng_search_lds_bytes': ([_i64, C.c_int, C.c_int, C.c_int, C.c_int, _i64, C.c_int], _i64),
+    'grl_nng_search': ([_fp, _i64, _fp, _i64, C.c_int, _fp, _fp, _i64, _fp, _fp, _fp, C.c_int, _i64] + [C.c_int] * 7 + [_fp],
+                       C.c_int),
+    'grl_nng_detours': ([_fp, _fp, _i64, C.c_int, _fp], C.c_int),
+    'grl_nng_merge': ([_fp, _fp, _fp, _fp, _i64, C.c_int, _fp], C.c_int),
     'grl_verify_fold': ([_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
     'grl_verify_rows': ([_fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, _fp],
                         C.c_int),

@@ -5175,3 +5175,232 @@ def refine_search(qf, index, store, k, R, nprobe=None, exclude=None, block_bytes
     else:
         cand = ivf_search(qf, index, R, nprobe, exclude=exclude, block_bytes=block_bytes)[1]
     return refine_lists(qf, store, cand, k, metric, block_bytes)
+
+
+# ----------------------------------------------------------------------------
+# kNN-graph gallery index with beam search on the device (nng.hip)
+# ----------------------------------------------------------------------------
+NNG_K_MAX, NNG_D_MAX = 128, 64                                        # GRL_NNG_* of include/grl_hip.h
+NNG_L_MIN, NNG_L_MAX, NNG_W_MAX, NNG_WD_MAX = 8, 512, 8, 256
+NNG_LDS_MAX = 65536
+NNG_QUERY_BLOCK = int(os.environ.get('GRL_NNG_QUERY_BLOCK', '65535'))  # queries per grl_nng_search call (1..65535)
+
+
+def _nng_store(x, dtype, what, name):
+    """``x`` as a RefineStore: a store as it is, a float32 device tensor [n, d] wrapped (``dtype``)"""
+    if isinstance(x, RefineStore):
+        return x, False
+    if not torch.is_tensor(x):
+        raise ValueError('%s: %s must be a RefineStore or a [n, d] float32 device tensor (got %s)' % (what, name, type(x).__name__))
+    return RefineStore(x.contiguous() if x.dim() == 2 else x, dtype), dtype != 'f32'
+
+
+def nng_knn(store_or_xf, K, metric='cosine', block_bytes=None):
+    """int64 [n, K] on the device: the exact K nearest OTHER rows of every row of ``store_or_xf`` (an fp32 ``RefineStore``
+    or a float32 device tensor [n, d]), nearest first -- ``search`` of the rows against themselves with the row itself
+    removed by its junk rule (pids = the row numbers, one camera); -1 pads a row when n - 1 < K.  2 <= K <= 128."""
+    _cluster_metric(metric, 'nng_knn')
+    K = _pq_int(K, 2, NNG_K_MAX, 'nng_knn', 'K')
+    if isinstance(store_or_xf, RefineStore):
+        if store_or_xf.dtype != 'f32':
+            raise ValueError("nng_knn: store_or_xf must be an 'f32' RefineStore: the exact lists are taken on the fp32 rows "
+                             "(got a %r store)" % (store_or_xf.dtype,))
+        xf = store_or_xf.data
+    else:
+        xf = _nng_store(store_or_xf, 'f32', 'nng_knn', 'store_or_xf')[0].data
+    n = int(xf.shape[0])
+    import numpy as np
+    ids, cams = np.arange(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    return search(xf, xf, K, metric, exclude=(ids, ids, cams, cams), block_bytes=block_bytes)[1]
+
+
+def nng_optimize(knn, D):
+    """int32 [n, D] on the device: the neighbour table of the candidate lists ``knn`` (an integer device tensor [n, K],
+    row i = the candidate neighbours of i, nearest first; an entry equal to i, outside 0..n-1 or repeated is padding) --
+    the graph optimisation of include/grl_hip.h: rank-based detour counts (grl_nng_detours), the first D live positions
+    by (detours, position), the reverse lists by (position, source) and their merge (grl_nng_merge).  Integers only:
+    tests/nng_ref.py gives the same table.  2 <= K <= 128, D even in 2..min(K, 64).  No host loop over n, nothing n x n."""
+    if not (torch.is_tensor(knn) and knn.is_cuda and knn.dim() == 2 and not knn.dtype.is_floating_point
+            and not knn.dtype.is_complex and knn.dtype != torch.bool):
+        raise ValueError('nng_optimize: knn must be an integer device tensor [n, K] (got %s)'
+                         % ((tuple(knn.shape), knn.dtype, knn.device) if torch.is_tensor(knn) else type(knn).__name__,))
+    n, K = (int(v) for v in knn.shape)
+    if not 2 <= K <= NNG_K_MAX:
+        raise ValueError('nng_optimize: knn must have K columns with K in 2..%d (got K = %d)' % (NNG_K_MAX, K))
+    if n >= 2 ** 31:
+        raise ValueError('nng_optimize: knn must have fewer than 2**31 rows (got %d)' % n)
+    D = _pq_int(D, 2, min(K, NNG_D_MAX), 'nng_optimize', 'D (even, 2 <= D <= min(K, %d))' % NNG_D_MAX)
+    if D % 2:
+        raise ValueError('nng_optimize: D must be even (got %d)' % D)
+    dev = knn.device
+    out = torch.full((n, D), -1, dtype=torch.int32, device=dev)
+    if n == 0:
+        return out
+    knn = knn.to(torch.int64)
+    knn32 = torch.where((knn >= 0) & (knn < n), knn, torch.full_like(knn, -1)).to(torch.int32).contiguous()
+    det = torch.empty((n, K), dtype=torch.int32, device=dev)
+    _call('grl_nng_detours', ptr(knn32), ptr(det), n, K)
+    # the first D live positions by (det, b): one integer sort per row
+    pos = torch.arange(K, dtype=torch.int64, device=dev).view(1, K)
+    pad = K * K + K
+    key, order = torch.where(det >= 0, det.to(torch.int64) * K + pos, torch.full_like(pos, pad)).sort(dim=1)
+    fwd = torch.where(key[:, :D] < pad, knn32.gather(1, order[:, :D]), torch.full_like(knn32[:, :D], -1)).contiguous()
+    # the reverse lists in CSR form, ordered by (position in F, source): a stable sort by target of the (position, source) order
+    flat = fwd.t().contiguous().view(-1)
+    keep = flat >= 0
+    tgt = flat[keep].to(torch.int64)
+    src = torch.arange(n, dtype=torch.int32, device=dev).repeat(D)[keep]
+    rev = src[torch.sort(tgt, stable=True)[1]].contiguous()
+    off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    off[1:] = torch.bincount(tgt, minlength=n).cumsum(0)
+    if rev.numel() == 0:
+        rev = torch.full((1,), -1, dtype=torch.int32, device=dev)
+    _call('grl_nng_merge', ptr(fwd), ptr(off), ptr(rev), ptr(out), n, D)
+    return out
+
+
+class NnGraphIndex(object):
+    """A kNN-graph index over the rows of a feature store: ``NnGraphIndex(store, neighbors, metric)`` wraps
+    the caller's ``RefineStore`` (n rows) and neighbour table ``neighbors`` (int32 device tensor [n, D], contiguous, D even
+    in 2..64; an entry outside 0..n-1 is padding) without copying either.  ``n``, ``d``, ``D``, ``metric``, ``store``,
+    ``neighbors``, ``nbytes`` (the table; ``nng_build`` adds the store when it made one).  ValueError names what is wrong."""
+
+    def __init__(self, store, neighbors, metric='cosine'):
+        _cluster_metric(metric, 'NnGraphIndex')
+        if not isinstance(store, RefineStore):
+            raise ValueError('NnGraphIndex: store must be a RefineStore (got %s)' % type(store).__name__)
+        if not (torch.is_tensor(neighbors) and neighbors.dim() == 2 and neighbors.dtype == torch.int32):
+            raise ValueError('NnGraphIndex: neighbors must be an int32 device tensor [n, D] (got %s)'
+                             % ((tuple(neighbors.shape), neighbors.dtype) if torch.is_tensor(neighbors)
+                                else type(neighbors).__name__,))
+        if not neighbors.is_cuda or neighbors.device != store.data.device:
+            raise ValueError('NnGraphIndex: neighbors must be on the device of the store, %s (got %s)'
+                             % (store.data.device, neighbors.device))
+        n, D = (int(v) for v in neighbors.shape)
+        if n != store.n:
+            raise ValueError('NnGraphIndex: neighbors must have one row per store row: the store has %d, neighbors %d' % (store.n, n))
+        if D % 2 or not 2 <= D <= NNG_D_MAX:
+            raise ValueError('NnGraphIndex: neighbors must have D columns with D even in 2..%d (got D = %d)' % (NNG_D_MAX, D))
+        if not neighbors.is_contiguous():
+            raise ValueError('NnGraphIndex: neighbors must be contiguous (got strides %s)' % (tuple(neighbors.stride()),))
+        self.store, self.neighbors, self.metric = store, neighbors, metric
+        self.n, self.d, self.D = n, store.d, D
+        self.nbytes = n * D * 4
+
+
+def nng_build(xf_or_store, K=64, D=32, metric='cosine', dtype='f32', knn=None):
+    """The index of the rows ``xf_or_store``: a float32 device tensor [n, d] (the index then owns a ``RefineStore`` of
+    ``dtype`` 'f32' | 'bf16' over it; a bf16 copy counts in ``nbytes``) or a ``RefineStore`` (used as it is; ``dtype``
+    must be its own).  ``knn=None`` takes the exact lists ``nng_knn(rows, K, metric)`` of the fp32 rows; a caller brings
+    approximate ones (an integer device tensor [n, K'], e.g. the lists of ``refine_search`` of the rows against their own
+    index) for a large n, and K is then K'.  Equal to ``NnGraphIndex(store, nng_optimize(knn, D), metric)``."""
+    _cluster_metric(metric, 'nng_build')
+    if dtype not in REFINE_TYPES:
+        raise ValueError("nng_build: dtype must be 'f32' or 'bf16' (got %r)" % (dtype,))
+    if isinstance(xf_or_store, RefineStore):
+        if xf_or_store.dtype != dtype:
+            raise ValueError('nng_build: dtype must be the store\'s own, %r (got %r)' % (xf_or_store.dtype, dtype))
+        store, owned = xf_or_store, False
+        if knn is None and dtype != 'f32':
+            raise ValueError("nng_build: knn is required with a 'bf16' RefineStore: the exact lists are taken on fp32 rows")
+        rows = store.data
+    else:
+        store, owned = _nng_store(xf_or_store, dtype, 'nng_build', 'xf_or_store')
+        rows = xf_or_store.contiguous()
+    if knn is None:
+        K = _pq_int(K, 2, NNG_K_MAX, 'nng_build', 'K')
+        knn = nng_knn(rows, K, metric)
+    elif torch.is_tensor(knn) and knn.dim() == 2 and knn.shape[0] != store.n:
+        raise ValueError('nng_build: knn must have one row per store row: the store has %d, knn %d' % (store.n, knn.shape[0]))
+    index = NnGraphIndex(store, nng_optimize(knn, D), metric)
+    if owned:
+        index.nbytes += store.nbytes
+    return index
+
+
+def nng_default_seeds(n, L):
+    """the seeds of ``nng_search(seeds=None)``: S = min(L, n) row numbers floor(j * n / S), a python list"""
+    S = min(int(L), int(n))
+    return [(j * int(n)) // S for j in range(S)]
+
+
+def nng_search(qf, index, k, L=64, w=1, T=64, seeds=None, exclude=None, return_stats=False):
+    """Each query's ``k`` nearest rows by a beam search on the graph of ``index`` (an ``NnGraphIndex``): ``(dist [nq, k]
+    float32, idx [nq, k] int64)`` on the device, and with ``return_stats`` a third value, int32 [nq, 2]: the rows visited
+    (= scored) and the iterations run.  One grl_nng_search launch per block of at most 65535 queries walks the graph from
+    the ``seeds`` with an itopk list of ``L`` entries (a power of two in 8..512, k <= L), ``w`` parents per iteration
+    (1..8, w * D <= 256) and at most ``T`` iterations, and scores every visited row with the normative pair distance of
+    ``refine_dist`` on the index's store: the lists need no second stage, and tests/nng_ref.py gives the same bits.
+    ``seeds=None``: S = min(L, n) evenly spaced rows floor(j * n / S); else an integer device tensor [S] (shared) or
+    [nq, S] (per query, e.g. the head of an ``ivf_search`` list), 1 <= S <= L, entries outside 0..n-1 and repeats skipped.
+    ``exclude`` is the junk tuple of ``search``: junk rows are walked like any other (dropping them would cut a query off
+    from its own neighbourhood) and are removed from the finished list of L, of which the first k remaining are returned;
+    with fewer than k left the tail is index -1, distance +inf.  The workgroup's LDS (query row, sort buffer, visited table
+    of >= 2 min(S + T * w * D, n) slots) must fit 64 KiB: ValueError names the bytes and the limit otherwise.  A
+    ``verify_metric`` is refused.  Not sharded: every rank computes the full result."""
+    what = 'nng_search'
+    if not isinstance(index, NnGraphIndex):
+        raise ValueError('%s: index must be an NnGraphIndex (got %s); a verify_metric or any other ranking is refused: the '
+                         'walk scores rows by cosine or euclidean pair distances' % (what, type(index).__name__))
+    store, n, D = index.store, index.n, index.D
+    if not torch.is_tensor(qf) or qf.dim() != 2 or qf.shape[1] != store.d:
+        raise ValueError('%s: qf must be [rows, d] = [rows, %d] (got %s)'
+                         % (what, store.d, tuple(qf.shape) if torch.is_tensor(qf) else type(qf).__name__))
+    require_device(qf, 'qf')
+    qf = qf.contiguous()
+    nq, dev = int(qf.shape[0]), qf.device
+    L = _pq_int(L, NNG_L_MIN, NNG_L_MAX, what, 'L (a power of two)')
+    if L & (L - 1):
+        raise ValueError('%s: L must be a power of two in %d..%d (got %d)' % (what, NNG_L_MIN, NNG_L_MAX, L))
+    k = _pq_int(k, 1, L, what, 'k (k <= L = %d)' % L)
+    w = _pq_int(w, 1, NNG_W_MAX, what, 'w')
+    if w * D > NNG_WD_MAX:
+        raise ValueError('%s: w must keep w * D <= %d (got w = %d with D = %d)' % (what, NNG_WD_MAX, w, D))
+    T = _pq_int(T, 1, 2 ** 31 - 1, what, 'T')
+    if seeds is None:
+        if n == 0:
+            seeds_t, S, stride = torch.zeros(1, dtype=torch.int32, device=dev), 1, 0
+        else:
+            s = nng_default_seeds(n, L)
+            seeds_t, S, stride = torch.tensor(s, dtype=torch.int32, device=dev), len(s), 0
+    else:
+        if not (torch.is_tensor(seeds) and seeds.is_cuda and seeds.dim() in (1, 2) and not seeds.dtype.is_floating_point
+                and not seeds.dtype.is_complex and seeds.dtype != torch.bool):
+            raise ValueError('%s: seeds must be an integer device tensor [S] or [nq, S] (got %s)'
+                             % (what, (tuple(seeds.shape), seeds.dtype, seeds.device) if torch.is_tensor(seeds)
+                                else type(seeds).__name__))
+        if seeds.dim() == 2 and seeds.shape[0] != nq:
+            raise ValueError('%s: seeds [nq, S] must have one row per query: %d (got %d)' % (what, nq, seeds.shape[0]))
+        S = int(seeds.shape[-1])
+        if not 1 <= S <= L:
+            raise ValueError('%s: seeds must hold 1 <= S <= L = %d ids per query (got S = %d)' % (what, L, S))
+        s64 = seeds.to(torch.int64)
+        seeds_t = torch.where((s64 >= 0) & (s64 < n), s64, torch.full_like(s64, -1)).to(torch.int32).contiguous()
+        stride = S if seeds.dim() == 2 else 0
+    junk = _junk_ids(exclude, nq, n, dev)
+    need = int(_lib.load().grl_nng_search_lds_bytes(n, store.d, D, L, w, T, S))
+    if need > NNG_LDS_MAX:
+        raise ValueError('%s: the query row, the sort buffer and the visited table of d = %d, L = %d, w = %d, T = %d, S = %d, '
+                         'D = %d need %d bytes of LDS, the limit is %d (lower T, w or L)'
+                         % (what, store.d, L, w, T, S, D, need, NNG_LDS_MAX))
+    dist = torch.full((nq, L), float('inf'), dtype=torch.float32, device=dev)
+    idx32 = torch.full((nq, L), -1, dtype=torch.int32, device=dev)
+    stats = torch.zeros((nq, 2), dtype=torch.int32, device=dev)
+    if nq and n:
+        block = max(1, min(65535, NNG_QUERY_BLOCK))
+        for q0 in range(0, nq, block):
+            q1 = min(q0 + block, nq)
+            _call('grl_nng_search', ptr(qf[q0:q1]), store.d, ptr(store.data), store.d, REFINE_TYPES[store.dtype],
+                  ptr(index.neighbors), ptr(seeds_t[q0:] if stride else seeds_t), stride, ptr(dist[q0:q1]), ptr(idx32[q0:q1]),
+                  ptr(stats[q0:q1]), q1 - q0, n, store.d, D, L, w, T, S, PQ_METRICS[index.metric])
+    idx = idx32.to(torch.int64)
+    if junk is not None and nq:
+        q_pids, q_cams, g_pids, g_cams = junk
+        safe = idx.clamp(min=0)
+        drop = (idx >= 0) & (g_pids[safe] == q_pids.view(-1, 1)) & (g_cams[safe] == q_cams.view(-1, 1))
+        # kept entries first, in their order (the L-list is sorted; a stable sort of the drop flag keeps it)
+        order = torch.sort(drop.to(torch.int8), dim=1, stable=True)[1]
+        dist = torch.where(drop, torch.full_like(dist, float('inf')), dist).gather(1, order)
+        idx = torch.where(drop, torch.full_like(idx, -1), idx).gather(1, order)
+    dist, idx = dist[:, :k].contiguous(), idx[:, :k].contiguous()
+    return (dist, idx, stats) if return_stats else (dist, idx)

@@ -691,6 +691,70 @@ def _refine_report(knob, kept, qf, gf, ids, path):
     return lines
 
 
+def parse_nng_knob(name, value):
+    """``GRL_EVAL_NNG``: unset or empty -> None (off); "K,D", "K,D,L", "K,D,L,w", "K,D,L,w,T" or "K,D,L,w,T,bf16" (or
+    ",f32") -> (K, D, L, w, T, dtype): the exact candidate lists per row (K in 2..128), the degree of the optimised graph (D
+    even in 2..min(K, 64)), the itopk size (L a power of two in 8..512, default 64), the parents per iteration (w in 1..8
+    with w * D <= 256, default 1), the iteration cap (T >= 1, default 64) and the type of the feature store (default
+    'f32') of engine.nng_build / engine.nng_search.  Anything else is a ValueError that names the variable."""
+    if value is None or not value.strip():
+        return None
+    parts = [p.strip() for p in value.split(',')]
+    try:
+        if not 2 <= len(parts) <= 6:
+            raise ValueError
+        K, D = int(parts[0]), int(parts[1])
+        L = int(parts[2]) if len(parts) >= 3 else 64
+        w = int(parts[3]) if len(parts) >= 4 else 1
+        T = int(parts[4]) if len(parts) >= 5 else 64
+        dtype = parts[5] if len(parts) == 6 else 'f32'
+        if dtype not in ('f32', 'bf16'):
+            raise ValueError
+    except ValueError:
+        raise ValueError('%s must be "K,D", "K,D,L", "K,D,L,w", "K,D,L,w,T" or "K,D,L,w,T,bf16" with integers (got %r)'
+                         % (name, value))
+    if not 2 <= K <= engine.NNG_K_MAX or D % 2 or not 2 <= D <= min(K, engine.NNG_D_MAX) \
+            or not engine.NNG_L_MIN <= L <= engine.NNG_L_MAX or L & (L - 1) or not 1 <= w <= engine.NNG_W_MAX \
+            or w * D > engine.NNG_WD_MAX or not 1 <= T <= 2 ** 31 - 1:
+        raise ValueError('%s: K must be in 2..%d, D even in 2..min(K, %d), L a power of two in %d..%d, w in 1..%d with '
+                         'w * D <= %d and T >= 1 (got %r)' % (name, engine.NNG_K_MAX, engine.NNG_D_MAX, engine.NNG_L_MIN,
+                                                              engine.NNG_L_MAX, engine.NNG_W_MAX, engine.NNG_WD_MAX, value))
+    return K, D, L, w, T, dtype
+
+
+def _nng_report(knob, qf, gf, ids, path):
+    """GRL_EVAL_NNG: a kNN-graph index of the query-prepended gallery ``gf`` (engine.nng_build on the exact lists, by
+    cosine) -- the lines printed last: the graph, recall@1 / 10 / 100 of engine.nng_search against engine.search under the
+    same junk rule, the mean rows visited per query, the index bytes -- and ``path + 'nng.json'`` (rank 0 alone writes;
+    strict JSON).  A report only: the route's ranking is not touched."""
+    import json
+    K, D, L, w, T, dtype = knob
+    n = int(gf.size(0))
+    index = engine.nng_build(gf.contiguous(), K, D, 'cosine', dtype)
+    k = min(100, L, n)
+    approx, stats = engine.nng_search(qf, index, k, L, w, T, exclude=ids, return_stats=True)[1:]
+    exact = engine.search(qf, gf, k, exclude=ids)[1]
+    ks = (1, 10, 100)
+    recall = engine.topk_recall(approx, exact, ks)
+    nq = int(qf.size(0))
+    visited = float(stats[:, 0].sum()) / max(nq, 1)
+    iters = float(stats[:, 1].sum()) / max(nq, 1)
+    feature_bytes = 4 * n * int(gf.size(1))
+    lines = ['NNG: K = {}, D = {}, L = {}, w = {}, T = {}, {} store, {} rows'.format(K, index.D, L, w, T, dtype, index.n),
+             'NNG recall@1: {:.2%}  @10: {:.2%}  @100: {:.2%}  (k = {})'.format(*(tuple(recall) + (k,))),
+             'NNG visited rows per query: {:.1f} of {} ({:.2%}), {:.1f} iterations'.format(
+                 visited, n, visited / max(n, 1), iters),
+             'NNG index: {} bytes against {} bytes of features'.format(index.nbytes, feature_bytes)]
+    if grl_dist._rank_world(None, None)[0] == 0:
+        js = {'K': K, 'D': index.D, 'L': L, 'w': w, 'T': T, 'store': dtype, 'metric': 'cosine', 'n': index.n, 'n_queries': nq,
+              'k': k, 'recall': {str(kk): (r if math.isfinite(r) else None) for kk, r in zip(ks, recall)},
+              'visited_mean': visited, 'iterations_mean': iters, 'index_bytes': int(index.nbytes),
+              'feature_bytes': feature_bytes}
+        with open((path or '') + 'nng.json', 'w') as fh:
+            json.dump(js, fh, allow_nan=False)
+    return lines
+
+
 class ATTEvaluator(object):
     def __init__(self, cnn_model, Siamese_model, only_eval):
         self.cnn_model = cnn_model
@@ -926,6 +990,24 @@ class ATTEvaluator(object):
         if refine_knob is not None and pq_knob is None:
             raise ValueError('GRL_EVAL_REFINE=%s needs GRL_EVAL_PQ: the shortlists come from GRL_EVAL_PQ\'s index (and '
                              'GRL_EVAL_IVF\'s, when set); set GRL_EVAL_PQ too' % os.environ['GRL_EVAL_REFINE'].strip())
+        # a kNN-graph index of the gallery walked by a beam search, off by default (engine.nng_build / nng_search): a report
+        nng_knob = parse_nng_knob('GRL_EVAL_NNG', os.environ.get('GRL_EVAL_NNG'))
+        if nng_knob is not None:
+            why = None
+            if rerank:
+                why = 'cannot re-rank: the walk scores a query against gallery rows by cosine, and k-reciprocal ' \
+                      're-ranking ranks by a Jaccard blend of whole neighbourhoods (evaluate with rerank=0)'
+            elif knob is not None:
+                why = 'cannot be combined with GRL_EVAL_METRIC=%s: the walk scores rows by the cosine pair distance, not ' \
+                      'by the verification head (unset one of them)' % os.environ['GRL_EVAL_METRIC'].strip()
+            elif set_knob is not None:
+                why = 'cannot be combined with GRL_EVAL_SET: the set distances are taken between clip rows, and the ' \
+                      'graph holds one node per tracklet (unset one of them)'
+            elif diffusion_knob is not None:
+                why = 'cannot be combined with GRL_EVAL_DIFFUSION: the diffusion scores replace the cosine ranking the ' \
+                      'walk approximates (unset one of them)'
+            if why is not None:
+                raise ValueError('GRL_EVAL_NNG=%s %s' % (os.environ['GRL_EVAL_NNG'].strip(), why))
         if pq_knob is not None:
             why = None
             if rerank:
@@ -1017,6 +1099,8 @@ class ATTEvaluator(object):
                     lines = tuple(lines) + tuple(_ivf_report(ivf_knob, pq_knob, kept, qf, gf, ids, path))
                 if refine_knob is not None:
                     lines = tuple(lines) + tuple(_refine_report(refine_knob, kept, qf, gf, ids, path))
+            if nng_knob is not None:
+                lines = tuple(lines) + tuple(_nng_report(nng_knob, qf, gf, ids, path))
             return lines
         if set_knob is not None:
             reduce, metric = set_knob

@@ -1068,6 +1068,72 @@ int grl_refine_scan(const float* q, int64_t ldq, const void* store, int64_t lds,
                     void* stream);
 int grl_refine_pack_bf16(const float* x, uint16_t* out, int64_t count, void* stream);
 
+/* ---- kNN-graph gallery index with beam search (nng.hip, engine.nng_knn / nng_optimize / NnGraphIndex / nng_build /
+ * nng_search).  Additive: GRL_ABI_VERSION stays 10. ----
+ * All ids are row numbers of a feature store of n rows as above, n < 2^31.  "Live" means 0 <= id < n; anything else is
+ * padding, is never dereferenced and is skipped wherever it stands.  tests/nng_ref.py is this text in numpy.
+ *
+ * Graph optimisation (integers only, exact).  Input knn int32 [n][K]: row i lists the candidate neighbours of i, nearest
+ * first.  An entry equal to i, a non-live entry and every repeat of an id after its first position are padding.  With
+ * t_x = knn[i][x]:
+ *   Detours.  For a live position b, det[i][b] = #{a < b, a live : t_b in {knn[t_a][r] : r < b, r live in row t_a}} (the
+ *     rank-based 2-hop count of CAGRA); det of a padding position is -1.
+ *   Pruned forward lists.  F[i] = the ids at the first D of row i's live positions in the order (det, b), padded with -1.
+ *   Reverse lists.  rev[j] = every i with j in F[i], ordered by (position of j in F[i], i).
+ *   Merge.  N[i] = the first D ids, without repeats, of the sequence below, padded with -1:
+ *     1. F[i][0 : D/2];
+ *     2. the entries of rev[i], in order, that are not yet present, until D/2 of them have been taken;
+ *     3. F[i][D/2 : D], those not yet present;
+ *     4. the rest of rev[i], those not yet present.
+ *   Domain: 2 <= K <= GRL_NNG_K_MAX, D even, 2 <= D <= min(K, GRL_NNG_D_MAX).
+ * grl_nng_detours writes det [n][K] (one workgroup per node: row i and the rows it points to in LDS, at most 64 of them
+ * at a time).  grl_nng_merge: fwd = F int32 [n][D], rev in CSR form (rev_off int64 [n + 1], rev int32 in the order
+ * above), out = N int32 [n][D]; one lane per node.
+ *
+ * Beam search.  For each query q, with the neighbour table N int32 [n][D], S seeds, itopk size L, search width w and
+ * iteration cap T:
+ *     visited = {}; C = []                               # C: entries (dist, id, expanded)
+ *     for s in seeds (in any order): if s live and s not in visited: visited += s; C += (dist(q, s), s, False)
+ *     C = first L of C sorted by (order_key(dist), id)
+ *     for it in 0 .. T-1:
+ *         P = the first w entries of C, in C's order, with expanded == False;  if P is empty: stop
+ *         mark them expanded;  new = []
+ *         for p in P, e in 0 .. D-1:  v = N[p.id][e];  if v live and v not in visited: visited += v; new += (dist(q, v), v, False)
+ *         C = first L of (C u new) sorted by (order_key(dist), id)
+ *     result = C                                          # at most L entries, padded with +inf / -1
+ * dist is exactly the pair distance above, steps 1-5, for both metrics and both store types; order_key is
+ * grl_row_argsort's (canonical NaN after +inf, -0 == +0).  visited is an exact set: an id that ever entered it is never
+ * scored again, even after it fell out of C.  The ids of C are unique, so the order is total, and the result does not
+ * depend on the order in which `new` is produced nor on which of two lanes claims a shared neighbour.  No floating-point
+ * atomics (an integer atomicCAS claims an id in the visited table), plain vector stores: the same bits from run to run
+ * and for any split of the queries into calls.  stats int32 [nq][2], both exact: |visited|, and the number of iterations
+ * that expanded at least one parent.
+ * Domain: L a power of two in GRL_NNG_L_MIN..GRL_NNG_L_MAX, 1 <= w <= GRL_NNG_W_MAX, w * D <= GRL_NNG_WD_MAX, T >= 1,
+ * 1 <= S <= L, d as the store takes it.  seeds int32 [nq][seed_stride] (S used), or shared by all queries with
+ * seed_stride = 0.  out float [nq][L], oidx int32 [nq][L].  At most 65535 queries per call.
+ * One workgroup per query holds in LDS the query row (4 d bytes), the sort buffer (8 bytes times the power of two >=
+ * L + w * D), the visited table and the iteration's id list (4 max(S, w * D) bytes, plus 64).  The table never drops an id:
+ * it has a power of two >= max(64, 2 min(S + T * w * D, n)) slots of 4 bytes (a call cannot visit more than n rows).
+ * grl_nng_search_lds_bytes returns the total (-1 outside the domain); above GRL_NNG_LDS_MAX = 64 KiB, the most a launch
+ * takes without the kernel's max-dynamic-LDS attribute, grl_nng_search is GRL_EINVAL and its message names both numbers.
+ * The defaults L = 64, w = 1, T = 64, D = 32 at d = 6144 take 58688 bytes.
+ * GRL_EINVAL, before any launch: a null pointer, a size outside the domain, an unknown store type or metric, a stride
+ * that is too small or (ldq, lds) no multiple of 4, a seed_stride that is neither 0 nor >= S, a pointer that is not
+ * aligned (as grl_refine_scan; 4 bytes for the int32 arrays, 8 for rev_off), nq > 65535, the LDS limit. */
+#define GRL_NNG_K_MAX    128
+#define GRL_NNG_D_MAX    64
+#define GRL_NNG_L_MIN    8
+#define GRL_NNG_L_MAX    512
+#define GRL_NNG_W_MAX    8
+#define GRL_NNG_WD_MAX   256
+#define GRL_NNG_LDS_MAX  65536
+int64_t grl_nng_search_lds_bytes(int64_t n, int d, int D, int L, int w, int64_t T, int S);
+int grl_nng_search(const float* q, int64_t ldq, const void* store, int64_t lds, int store_type, const int32_t* nbr,
+                   const int32_t* seeds, int64_t seed_stride, float* out, int32_t* oidx, int32_t* stats, int nq, int64_t n,
+                   int d, int D, int L, int w, int T, int S, int metric, void* stream);
+int grl_nng_detours(const int32_t* knn, int32_t* det, int64_t n, int K, void* stream);
+int grl_nng_merge(const int32_t* fwd, const int64_t* rev_off, const int32_t* rev, int32_t* out, int64_t n, int D, void* stream);
+
 /* ---- ranking by the Siamese verification head (verify.hip, engine.verify_metric / verify_dist) ----
  * In eval mode classifierBN -> classifierlinear on (p - g)^2 is affine in (p - g)^2; the class-1 minus class-0 logit is
  * s(p, g) = sum_d w_d (p_d - g_d)^2 + c.  The ranking distance F = (1 - beta)(-q.g) + beta(-s), p / g = columns
