@@ -233,6 +233,11 @@ _SIGNATURES = {
                        C.c_int),
     'grl_nng_detours': ([_fp, _fp, _i64, C.c_int, _fp], C.c_int),
     'grl_nng_merge': ([_fp, _fp, _fp, _fp, _i64, C.c_int, _fp], C.c_int),
+    # binary hash codes: Hamming scan, bit packing, asymmetric tables (bin.hip)
+    'grl_bin_scan': ([_fp, _fp, _i64, _fp, _i64, C.c_int, _i64, C.c_int, _fp], C.c_int),
+    'grl_bin_pack': ([_fp, _i64, _fp, _fp, _i64, _fp, _i64, _i64, C.c_int, _fp], C.c_int),
+    'grl_bin_words': ([_fp, _fp, _i64, _i64, C.c_int, _fp], C.c_int),
+    'grl_bin_lut': ([_fp, _i64, _fp, C.c_int, C.c_int, _fp], C.c_int),
     'grl_verify_fold': ([_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
     'grl_verify_rows': ([_fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, _fp],
                         C.c_int),

@@ -4393,6 +4393,7 @@ def set_pair_roc(qset, gset, q_pids, g_pids, q_camids, g_camids, reduce='chamfer
 PQ_METRICS = {'cosine': 0, 'euclidean': 1}                            # GRL_PQ_COSINE / GRL_PQ_EUCLIDEAN of include/grl_hip.h
 PQ_M_MAX = 4096                                                       # GRL_PQ_M_MAX
 PQ_LUT_BYTES = int(os.environ.get('GRL_PQ_LUT_BYTES', str(1 << 30)))  # resident query tables: nq * M * ksub * 4 bytes
+PQ_NQ_MAX = 262140                                                    # queries per grl_pq_scan call (its grid: 4 * 65535)
 
 
 def _pq_int(v, lo, hi, what, name):
@@ -5404,3 +5405,357 @@ def nng_search(qf, index, k, L=64, w=1, T=64, seeds=None, exclude=None, return_s
         idx = torch.where(drop, torch.full_like(idx, -1), idx).gather(1, order)
     dist, idx = dist[:, :k].contiguous(), idx[:, :k].contiguous()
     return (dist, idx, stats) if return_stats else (dist, idx)
+
+
+# ----------------------------------------------------------------------------
+# binary hash codes (ITQ, LSH) and Hamming search on the device (bin.hip)
+# ----------------------------------------------------------------------------
+BIN_NBITS_MAX = 1024                                                  # GRL_BIN_NBITS_MAX of include/grl_hip.h
+BIN_SLAB = 1024                                                       # GRL_BIN_SLAB: gallery columns per workgroup of grl_bin_scan
+BIN_NQ_MAX = 524280                                                   # GRL_BIN_NQ_MAX: queries per grl_bin_scan call
+BIN_METHODS = ('itq', 'lsh')
+BIN_MODES = ('hamming', 'asymmetric')
+
+
+def _bin_nbits(nbits, what):
+    import numbers
+    if isinstance(nbits, bool) or not isinstance(nbits, numbers.Integral) or nbits % 32 or not 32 <= nbits <= BIN_NBITS_MAX:
+        raise ValueError('%s: nbits must be an integer multiple of 32 in 32..%d (got %r)' % (what, BIN_NBITS_MAX, nbits))
+    return int(nbits)
+
+
+def _bin_mode(mode, what):
+    if mode not in BIN_MODES:
+        raise ValueError("%s: mode must be 'hamming' or 'asymmetric' (got %r)" % (what, mode))
+
+
+def _bin_mean(xp, n):
+    """mu [1, dp] of the padded rows: ``pca``'s mean (cluster_centroids(xf, zeros, 1, 'mean')'s kernels)."""
+    labels = torch.zeros(n, dtype=torch.int32, device=xp.device)
+    counts = torch.full((1,), n, dtype=torch.int32, device=xp.device)
+    return _kmeans_update(xp, labels, counts, 1, 'mean')[0]
+
+
+def _bin_shift(mu, ppad):
+    """shift [nbits] = -(proj mu): one GEMM row and grl_pca_affine, as ``Pca.affine`` makes its own."""
+    rows = ppad.shape[0]
+    cm, one, shift = (_new((rows,), ppad) for _ in range(3))
+    _pca_shift(mu, ppad, rows, None, one, shift, cm)
+    return shift
+
+
+class BinaryCodebook(object):
+    """The hyperplanes of a binary hash: ``proj`` [nbits, d] float32 on the device, ``shift`` [nbits] or
+    None, nbits a multiple of 32 in 32..1024.  z = x proj^T + shift is one fp32 GEMM (exact fp32 whatever ``set_math``
+    says; d is padded with zero columns to a multiple of 32 as ``Pca.transform`` pads it) and bit b of a row is z[b] > 0
+    (NaN, -0 and +0 give 0).  ``metric`` is the distance a second stage refines by (``bin_refine_search``).  A caller may
+    wrap a projection of its own; ``bin_train`` fills ``method`` / ``n_iter`` / ``seed`` / ``objective`` (None otherwise).
+    ValueError names the argument that is wrong."""
+
+    def __init__(self, proj, shift=None, metric='cosine'):
+        what = 'BinaryCodebook'
+        _cluster_metric(metric, what)
+        _pca_matrix(proj, what, 'proj')
+        nbits, d = int(proj.shape[0]), int(proj.shape[1])
+        _bin_nbits(nbits, what)
+        if d < 1:
+            raise ValueError('%s: proj must be [nbits, d] with d >= 1 (got %s)' % (what, tuple(proj.shape)))
+        if shift is not None and not (torch.is_tensor(shift) and shift.is_cuda and shift.dtype == torch.float32
+                                      and tuple(shift.shape) == (nbits,)):
+            raise ValueError('%s: shift must be None or a float32 device tensor [nbits] = [%d] (got %s)'
+                             % (what, nbits, (tuple(shift.shape), shift.dtype, shift.device) if torch.is_tensor(shift)
+                                else type(shift).__name__))
+        self.nbits, self.d, self.metric = nbits, d, metric
+        self.proj, self._ppad = proj, _pad_features(proj)
+        self.shift = None if shift is None else shift.contiguous()
+        self.method = self.n_iter = self.seed = self.objective = None
+
+    def _check(self, xf, what, name):
+        _pca_matrix(xf, what, name)
+        if xf.shape[1] != self.d:
+            raise ValueError('%s: %s must be [rows, d] = [rows, %d] (got %s)' % (what, name, self.d, tuple(xf.shape)))
+        return xf
+
+    def _rows(self, xf, what, name):
+        return _pad_features(self._check(xf, what, name))
+
+    def _project(self, xp):
+        n = xp.shape[0]
+        z = _new((n, self.nbits), xp)
+        if n:
+            gemm(xp, self._ppad, z, n, self.nbits, xp.shape[1], shift=self.shift, math=MATH_F32)
+        return z
+
+    def project(self, xf):
+        """z [rows, nbits] float32: z[i, b] = (xf[i] . proj[b]) + shift[b], the fp32 GEMM's bits."""
+        return self._project(self._rows(xf, 'BinaryCodebook.project', 'xf'))
+
+    def _pack(self, z, scan=True):
+        """grl_bin_pack: (codes uint8 [n, nbits / 8], scan words int32 [nbits / 32, n]) of the projections ``z``; without
+        ``scan`` (query rows: the symmetric scan reads their public bytes) the words are None and are not written."""
+        n = z.shape[0]
+        codes = torch.empty((n, self.nbits // 8), dtype=torch.uint8, device=z.device)
+        words = torch.empty((self.nbits // 32, n), dtype=torch.int32, device=z.device) if scan else None
+        if n:
+            _call('grl_bin_pack', ptr(z), self.nbits, ptr(codes), ptr(words), n, None, 0, n, self.nbits)
+        return codes, words
+
+    def _encode(self, xf, what='BinaryCodebook.encode'):
+        return self._pack(self._project(self._rows(xf, what, 'xf')))
+
+    def encode(self, xf):
+        """uint8 [rows, nbits / 8], the public layout: bit j of byte m is ``project(xf)[:, 8 * m + j] > 0``, i.e.
+        numpy.packbits(z > 0, axis=1, bitorder='little')."""
+        return self._encode(xf)[0]
+
+    def lut(self, qf):
+        """The asymmetric tables [nq, nbits / 8, 256] float32 of the query projections z = project(qf): entry [q, m, c] is
+        the sequential fp32 sum from +0 over j = 0..7 of -z[q, 8m + j] where bit j of c is set, +z[q, 8m + j] elsewhere
+        (grl_bin_lut; tests/bin_ref.py gives the same bits)."""
+        z = self._project(self._rows(qf, 'BinaryCodebook.lut', 'qf'))
+        nq = z.shape[0]
+        lut = _new((nq, self.nbits // 8, 256), z)
+        if nq:
+            _call('grl_bin_lut', ptr(z), self.nbits, ptr(lut), nq, self.nbits)
+        return lut
+
+
+def bin_train(xf, nbits, method='itq', n_iter=50, seed=0):
+    """A ``BinaryCodebook`` of ``nbits`` hyperplanes trained on the rows of ``xf`` [n, d].  Both methods centre on the mean
+    of ``xf`` (``pca``'s mean, bit for bit): shift = -(proj mean), since post-ReLU features sit far from the origin.
+    'lsh': proj = Generator(PCG64(seed)).standard_normal((nbits, d)) as float32 from the host.  'itq' (iterative
+    quantisation): V = pca(xf, nbits, seed=seed).transform(xf); R_0 = the float64 QR of a host Gaussian [nbits, nbits] of
+    the same seed; ``n_iter`` rounds of Z = V R (the GEMM), B = sign(Z) as +-1 (grl_bin_pack), A = B^T V (the slab-reduced
+    weight-gradient GEMM), R = the orthogonal Procrustes solution from the float64 SVD of A on the host (one nbits x nbits
+    download and upload per round: training glue that does not grow with n); ``objective`` lists the sums of singular
+    values, one per round; finally proj = R^T C by the GEMM.  pca's limits and errors apply (nbits + 10 <= min(n - 1, d,
+    512)).  The same bits on every run.  Not sharded: every rank trains the full, identical codebook.  ValueError names
+    the argument: ``xf`` not a 2-d float32 device tensor, method, nbits, n_iter < 1, seed < 0."""
+    import numpy as np
+    what = 'bin_train'
+    _pca_matrix(xf, what, 'xf')
+    if method not in BIN_METHODS:
+        raise ValueError("%s: method must be 'itq' or 'lsh' (got %r)" % (what, method))
+    c = _bin_nbits(nbits, what)
+    n_iter = _kmeans_int(n_iter, 1, what, 'n_iter')
+    seed = _kmeans_int(seed, 0, what, 'seed')
+    n, d = int(xf.shape[0]), int(xf.shape[1])
+    dev = xf.device
+    if method == 'lsh':
+        if n < 1 or d < 1:
+            raise ValueError('%s: xf needs at least one row and one column (got %s)' % (what, tuple(xf.shape)))
+        xp = _pad_features(xf)
+        dp = xp.shape[1]
+        ppad = torch.zeros((c, dp), dtype=torch.float32, device=dev)
+        host = np.random.Generator(np.random.PCG64(seed)).standard_normal((c, d)).astype(np.float32)
+        ppad[:, :d] = torch.from_numpy(host).to(dev)
+        mu, objective = _bin_mean(xp, n), None
+    else:
+        p = pca(xf, c, seed=seed)
+        cpad, mu = p._cpad, p._mu
+        dp, npad = cpad.shape[1], _pad32(n)
+        # v and b are padded with zero rows to a multiple of 32, as _PcaFit pads the z it hands to _pca_wgrad; only the
+        # rows below n are ever rewritten, so the padding stays zero and adds +0 to B^T V
+        v = torch.zeros((npad, c), dtype=torch.float32, device=dev)
+        v[:n] = p.transform(xf)
+        b = torch.zeros((npad, c), dtype=torch.float32, device=dev)
+        z, a = _new((n, c), v), _new((c, c), v)
+        g = np.random.Generator(np.random.PCG64(seed)).standard_normal((c, c))
+        r = np.linalg.qr(g)[0]
+        objective = []
+        for _ in range(n_iter):
+            rt = torch.from_numpy(np.ascontiguousarray(r.T).astype(np.float32)).to(dev)
+            gemm(v, rt, z, n, c, c, math=MATH_F32)                              # Z = V R
+            _call('grl_bin_pack', ptr(z), c, None, None, 0, ptr(b), c, n, c)    # B = sign(Z)
+            _pca_wgrad(b, v, a, n, c, c, c)                                     # A = B^T V
+            u, s, vh = np.linalg.svd(a.cpu().numpy().astype(np.float64))
+            objective.append(float(s.sum()))
+            r = (u @ vh).T                                                      # argmax_R tr(A R) over the orthogonal R
+        rt = torch.from_numpy(np.ascontiguousarray(r.T).astype(np.float32)).to(dev)
+        ct = _new((dp, c), v)
+        _call('grl_transpose', ptr(cpad), ptr(ct), c, dp, dp)
+        ppad = _new((c, dp), v)
+        gemm(rt, ct, ppad, c, dp, c, math=MATH_F32)                             # proj = R^T C
+    shift = _bin_shift(mu, ppad)
+    book = BinaryCodebook(ppad[:, :d] if dp == d else ppad[:, :d].contiguous(), shift)
+    book.method, book.n_iter, book.seed, book.objective = method, n_iter, seed, objective
+    return book
+
+
+def _bin_codes(codes, nbits, what):
+    if not (torch.is_tensor(codes) and codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2
+            and codes.shape[1] == nbits // 8):
+        raise ValueError('%s: codes must be a uint8 device tensor [n, nbits / 8] = [n, %d] (got %s)'
+                         % (what, nbits // 8, (tuple(codes.shape), codes.dtype) if torch.is_tensor(codes) else type(codes).__name__))
+    return codes.contiguous()
+
+
+class BinaryIndex(object):
+    """A gallery as binary codes: ``codebook``, ``codes`` (uint8 [n, nbits / 8] on the device, the public layout), ``n``,
+    ``nbits`` and ``nbytes`` = everything the index keeps on the device: the codes, their scan-layout copy (uint32
+    [nbits / 32, n], what grl_bin_scan and grl_pq_scan read coalesced; grl_bin_words makes it from caller-supplied codes)
+    and the projection with its shift."""
+
+    def __init__(self, codebook, codes, _scan=None):
+        if not isinstance(codebook, BinaryCodebook):
+            raise ValueError('BinaryIndex: codebook must be a BinaryCodebook (got %s)' % type(codebook).__name__)
+        self.codebook, self.nbits = codebook, codebook.nbits
+        self.codes = _bin_codes(codes, codebook.nbits, 'BinaryIndex')
+        self.n = int(self.codes.shape[0])
+        if _scan is None:
+            _scan = torch.empty((self.nbits // 32, self.n), dtype=torch.int32, device=self.codes.device)
+            if self.n:
+                _call('grl_bin_words', ptr(self.codes), ptr(_scan), self.n, self.n, self.nbits)
+        self._scan = _scan
+        self.nbytes = self.codes.numel() + 4 * _scan.numel() + 4 * codebook.proj.numel() \
+            + (0 if codebook.shift is None else 4 * codebook.nbits)
+
+
+def bin_index(xf, codebook):
+    """``BinaryIndex(codebook, codebook.encode(xf))`` with the scan layout written by the same launch as the codes."""
+    if not isinstance(codebook, BinaryCodebook):
+        raise ValueError('bin_index: codebook must be a BinaryCodebook (got %s)' % type(codebook).__name__)
+    codes, scan = codebook._encode(xf, 'bin_index')
+    return BinaryIndex(codebook, codes, scan)
+
+
+def _bin_check(index, what):
+    if not isinstance(index, BinaryIndex):
+        raise ValueError('%s: index must be a BinaryIndex (got %s)' % (what, type(index).__name__))
+
+
+class _BinBlocks(object):
+    """Column blocks of the distance matrix of ``qf`` against the code rows of ``index``: ``_PqBlocks``' block-source
+    contract (``spans``, ``block(c0, c1)``, ``qf``, ``nq``, ``ng``; one reused buffer).  'hamming': the constructor encodes
+    the queries and a block is grl_bin_scan over the word rows [c0, c1) in place (the kernel takes the row stride);
+    'asymmetric': the constructor makes the tables of all its queries (``codebook.lut``) and a block is grl_pq_scan with
+    M = nbits / 8, ksub = 256 over a contiguous copy of the block's words.  An entry depends on its codes and its query
+    alone, so a block holds the full matrix's bits whatever its width."""
+
+    def __init__(self, qf, index, mode='hamming', block_cols=None, block_bytes=None):
+        _bin_check(index, '_BinBlocks')
+        _bin_mode(mode, '_BinBlocks')
+        book = index.codebook
+        xp = book._rows(qf, '_BinBlocks', 'qf')
+        self.qf, self.index, self.mode, self.nq, self.ng = xp, index, mode, xp.shape[0], index.n
+        nq, hi = self.nq, index.n
+        if block_cols is None:
+            budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
+            block_cols = max(256, budget // (4 * max(nq, 1)) // 256 * 256)
+        width = max(1, min(int(block_cols), hi))
+        self.width = width
+        self.spans = [(c, min(c + width, hi)) for c in range(0, hi, width)]
+        self.buf = _new((nq * width,), xp) if self.spans and nq else None
+        self.qwords = self.lut = self.z = None
+        if self.spans and nq:
+            self.z = book._project(xp)
+            if mode == 'hamming':
+                self.qwords = book._pack(self.z, scan=False)[0].view(torch.int32)         # [nq, nbits / 32]: the public bytes
+            else:
+                self.lut = _new((nq, book.nbits // 8, 256), xp)
+                _call('grl_bin_lut', ptr(self.z), book.nbits, ptr(self.lut), nq, book.nbits)
+
+    def block(self, c0, c1):
+        n, nbits, nq = c1 - c0, self.index.nbits, self.nq
+        out = self.buf[:nq * n].view(nq, n)
+        scan = self.index._scan
+        if self.mode == 'hamming':
+            for q0 in range(0, nq, BIN_NQ_MAX):
+                q1 = min(q0 + BIN_NQ_MAX, nq)
+                _call('grl_bin_scan', ptr(self.qwords[q0:q1]), ptr(scan[:, c0:]), self.ng, ptr(out[q0:q1]), n, q1 - q0, n, nbits)
+            return out
+        if n != self.ng:                                   # grl_pq_scan's row stride is its column count
+            scan = scan[:, c0:c1].contiguous()
+        _call('grl_pq_scan', ptr(self.lut), ptr(scan), ptr(out), nq, n, nbits // 8, 256, n, PQ_METRICS['cosine'], None)
+        return out
+
+
+def bin_dist(qf, index, mode='hamming', block_cols=None, block_bytes=None):
+    """The materialised [nq, n] float32 distances of ``qf`` against ``index``, for small cases and tests.  'hamming': the
+    number of differing bits between the query's code and the row's, an exact integer in 0..nbits.  'asymmetric':
+    -sum_b z_q[b] s_g[b] with z_q the query's projection and s_g = +-1 the row's bits, as the ADC sum of include/grl_hip.h
+    over ``codebook.lut(qf)`` (tests/pq_ref.adc_dist gives the same bits); smaller = nearer under both.  The same bits for
+    every ``block_cols``."""
+    _bin_check(index, 'bin_dist')
+    _bin_mode(mode, 'bin_dist')
+    blocks = _BinBlocks(qf, index, mode, index.n if block_cols is None and block_bytes is None else block_cols, block_bytes)
+    out = _new((blocks.nq, index.n), blocks.qf)
+    if blocks.nq:
+        for c0, c1 in blocks.spans:
+            out[:, c0:c1] = blocks.block(c0, c1)
+    return out
+
+
+def _bin_query_rows(book, mode):
+    """queries per block source: the grid's limit, and for 'asymmetric' the tables that fit GRL_PQ_LUT_BYTES (at least one)"""
+    if mode == 'hamming':
+        return BIN_NQ_MAX
+    return max(1, min(PQ_NQ_MAX, PQ_LUT_BYTES // (4 * (book.nbits // 8) * 256)))
+
+
+def bin_search(qf, index, k, mode='hamming', exclude=None, block_cols=None, block_bytes=None):
+    """``search`` on D = bin_dist(qf, index, mode): ``(dist [nq, k] float32, idx [nq, k] int64)``, bit for bit
+    ``rank_rows(D)[:, :k]`` and D at those indices, without D: blocks of code rows through grl_bin_scan ('hamming') or
+    grl_pq_scan over the asymmetric tables, ranked by search's running top-k.  Hamming distances are small integers, so
+    ties are the rule: they go to the smaller gallery index.  ``exclude`` is search's junk rule; padding is index -1,
+    distance +inf; k <= 1024.  The asymmetric tables obey GRL_PQ_LUT_BYTES as ``pq_search``'s do: beyond it the queries
+    are served in row blocks, whose results are independent and concatenated.  Not sharded."""
+    _bin_check(index, 'bin_search')
+    _bin_mode(mode, 'bin_search')
+    if isinstance(k, bool) or not 1 <= int(k) <= SEARCH_K_MAX:
+        raise ValueError('bin_search: k must be in 1..%d (got %r)' % (SEARCH_K_MAX, k))
+    k, book = int(k), index.codebook
+    qf = book._check(qf, 'bin_search', 'qf')
+    nq = qf.shape[0]
+    junk = _junk_ids(exclude, nq, index.n, qf.device)
+    rows = _bin_query_rows(book, mode)
+    dist, idx = [], []
+    for q0 in range(0, max(nq, 1), rows):
+        q1 = min(q0 + rows, nq)
+        blocks = _BinBlocks(qf[q0:q1], index, mode, block_cols, block_bytes)
+        j = None if junk is None else (junk[0][q0:q1], junk[1][q0:q1], junk[2], junk[3])
+        dv, di = _search_blocks(blocks, q1 - q0, k, False, j)
+        dist.append(dv)
+        idx.append(di)
+    return (dist[0], idx[0]) if len(dist) == 1 else (torch.cat(dist), torch.cat(idx))
+
+
+def bin_metrics_streaming(qf, index, q_pids, g_pids, q_camids, g_camids, mode='hamming', max_rank=100, block_cols=None,
+                          block_bytes=None):
+    """``rank_metrics(rank_rows(D), ...)`` for D = bin_dist(qf, index, mode) without D: (cmc[max_rank] float32, mAP float)
+    with rank_metrics_streaming's contract.  'asymmetric': the tables of ALL queries must fit GRL_PQ_LUT_BYTES, as in
+    ``pq_metrics_streaming`` (ValueError naming the bytes), and there are at most 262 140 of them (grl_pq_scan's grid).
+    Not sharded."""
+    _bin_check(index, 'bin_metrics_streaming')
+    _bin_mode(mode, 'bin_metrics_streaming')
+    book = index.codebook
+    qf = book._check(qf, 'bin_metrics_streaming', 'qf')
+    if mode == 'asymmetric':
+        need = 4 * qf.shape[0] * (book.nbits // 8) * 256
+        if qf.shape[0] > PQ_NQ_MAX:
+            raise ValueError('bin_metrics_streaming: at most %d queries per call in mode \'asymmetric\' (grl_pq_scan\'s grid; got '
+                             '%d): evaluate the queries in parts or use mode \'hamming\'' % (PQ_NQ_MAX, qf.shape[0]))
+        if need > PQ_LUT_BYTES:
+            raise ValueError('bin_metrics_streaming: the query tables take %d bytes (nq * nbits / 8 * 256 * 4 = %d * %d * 256 '
+                             '* 4), above GRL_PQ_LUT_BYTES = %d' % (need, qf.shape[0], book.nbits // 8, PQ_LUT_BYTES))
+    blocks = _BinBlocks(qf, index, mode, block_cols, block_bytes)
+    first, nhit, ap = _rank_blocks(blocks, blocks.nq, index.n, q_pids, g_pids, q_camids, g_camids, False)
+    return _cmc_map(first, nhit, ap, index.n, max_rank)
+
+
+def bin_refine_search(qf, index, store, k, R, mode='hamming', exclude=None, block_bytes=None):
+    """Two-stage search over a ``BinaryIndex``: exactly ``refine_lists(qf, store, bin_search(qf, index, R, mode,
+    exclude=exclude)[1], k, index.codebook.metric, block_bytes)``.  The junk rule is applied in the first stage and nowhere
+    else.  k <= R <= 1024; store.n and store.d must be the index's.  ValueError names the argument that is wrong."""
+    _bin_check(index, 'bin_refine_search')
+    _bin_mode(mode, 'bin_refine_search')
+    if not isinstance(store, RefineStore):
+        raise ValueError('bin_refine_search: store must be a RefineStore (got %s)' % type(store).__name__)
+    d = index.codebook.d
+    if store.n != index.n or store.d != d:
+        raise ValueError('bin_refine_search: store must hold the rows of the index: store is [%d, %d], the index [%d, %d]'
+                         % (store.n, store.d, index.n, d))
+    k = _pq_int(k, 1, SEARCH_K_MAX, 'bin_refine_search', 'k')
+    R = _pq_int(R, k, SEARCH_K_MAX, 'bin_refine_search', 'R (k <= R <= %d)' % SEARCH_K_MAX)
+    cand = bin_search(qf, index, R, mode, exclude=exclude, block_bytes=block_bytes)[1]
+    return refine_lists(qf, store, cand, k, index.codebook.metric, block_bytes)

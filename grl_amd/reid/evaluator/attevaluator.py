@@ -755,6 +755,71 @@ def _nng_report(knob, qf, gf, ids, path):
     return lines
 
 
+def parse_bin_knob(name, value):
+    """``GRL_EVAL_BIN``: unset or empty -> None (off); "nbits", "nbits,method", "nbits,method,n_iter" or
+    "nbits,method,n_iter,seed" -> (nbits, method, n_iter, seed) with nbits a multiple of 32 in 32..1024 (the bits of a code
+    row), method 'itq' or 'lsh' (default 'itq'), n_iter >= 1 (the ITQ rounds, default 50) and seed >= 0 (default 0) of
+    engine.bin_train.  Anything else is a ValueError that names the variable."""
+    if value is None or not value.strip():
+        return None
+    parts = [p.strip() for p in value.split(',')]
+    try:
+        if len(parts) > 4:
+            raise ValueError
+        nbits = int(parts[0])
+        method = parts[1] if len(parts) >= 2 else 'itq'
+        n_iter = int(parts[2]) if len(parts) >= 3 else 50
+        seed = int(parts[3]) if len(parts) == 4 else 0
+        if method not in engine.BIN_METHODS:
+            raise ValueError
+    except ValueError:
+        raise ValueError('%s must be "nbits", "nbits,itq", "nbits,lsh", "nbits,method,n_iter" or "nbits,method,n_iter,seed" '
+                         'with integers (got %r)' % (name, value))
+    if nbits % 32 or not 32 <= nbits <= engine.BIN_NBITS_MAX or not 1 <= n_iter <= 2 ** 31 - 1 \
+            or not 0 <= seed <= 2 ** 31 - 1:
+        raise ValueError('%s: nbits must be a multiple of 32 in 32..%d, n_iter >= 1 and seed >= 0 (got %r)'
+                         % (name, engine.BIN_NBITS_MAX, value))
+    return nbits, method, n_iter, seed
+
+
+def _bin_report(knob, qf, gf, ids, path):
+    """GRL_EVAL_BIN: a binary-code index of the query-prepended gallery ``gf`` (engine.bin_train + engine.bin_index) -- the
+    lines printed last: CMC / mAP by the Hamming and by the asymmetric distance next to the exact ones, recall@1 / 10 / 100
+    of engine.bin_search in both modes against engine.search under the same junk rule, the index bytes against the feature
+    bytes -- and ``path + 'bin.json'`` (rank 0 alone writes; strict JSON).  A report only: the route's ranking is not
+    touched."""
+    import json
+    nbits, method, n_iter, seed = knob
+    q_pids, g_pids, q_camids, g_camids = ids
+    book = engine.bin_train(gf, nbits, method, n_iter, seed)
+    index = engine.bin_index(gf, book)
+    cmc_x, mAP_x = engine.rank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids)
+    k = min(100, engine.SEARCH_K_MAX, int(gf.size(0)))
+    exact = engine.search(qf, gf, k, exclude=ids)[1]
+    ks = (1, 10, 100)
+    feature_bytes = 4 * int(gf.size(0)) * int(gf.size(1))
+    ranks = [r for r in (1, 5, 10, 20) if r <= len(cmc_x)]
+    lines = ['BIN: {} bits by {} ({} bytes per row of {}), {} rows'.format(nbits, method, nbits // 8, 4 * int(gf.size(1)),
+                                                                          index.n)]
+    fin = lambda r: r if math.isfinite(r) else None
+    js = {'nbits': nbits, 'method': method, 'n_iter': n_iter, 'seed': seed, 'n': index.n, 'n_queries': int(qf.size(0)), 'k': k,
+          'objective': book.objective, 'exact': {'mAP': float(mAP_x), 'cmc': [float(v) for v in cmc_x]},
+          'index_bytes': int(index.nbytes), 'code_bytes': int(index.codes.numel()), 'feature_bytes': feature_bytes}
+    for mode, tag in (('hamming', 'Hamming'), ('asymmetric', 'Asymmetric')):
+        cmc, mAP = engine.bin_metrics_streaming(qf, index, q_pids, g_pids, q_camids, g_camids, mode=mode)
+        recall = engine.topk_recall(engine.bin_search(qf, index, k, mode, exclude=ids)[1], exact, ks)
+        lines += ['{} Mean AP: {:4.1%} (exact {:4.1%})'.format(tag, mAP, mAP_x)]
+        lines += ['{} Rank-{:<3}: {:.1%} (exact {:.1%})'.format(tag, r, cmc[r - 1], cmc_x[r - 1]) for r in ranks]
+        lines += ['{} recall@1: {:.2%}  @10: {:.2%}  @100: {:.2%}'.format(tag, *recall)]
+        js[mode] = {'mAP': float(mAP), 'cmc': [float(v) for v in cmc], 'recall': {str(kk): fin(r) for kk, r in zip(ks, recall)}}
+    lines += ['BIN index: {} bytes against {} bytes of features ({:.1f}x smaller)'.format(
+        index.nbytes, feature_bytes, feature_bytes / float(index.nbytes))]
+    if grl_dist._rank_world(None, None)[0] == 0:
+        with open((path or '') + 'bin.json', 'w') as fh:
+            json.dump(js, fh, allow_nan=False)
+    return lines
+
+
 class ATTEvaluator(object):
     def __init__(self, cnn_model, Siamese_model, only_eval):
         self.cnn_model = cnn_model
@@ -1008,6 +1073,24 @@ class ATTEvaluator(object):
                       'walk approximates (unset one of them)'
             if why is not None:
                 raise ValueError('GRL_EVAL_NNG=%s %s' % (os.environ['GRL_EVAL_NNG'].strip(), why))
+        # binary hash codes of the gallery and Hamming search, off by default (engine.bin_train / bin_search): a report
+        bin_knob = parse_bin_knob('GRL_EVAL_BIN', os.environ.get('GRL_EVAL_BIN'))
+        if bin_knob is not None:
+            why = None
+            if rerank:
+                why = 'cannot re-rank: the codes approximate the cosine distance of a query to a gallery row, and ' \
+                      'k-reciprocal re-ranking ranks by a Jaccard blend of whole neighbourhoods (evaluate with rerank=0)'
+            elif knob is not None:
+                why = 'cannot be combined with GRL_EVAL_METRIC=%s: the verification head\'s distance is not a count of ' \
+                      'hyperplanes between the rows (unset one of them)' % os.environ['GRL_EVAL_METRIC'].strip()
+            elif set_knob is not None:
+                why = 'cannot be combined with GRL_EVAL_SET: the set distances are taken between clip rows, and the ' \
+                      'index holds one code row per tracklet (unset one of them)'
+            elif diffusion_knob is not None:
+                why = 'cannot be combined with GRL_EVAL_DIFFUSION: the diffusion scores replace the cosine ranking the ' \
+                      'index approximates (unset one of them)'
+            if why is not None:
+                raise ValueError('GRL_EVAL_BIN=%s %s' % (os.environ['GRL_EVAL_BIN'].strip(), why))
         if pq_knob is not None:
             why = None
             if rerank:
@@ -1101,6 +1184,8 @@ class ATTEvaluator(object):
                     lines = tuple(lines) + tuple(_refine_report(refine_knob, kept, qf, gf, ids, path))
             if nng_knob is not None:
                 lines = tuple(lines) + tuple(_nng_report(nng_knob, qf, gf, ids, path))
+            if bin_knob is not None:
+                lines = tuple(lines) + tuple(_bin_report(bin_knob, qf, gf, ids, path))
             return lines
         if set_knob is not None:
             reduce, metric = set_knob

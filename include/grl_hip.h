@@ -1134,6 +1134,36 @@ int grl_nng_search(const float* q, int64_t ldq, const void* store, int64_t lds, 
 int grl_nng_detours(const int32_t* knn, int32_t* det, int64_t n, int K, void* stream);
 int grl_nng_merge(const int32_t* fwd, const int64_t* rev_off, const int32_t* rev, int32_t* out, int64_t n, int D, void* stream);
 
+/* ---- binary hash codes: bit packing, Hamming scan, asymmetric tables (bin.hip, engine.bin_* / BinaryCodebook /
+ * BinaryIndex).  Additive: GRL_ABI_VERSION stays 10. ----
+ * A gallery row is nbits bits, nbits a multiple of 32 in 32..GRL_BIN_NBITS_MAX, W = nbits / 32 words.  The projection,
+ * normative: z[i][b] = (x_i . proj[b]) + shift[b], the fp32 GEMM (grl_conv_gemm_f32, GRL_MATH_F32 whatever the math mode is).
+ * Bit b of row i is z[i][b] > 0: NaN, -0 and +0 give 0.  PUBLIC LAYOUT: codes uint8 [n][nbits / 8], bit j of byte m =
+ * projection column 8m + j (numpy.packbits(bits, axis=1, bitorder='little')).  SCAN LAYOUT: uint32 [W][ldw], ldw >= n, word
+ * [w][g] = the bytes 4w .. 4w + 3 of public row g, little endian (bit t of the word = column 32w + t) -- exactly grl_pq_pack's
+ * scan layout for M = nbits / 8, ksub = 256 when ldw = n, so one copy serves grl_bin_scan and grl_pq_scan.  Query codes of the
+ * symmetric scan: uint32 [nq][W], the public bytes of the query rows reinterpreted.
+ * grl_bin_scan: out[q][g] = (float) sum_w popcount(qwords[q][w] ^ words[w][g]) for q < nq, g < n (row stride ldo >= n; only
+ * the first n columns of a row are written): the Hamming distance, an exact integer in 0..nbits.  Integer accumulators, no
+ * atomics, one conversion at the store; a workgroup scores 8 queries against a slab of GRL_BIN_SLAB columns.
+ * grl_bin_pack: z [n][ldz] -> codes (public layout), words (scan layout) and signs float [n][lds] (+1.0f where the bit
+ * is set, -1.0f elsewhere), in one launch; each of the three may be NULL (not all).  grl_bin_words: codes -> words.
+ * grl_bin_lut: the asymmetric tables lut [nq][nbits / 8][256] of the query projections z [nq][ldz]: entry [q][m][c] is the
+ * sequential fp32 sum from +0.0f over j = 0 .. 7 of t_j, t_j = -z[q][8m + j] when bit j of c is set, else +z[q][8m + j]
+ * (adds and exact negations only).  The asymmetric distance of a pair is grl_pq_scan over these tables and the scan words
+ * (M = nbits / 8, ksub = 256, GRL_PQ_COSINE, ldw = n): -sum_b z_q[b] s_g[b], s = +-1, in the ADC sum's normative order.
+ * GRL_EINVAL, before any launch: a null pointer, a negative size, nbits not a multiple of 32 or outside the range, ldz or
+ * lds < nbits, ldw or ldo < n, a pointer that is not 4-byte aligned, nq > GRL_BIN_NQ_MAX (the grid's limit: 8 * 65535). */
+#define GRL_BIN_NBITS_MAX  1024
+#define GRL_BIN_SLAB       1024
+#define GRL_BIN_NQ_MAX     524280
+int grl_bin_scan(const uint32_t* qwords, const uint32_t* words, int64_t ldw, float* out, int64_t ldo, int nq, int64_t n,
+                 int nbits, void* stream);
+int grl_bin_pack(const float* z, int64_t ldz, uint8_t* codes, uint32_t* words, int64_t ldw, float* signs, int64_t lds,
+                 int64_t n, int nbits, void* stream);
+int grl_bin_words(const uint8_t* codes, uint32_t* words, int64_t ldw, int64_t n, int nbits, void* stream);
+int grl_bin_lut(const float* z, int64_t ldz, float* lut, int nq, int nbits, void* stream);
+
 /* ---- ranking by the Siamese verification head (verify.hip, engine.verify_metric / verify_dist) ----
  * In eval mode classifierBN -> classifierlinear on (p - g)^2 is affine in (p - g)^2; the class-1 minus class-0 logit is
  * s(p, g) = sum_d w_d (p_d - g_d)^2 + c.  The ranking distance F = (1 - beta)(-q.g) + beta(-s), p / g = columns
