@@ -238,6 +238,14 @@ _SIGNATURES = {
     'grl_bin_pack': ([_fp, _i64, _fp, _fp, _i64, _fp, _i64, _i64, C.c_int, _fp], C.c_int),
     'grl_bin_words': ([_fp, _fp, _i64, _i64, C.c_int, _fp], C.c_int),
     'grl_bin_lut': ([_fp, _i64, _fp, C.c_int, C.c_int, _fp], C.c_int),
+    # int8 scalar-quantised gallery: quantiser, decode, integer-MFMA scan (sq8.hip)
+    'grl_sq8_absmax': ([_fp, _i64, _fp, _fp, _i64, C.c_int, _fp], C.c_int),
+    'grl_sq8_steps': ([_fp, _fp, _fp, C.c_int, _fp], C.c_int),
+    'grl_sq8_encode': ([_fp, _i64, _fp, _fp, _fp, _i64, _i64, C.c_int, _fp], C.c_int),
+    'grl_sq8_decode': ([_fp, _i64, _fp, _fp, _fp, _i64, _i64, C.c_int, _fp], C.c_int),
+    'grl_sq8_query': ([_fp, _i64, _fp, _fp, _i64, _fp, C.c_int, C.c_int, _fp], C.c_int),
+    'grl_sq8_scan': ([_fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, _i64, C.c_int, C.c_int, _fp], C.c_int),
+    'grl_sq8_scan_i32': ([_fp, _i64, _fp, _i64, _fp, _i64, C.c_int, _i64, C.c_int, _fp], C.c_int),
     'grl_verify_fold': ([_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp], C.c_int),
     'grl_verify_rows': ([_fp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _i64, C.c_int, _fp],
                         C.c_int),

@@ -5759,3 +5759,273 @@ def bin_refine_search(qf, index, store, k, R, mode='hamming', exclude=None, bloc
     R = _pq_int(R, k, SEARCH_K_MAX, 'bin_refine_search', 'R (k <= R <= %d)' % SEARCH_K_MAX)
     cand = bin_search(qf, index, R, mode, exclude=exclude, block_bytes=block_bytes)[1]
     return refine_lists(qf, store, cand, k, index.codebook.metric, block_bytes)
+
+
+# ----------------------------------------------------------------------------
+# int8 scalar-quantised gallery searched on the integer MFMA (sq8.hip)
+# ----------------------------------------------------------------------------
+SQ8_D_MAX = 16384                                                     # GRL_SQ8_D_MAX of include/grl_hip.h
+SQ8_TILE = 128                                                        # GRL_SQ8_TILE: the output tile of grl_sq8_scan, both ways
+SQ8_NQ_MAX = 1048576                                                  # GRL_SQ8_NQ_MAX: queries per grl_sq8_scan / grl_sq8_query call
+
+
+def _sq8_dpad(d):
+    return -(-d // 64) * 64
+
+
+def _sq8_vector(t, d, what, name):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 1 and (d is None or t.shape[0] == d)):
+        raise ValueError('%s: %s must be a float32 device tensor [d]%s (got %s)'
+                         % (what, name, '' if d is None else ' = [%d]' % d,
+                            (tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else type(t).__name__))
+    return t.contiguous()
+
+
+class Sq8Codebook(object):
+    """The per-column scalar quantiser of include/grl_hip.h: ``mean`` [d] and ``delta`` [d] >= 0, float32
+    on the device, d <= 16384; ``inv`` [d] is kept next to them (127 / (127 delta), 0 where delta is 0; ``sq8_train`` stores
+    127 / amax).  A row's code is clamp(rint((x - mean) * inv), -127, 127) per column as int8 (NaN gives 0), stored
+    [rows, dpad] with dpad = d rounded up to a multiple of 64 and zero columns beyond d; its value is mean + delta * code.
+    ``metric`` ('cosine' | 'euclidean') is the distance of the scan and of a second stage.  ValueError names the argument
+    that is wrong."""
+
+    def __init__(self, mean, delta, metric='cosine', _inv=None):
+        what = 'Sq8Codebook'
+        _cluster_metric(metric, what)
+        self.mean = _sq8_vector(mean, None, what, 'mean')
+        d = int(self.mean.shape[0])
+        if not 1 <= d <= SQ8_D_MAX:
+            raise ValueError('%s: mean must be [d] with d in 1..%d (got %s)' % (what, SQ8_D_MAX, tuple(mean.shape)))
+        self.delta = _sq8_vector(delta, d, what, 'delta')
+        if not bool((self.delta >= 0).all()):
+            raise ValueError('%s: delta must be >= 0 in every column (and not NaN)' % what)
+        self.d, self.dpad, self.metric = d, _sq8_dpad(d), metric
+        if _inv is None:
+            _inv = _new((d,), self.mean)
+            _call('grl_sq8_steps', None, ptr(self.delta), ptr(_inv), d)
+        self.inv = _inv
+        self._mupad = _pad_features(self.mean.view(1, d))            # [1, dp]: the bias GEMM's row
+
+    def _check(self, xf, what, name):
+        _pca_matrix(xf, what, name)
+        if xf.shape[1] != self.d:
+            raise ValueError('%s: %s must be [rows, d] = [rows, %d] (got %s)' % (what, name, self.d, tuple(xf.shape)))
+        return xf
+
+    def _codes(self, codes, what):
+        """caller-supplied codes as the stored layout int8 [rows, dpad]: [rows, dpad] is taken as it is (its columns >= d
+        must be 0), [rows, d] is copied into zero-padded rows"""
+        if not (torch.is_tensor(codes) and codes.is_cuda and codes.dtype == torch.int8 and codes.dim() == 2
+                and codes.shape[1] in (self.d, self.dpad)):
+            raise ValueError('%s: codes must be an int8 device tensor [rows, dpad] = [rows, %d] or [rows, d] = [rows, %d] (got %s)'
+                             % (what, self.dpad, self.d,
+                                (tuple(codes.shape), codes.dtype) if torch.is_tensor(codes) else type(codes).__name__))
+        if codes.shape[1] == self.dpad:
+            codes = codes.contiguous()
+            if self.dpad > self.d and bool(codes[:, self.d:].any()):
+                raise ValueError('%s: the columns d .. dpad = %d .. %d of codes must be 0' % (what, self.d, self.dpad))
+            return codes
+        out = torch.zeros((codes.shape[0], self.dpad), dtype=torch.int8, device=codes.device)
+        out[:, :self.d] = codes
+        return out
+
+    def encode(self, xf):
+        """int8 [rows, dpad], the stored layout (``[:, :d]`` is the public view): the row codes of ``xf`` [rows, d]."""
+        xf = self._check(xf, 'Sq8Codebook.encode', 'xf').contiguous()
+        n = xf.shape[0]
+        codes = torch.empty((n, self.dpad), dtype=torch.int8, device=xf.device)
+        if n:
+            _call('grl_sq8_encode', ptr(xf), self.d, ptr(self.mean), ptr(self.inv), ptr(codes), self.dpad, n, self.d)
+        return codes
+
+    def _decode(self, codes, out, ldo):
+        if codes.shape[0]:
+            _call('grl_sq8_decode', ptr(codes), self.dpad, ptr(self.mean), ptr(self.delta), ptr(out), ldo, codes.shape[0], self.d)
+        return out
+
+    def decode(self, codes):
+        """float32 [rows, d]: mean + delta * code per column (one multiply, one add), the value of a stored row."""
+        codes = self._codes(codes, 'Sq8Codebook.decode')
+        return self._decode(codes, _new((codes.shape[0], self.d), self.mean), self.d)
+
+    def _query(self, qp, d):
+        """(qcodes, scale, bias, qq) of query rows padded to a multiple of 32 columns (``_pad_features``)"""
+        nq, dp = qp.shape
+        dev = qp.device
+        qcodes = torch.empty((nq, self.dpad), dtype=torch.int8, device=dev)
+        scale, bias, qq = _new((nq,), qp), _new((nq,), qp), _new((nq,), qp)
+        for q0 in range(0, nq, SQ8_NQ_MAX):
+            q1 = min(q0 + SQ8_NQ_MAX, nq)
+            _call('grl_sq8_query', ptr(qp[q0:q1]), dp, ptr(self.delta), ptr(qcodes[q0:q1]), self.dpad, ptr(scale[q0:q1]),
+                  q1 - q0, d)
+        if nq:
+            gemm(self._mupad, qp, bias, 1, nq, dp, math=MATH_F32)             # bias[q] = q . mean: one GEMM row
+            _call('grl_row_sqnorm', ptr(qp), ptr(qq), nq, dp, dp)
+        return qcodes, scale, bias, qq
+
+    def query(self, qf):
+        """``(qcodes int8 [nq, dpad], scale [nq], bias [nq], qq [nq])`` of the queries ``qf`` [nq, d]: w = q * delta per
+        column, s = the largest finite |w|, qcodes = clamp(rint(w * (127 / s)), -127, 127) (0 for a NaN or infinite w,
+        and everywhere when s is 0), scale = s / 127; bias = q . mean by the exact-fp32 GEMM; qq = grl_row_sqnorm(q).
+        The dot product of a query with a stored row is then scale * (qcodes . codes) + bias."""
+        return self._query(_pad_features(self._check(qf, 'Sq8Codebook.query', 'qf')), self.d)
+
+
+def sq8_train(xf, metric='cosine'):
+    """The ``Sq8Codebook`` of the rows of ``xf`` [n, d]: ``mean`` = the column mean (``pca``'s and ``bin_train``'s, bit
+    for bit), amax[j] = max_i |x[i][j] - mean[j]| (NaN ignored; an integer atomic maximum on the bits: no order),
+    delta = amax / 127 and inv = 127 / amax (0 for a constant column).  The same bits on every run.  Not sharded: every
+    rank trains the full, identical codebook."""
+    what = 'sq8_train'
+    _pca_matrix(xf, what, 'xf')
+    _cluster_metric(metric, what)
+    n, d = int(xf.shape[0]), int(xf.shape[1])
+    if n < 1 or not 1 <= d <= SQ8_D_MAX:
+        raise ValueError('%s: xf needs at least one row and 1..%d columns (got %s)' % (what, SQ8_D_MAX, tuple(xf.shape)))
+    xp = _pad_features(xf)
+    mean = _bin_mean(xp, n)[0, :d].contiguous()
+    amax, delta, inv = (_new((d,), xp) for _ in range(3))
+    _call('grl_sq8_absmax', ptr(xp), xp.shape[1], ptr(mean), ptr(amax), n, d)
+    _call('grl_sq8_steps', ptr(amax), ptr(delta), ptr(inv), d)
+    return Sq8Codebook(mean, delta, metric, _inv=inv)
+
+
+class Sq8Index(object):
+    """A gallery as int8 codes: ``codebook``, ``codes`` (int8 [n, dpad] on the device, zero beyond column d; ``codes[:, :d]``
+    is the public view; caller-supplied codes may be [n, d] and may hold -128), ``gg`` [n] = grl_row_sqnorm of the decoded
+    rows (the Euclidean epilogue's term), ``n``, ``d`` and ``nbytes`` = everything the index keeps on the device: codes, gg
+    and the codebook's three vectors."""
+
+    def __init__(self, codebook, codes):
+        if not isinstance(codebook, Sq8Codebook):
+            raise ValueError('Sq8Index: codebook must be a Sq8Codebook (got %s)' % type(codebook).__name__)
+        self.codebook, self.d = codebook, codebook.d
+        self.codes = codebook._codes(codes, 'Sq8Index')
+        self.n = n = int(self.codes.shape[0])
+        self.gg = _new((n,), self.codes)
+        d4 = -(-self.d // 4) * 4                                      # rows grl_row_sqnorm can read; the padding stays zero
+        rows = max(1, min(n, (64 << 20) // (4 * d4)))
+        buf = torch.zeros((rows, d4), dtype=torch.float32, device=self.codes.device) if n else None
+        for r0 in range(0, n, rows):
+            r1 = min(r0 + rows, n)
+            codebook._decode(self.codes[r0:r1], buf, d4)
+            _call('grl_row_sqnorm', ptr(buf), ptr(self.gg[r0:]), r1 - r0, d4, d4)
+        self.nbytes = self.codes.numel() + 4 * n + 12 * self.d
+
+    def reconstruct(self, rows):
+        """float32 [len(rows), d]: the stored values of the gallery rows ``rows`` (a 1-d integer device tensor)."""
+        if not (torch.is_tensor(rows) and rows.is_cuda and rows.dim() == 1 and not rows.dtype.is_floating_point
+                and not rows.dtype.is_complex and rows.dtype != torch.bool):
+            raise ValueError('Sq8Index.reconstruct: rows must be a 1-d integer device tensor of gallery indices')
+        rows = rows.to(torch.int64)
+        if rows.numel() and bool(((rows < 0) | (rows >= self.n)).any()):
+            raise ValueError('Sq8Index.reconstruct: rows must be in 0..n-1 = 0..%d' % (self.n - 1))
+        codes = self.codes[rows].contiguous()
+        return self.codebook._decode(codes, _new((codes.shape[0], self.d), self.gg), self.d)
+
+
+def sq8_index(xf, codebook):
+    """``Sq8Index(codebook, codebook.encode(xf))``."""
+    if not isinstance(codebook, Sq8Codebook):
+        raise ValueError('sq8_index: codebook must be a Sq8Codebook (got %s)' % type(codebook).__name__)
+    xf = codebook._check(xf, 'sq8_index', 'xf')
+    if xf.shape[0] >= 2 ** 31:
+        raise ValueError('sq8_index: n must be below 2**31 (got %d)' % xf.shape[0])
+    return Sq8Index(codebook, codebook.encode(xf))
+
+
+def _sq8_check(index, what):
+    if not isinstance(index, Sq8Index):
+        raise ValueError('%s: index must be a Sq8Index (got %s)' % (what, type(index).__name__))
+
+
+class _Sq8Blocks(object):
+    """Column blocks of the distance matrix of ``qf`` against the code rows of ``index``: ``_PqBlocks``' block-source
+    contract (``spans``, ``block(c0, c1)``, ``qf``, ``nq``, ``ng``; one reused buffer).  The constructor quantises the
+    queries (``codebook.query``); a block is grl_sq8_scan over the code rows [c0, c1) in place (a pointer offset: the
+    kernel takes the row stride).  An entry depends on its two code rows and its query's scale, bias and norm alone, and
+    the integer sum has no order, so a block holds the full matrix's bits whatever its width."""
+
+    def __init__(self, qf, index, block_cols=None, block_bytes=None):
+        _sq8_check(index, '_Sq8Blocks')
+        book = index.codebook
+        xp = _pad_features(book._check(qf, '_Sq8Blocks', 'qf'))
+        self.qf, self.index, self.nq, self.ng = xp, index, xp.shape[0], index.n
+        nq, hi = self.nq, index.n
+        if block_cols is None:
+            budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
+            block_cols = max(256, budget // (4 * max(nq, 1)) // 256 * 256)
+        width = max(1, min(int(block_cols), hi))
+        self.width = width
+        self.spans = [(c, min(c + width, hi)) for c in range(0, hi, width)]
+        self.buf = _new((nq * width,), xp) if self.spans and nq else None
+        self.qcodes = self.scale = self.bias = self.qq = None
+        if self.spans and nq:
+            self.qcodes, self.scale, self.bias, self.qq = book._query(xp, book.d)
+
+    def block(self, c0, c1):
+        n, nq, book = c1 - c0, self.nq, self.index.codebook
+        out = self.buf[:nq * n].view(nq, n)
+        for q0 in range(0, nq, SQ8_NQ_MAX):
+            q1 = min(q0 + SQ8_NQ_MAX, nq)
+            _call('grl_sq8_scan', ptr(self.qcodes[q0:q1]), book.dpad, ptr(self.index.codes[c0:c1]), book.dpad,
+                  ptr(self.scale[q0:q1]), ptr(self.bias[q0:q1]), ptr(self.qq[q0:q1]), ptr(self.index.gg[c0:c1]),
+                  ptr(out[q0:q1]), n, q1 - q0, n, book.dpad, PQ_METRICS[book.metric])
+        return out
+
+
+def sq8_dist(qf, index, block_cols=None, block_bytes=None):
+    """The materialised [nq, n] float32 distances of ``qf`` against ``index``, for small cases and tests: per pair
+    dot = scale * float(qcodes . codes) + bias with the exact int32 sum; 'cosine': -dot; 'euclidean':
+    sqrt(max((qq + gg) - 2 dot, 1e-12)), a NaN argument giving 1e-12 as in pairwise_distance_tensor.  tests/sq8_ref.py
+    gives the same bits.  The same bits for every ``block_cols``."""
+    _sq8_check(index, 'sq8_dist')
+    blocks = _Sq8Blocks(qf, index, index.n if block_cols is None and block_bytes is None else block_cols, block_bytes)
+    out = _new((blocks.nq, index.n), blocks.qf)
+    if blocks.nq:
+        for c0, c1 in blocks.spans:
+            out[:, c0:c1] = blocks.block(c0, c1)
+    return out
+
+
+def sq8_search(qf, index, k, exclude=None, block_cols=None, block_bytes=None):
+    """``search`` on D = sq8_dist(qf, index): ``(dist [nq, k] float32, idx [nq, k] int64)``, bit for bit
+    ``rank_rows(D)[:, :k]`` and D at those indices, without D: blocks of code rows through grl_sq8_scan, ranked by
+    search's running top-k.  Ties go to the smaller gallery index; ``exclude`` is search's junk rule; padding is index -1,
+    distance +inf; k <= 1024.  Not sharded: every rank computes the full result."""
+    _sq8_check(index, 'sq8_search')
+    if isinstance(k, bool) or not 1 <= int(k) <= SEARCH_K_MAX:
+        raise ValueError('sq8_search: k must be in 1..%d (got %r)' % (SEARCH_K_MAX, k))
+    k = int(k)
+    qf = index.codebook._check(qf, 'sq8_search', 'qf')
+    nq = qf.shape[0]
+    junk = _junk_ids(exclude, nq, index.n, qf.device)
+    blocks = _Sq8Blocks(qf, index, block_cols, block_bytes)
+    return _search_blocks(blocks, nq, k, False, junk)
+
+
+def sq8_metrics_streaming(qf, index, q_pids, g_pids, q_camids, g_camids, max_rank=100, block_cols=None, block_bytes=None):
+    """``rank_metrics(rank_rows(D), ...)`` for D = sq8_dist(qf, index) without D: (cmc[max_rank] float32, mAP float) with
+    rank_metrics_streaming's contract.  Not sharded."""
+    _sq8_check(index, 'sq8_metrics_streaming')
+    qf = index.codebook._check(qf, 'sq8_metrics_streaming', 'qf')
+    blocks = _Sq8Blocks(qf, index, block_cols, block_bytes)
+    first, nhit, ap = _rank_blocks(blocks, blocks.nq, index.n, q_pids, g_pids, q_camids, g_camids, False)
+    return _cmc_map(first, nhit, ap, index.n, max_rank)
+
+
+def sq8_refine_search(qf, index, store, k, R, exclude=None, block_bytes=None):
+    """Two-stage search over a ``Sq8Index``: exactly ``refine_lists(qf, store, sq8_search(qf, index, R,
+    exclude=exclude)[1], k, index.codebook.metric, block_bytes)``.  The junk rule is applied in the first stage and nowhere
+    else.  k <= R <= 1024; store.n and store.d must be the index's.  ValueError names the argument that is wrong."""
+    _sq8_check(index, 'sq8_refine_search')
+    if not isinstance(store, RefineStore):
+        raise ValueError('sq8_refine_search: store must be a RefineStore (got %s)' % type(store).__name__)
+    d = index.codebook.d
+    if store.n != index.n or store.d != d:
+        raise ValueError('sq8_refine_search: store must hold the rows of the index: store is [%d, %d], the index [%d, %d]'
+                         % (store.n, store.d, index.n, d))
+    k = _pq_int(k, 1, SEARCH_K_MAX, 'sq8_refine_search', 'k')
+    R = _pq_int(R, k, SEARCH_K_MAX, 'sq8_refine_search', 'R (k <= R <= %d)' % SEARCH_K_MAX)
+    cand = sq8_search(qf, index, R, exclude=exclude, block_bytes=block_bytes)[1]
+    return refine_lists(qf, store, cand, k, index.codebook.metric, block_bytes)

@@ -820,6 +820,72 @@ def _bin_report(knob, qf, gf, ids, path):
     return lines
 
 
+def parse_sq8_knob(name, value):
+    """``GRL_EVAL_SQ8``: unset or empty -> None (off); "1" -> (None, None): the int8 scalar-quantised index of
+    engine.sq8_train / sq8_search; "1,R", "1,R,f32" or "1,R,bf16" -> (R, dtype): also the two-stage search
+    engine.sq8_refine_search with a shortlist of R in 1..1024 rows from an engine.RefineStore of that type (default 'f32').
+    Anything else is a ValueError that names the variable."""
+    if value is None or not value.strip():
+        return None
+    parts = [p.strip() for p in value.split(',')]
+    try:
+        if len(parts) > 3 or parts[0] != '1':
+            raise ValueError
+        R = int(parts[1]) if len(parts) >= 2 else None
+        dtype = parts[2] if len(parts) == 3 else ('f32' if R is not None else None)
+        if dtype not in (None, 'f32', 'bf16'):
+            raise ValueError
+    except ValueError:
+        raise ValueError('%s must be "1", "1,R", "1,R,f32" or "1,R,bf16" with an integer R (got %r)' % (name, value))
+    if R is not None and not 1 <= R <= engine.SEARCH_K_MAX:
+        raise ValueError('%s: R must be in 1..%d (got %r)' % (name, engine.SEARCH_K_MAX, value))
+    return R, dtype
+
+
+def _sq8_report(knob, qf, gf, ids, path):
+    """GRL_EVAL_SQ8: an int8 scalar-quantised index of the query-prepended gallery ``gf`` by cosine (engine.sq8_train +
+    engine.sq8_index) -- the lines printed last: CMC / mAP of the sq8 ranking next to the exact ones, recall@1 / 10 / 100 of
+    engine.sq8_search against engine.search under the same junk rule, with R the same for engine.sq8_refine_search, the
+    index bytes against the feature bytes -- and ``path + 'sq8.json'`` (rank 0 alone writes; strict JSON).  A report only:
+    the route's ranking is not touched."""
+    import json
+    R, dtype = knob
+    q_pids, g_pids, q_camids, g_camids = ids
+    gf = gf.contiguous()
+    index = engine.sq8_index(gf, engine.sq8_train(gf, 'cosine'))
+    cmc_x, mAP_x = engine.rank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids)
+    k = min(100, engine.SEARCH_K_MAX, int(gf.size(0)))
+    exact = engine.search(qf, gf, k, exclude=ids)[1]
+    ks = (1, 10, 100)
+    feature_bytes = 4 * int(gf.size(0)) * int(gf.size(1))
+    ranks = [r for r in (1, 5, 10, 20) if r <= len(cmc_x)]
+    fin = lambda r: r if math.isfinite(r) else None
+    cmc, mAP = engine.sq8_metrics_streaming(qf, index, q_pids, g_pids, q_camids, g_camids)
+    recall = engine.topk_recall(engine.sq8_search(qf, index, k, exclude=ids)[1], exact, ks)
+    lines = ['SQ8: {} bytes per row of {}, {} rows'.format(index.codebook.dpad, 4 * int(gf.size(1)), index.n)]
+    lines += ['SQ8 Mean AP: {:4.1%} (exact {:4.1%})'.format(mAP, mAP_x)]
+    lines += ['SQ8 Rank-{:<3}: {:.1%} (exact {:.1%})'.format(r, cmc[r - 1], cmc_x[r - 1]) for r in ranks]
+    lines += ['SQ8 recall@1: {:.2%}  @10: {:.2%}  @100: {:.2%}'.format(*recall)]
+    js = {'n': index.n, 'd': index.d, 'dpad': index.codebook.dpad, 'n_queries': int(qf.size(0)), 'k': k, 'metric': 'cosine',
+          'exact': {'mAP': float(mAP_x), 'cmc': [float(v) for v in cmc_x]},
+          'sq8': {'mAP': float(mAP), 'cmc': [float(v) for v in cmc], 'recall': {str(kk): fin(r) for kk, r in zip(ks, recall)}},
+          'index_bytes': int(index.nbytes), 'code_bytes': int(index.codes.numel()), 'feature_bytes': feature_bytes}
+    if R is not None:
+        store = engine.RefineStore(gf, dtype)
+        kr = min(k, R)
+        refined = engine.topk_recall(engine.sq8_refine_search(qf, index, store, kr, R, exclude=ids)[1], exact, ks)
+        lines += ['SQ8 refined recall@1: {:.2%}  @10: {:.2%}  @100: {:.2%}  (R = {}, k = {}, {} store of {} bytes)'.format(
+            *(tuple(refined) + (R, kr, dtype, store.nbytes)))]
+        js['refine'] = {'R': R, 'k': kr, 'store': dtype, 'store_bytes': int(store.nbytes),
+                        'recall': {str(kk): fin(r) for kk, r in zip(ks, refined)}}
+    lines += ['SQ8 index: {} bytes against {} bytes of features ({:.1f}x smaller)'.format(
+        index.nbytes, feature_bytes, feature_bytes / float(index.nbytes))]
+    if grl_dist._rank_world(None, None)[0] == 0:
+        with open((path or '') + 'sq8.json', 'w') as fh:
+            json.dump(js, fh, allow_nan=False)
+    return lines
+
+
 class ATTEvaluator(object):
     def __init__(self, cnn_model, Siamese_model, only_eval):
         self.cnn_model = cnn_model
@@ -1091,6 +1157,25 @@ class ATTEvaluator(object):
                       'index approximates (unset one of them)'
             if why is not None:
                 raise ValueError('GRL_EVAL_BIN=%s %s' % (os.environ['GRL_EVAL_BIN'].strip(), why))
+        # an int8 scalar-quantised index of the gallery searched on the integer MFMA, off by default (engine.sq8_train /
+        # sq8_search): a report
+        sq8_knob = parse_sq8_knob('GRL_EVAL_SQ8', os.environ.get('GRL_EVAL_SQ8'))
+        if sq8_knob is not None:
+            why = None
+            if rerank:
+                why = 'cannot re-rank: the codes approximate the cosine distance of a query to a gallery row, and ' \
+                      'k-reciprocal re-ranking ranks by a Jaccard blend of whole neighbourhoods (evaluate with rerank=0)'
+            elif knob is not None:
+                why = 'cannot be combined with GRL_EVAL_METRIC=%s: the verification head\'s distance is not a dot product ' \
+                      'of the rows (unset one of them)' % os.environ['GRL_EVAL_METRIC'].strip()
+            elif set_knob is not None:
+                why = 'cannot be combined with GRL_EVAL_SET: the set distances are taken between clip rows, and the ' \
+                      'index holds one code row per tracklet (unset one of them)'
+            elif diffusion_knob is not None:
+                why = 'cannot be combined with GRL_EVAL_DIFFUSION: the diffusion scores replace the cosine ranking the ' \
+                      'index approximates (unset one of them)'
+            if why is not None:
+                raise ValueError('GRL_EVAL_SQ8=%s %s' % (os.environ['GRL_EVAL_SQ8'].strip(), why))
         if pq_knob is not None:
             why = None
             if rerank:
@@ -1186,6 +1271,8 @@ class ATTEvaluator(object):
                 lines = tuple(lines) + tuple(_nng_report(nng_knob, qf, gf, ids, path))
             if bin_knob is not None:
                 lines = tuple(lines) + tuple(_bin_report(bin_knob, qf, gf, ids, path))
+            if sq8_knob is not None:
+                lines = tuple(lines) + tuple(_sq8_report(sq8_knob, qf, gf, ids, path))
             return lines
         if set_knob is not None:
             reduce, metric = set_knob

@@ -1164,6 +1164,49 @@ int grl_bin_pack(const float* z, int64_t ldz, uint8_t* codes, uint32_t* words, i
 int grl_bin_words(const uint8_t* codes, uint32_t* words, int64_t ldw, int64_t n, int nbits, void* stream);
 int grl_bin_lut(const float* z, int64_t ldz, float* lut, int nq, int nbits, void* stream);
 
+/* ---- int8 scalar-quantised gallery: quantiser, decode and the integer-MFMA scan (sq8.hip, engine.sq8_* / Sq8Codebook /
+ * Sq8Index).  Additive: GRL_ABI_VERSION stays 10. ----
+ * Normative; every operation is one fp32 operation, nothing is contracted, rint rounds half to even (tests/sq8_ref.py is the
+ * numpy model).  d <= GRL_SQ8_D_MAX columns, dpad = d rounded up to a multiple of 64.
+ * CODEBOOK: mean[d], delta[d] >= 0, inv[d].  grl_sq8_steps with amax: delta[j] = amax[j] / 127.0f, inv[j] = 127.0f / amax[j],
+ * 0 where amax[j] == 0; without (amax NULL, delta read): inv[j] = 127.0f / (127.0f * delta[j]), 0 where delta[j] == 0.
+ * grl_sq8_absmax: amax[j] = max_i |x[i][j] - mean[j]| (a NaN difference is ignored; 0 for n = 0), an integer atomic max
+ * on the bits of the non-negative floats after the entry point has cleared amax: a maximum has no order.
+ * ROW CODE (grl_sq8_encode): v = (x[i][j] - mean[j]) * inv[j]; c = 0 when v is NaN, else rint(v) clamped to -127 .. 127.
+ * codes int8 [n][ldc], ldc >= dpad a multiple of 16; the columns d .. dpad of a row are written 0 (a zero column adds
+ * exactly 0 to every sum).  Caller-supplied codes may hold -128.
+ * VALUE OF A STORED ROW (grl_sq8_decode): out[i][j] = mean[j] + delta[j] * (float)c[i][j] for j < d: one multiply, one add.
+ * QUERY (grl_sq8_query): w[j] = q[j] * delta[j]; s = the maximum of |w[j]| over the FINITE w[j] (0 if there is none);
+ * r = 127.0f / s; cq[j] = 0 when w[j] is NaN or infinite or fl(w[j] * r) is NaN, else rint(w[j] * r) clamped to
+ * -127 .. 127; scale = s / 127.0f.  s == 0: every code 0, scale 0.  qcodes int8 [nq][ldc] with the zero tail up to dpad.
+ * SCAN (grl_sq8_scan): isum = sum_j cq[q][j] * c[g][j], exact in int32 (dpad * 128^2 <= 2^28); dot = scale[q] *
+ * (float)isum + bias[q] (the conversion rounds to nearest even; bias[q] = q . mean comes from the fp32 GEMM);
+ * GRL_PQ_COSINE: out[q][g] = -dot; GRL_PQ_EUCLIDEAN: t = (qq[q] + gg[g]) - 2.0f * dot, out = sqrtf(t > 1e-12f ? t :
+ * 1e-12f) (a NaN t gives 1e-12f, as grl_pq_scan's).  qq, gg = grl_row_sqnorm of the query and of the decoded row, read by
+ * GRL_PQ_EUCLIDEAN only.  grl_sq8_scan_i32 stores isum itself.  Both operands are rows of K-contiguous bytes with a row
+ * stride, so a block of gallery rows is a pointer offset.  A workgroup of 256 lanes owns a GRL_SQ8_TILE x GRL_SQ8_TILE
+ * tile of out through v_mfma_i32_32x32x32_i8; rows >= n and queries >= nq are neither loaded nor stored.
+ * GRL_EINVAL, before any launch: a null pointer, a negative size, d outside 1..GRL_SQ8_D_MAX, dpad not a multiple of 64 or
+ * above GRL_SQ8_D_MAX, a row stride below its extent (or, for codes, not a multiple of 16), a pointer that is not aligned
+ * (16 bytes: codes and qcodes; 4 bytes: floats and int32), nq > GRL_SQ8_NQ_MAX, an unknown metric, GRL_PQ_EUCLIDEAN
+ * without qq and gg. */
+#define GRL_SQ8_D_MAX    16384
+#define GRL_SQ8_TILE     128
+#define GRL_SQ8_NQ_MAX   1048576
+int grl_sq8_absmax(const float* x, int64_t ldx, const float* mean, float* amax, int64_t n, int d, void* stream);
+int grl_sq8_steps(const float* amax, float* delta, float* inv, int d, void* stream);
+int grl_sq8_encode(const float* x, int64_t ldx, const float* mean, const float* inv, int8_t* codes, int64_t ldc, int64_t n,
+                   int d, void* stream);
+int grl_sq8_decode(const int8_t* codes, int64_t ldc, const float* mean, const float* delta, float* out, int64_t ldo,
+                   int64_t n, int d, void* stream);
+int grl_sq8_query(const float* q, int64_t ldq, const float* delta, int8_t* qcodes, int64_t ldc, float* scale, int nq, int d,
+                  void* stream);
+int grl_sq8_scan(const int8_t* qcodes, int64_t ldqc, const int8_t* codes, int64_t ldc, const float* scale, const float* bias,
+                 const float* qq, const float* gg, float* out, int64_t ldo, int nq, int64_t n, int dpad, int metric,
+                 void* stream);
+int grl_sq8_scan_i32(const int8_t* qcodes, int64_t ldqc, const int8_t* codes, int64_t ldc, int32_t* out, int64_t ldo, int nq,
+                     int64_t n, int dpad, void* stream);
+
 /* ---- ranking by the Siamese verification head (verify.hip, engine.verify_metric / verify_dist) ----
  * In eval mode classifierBN -> classifierlinear on (p - g)^2 is affine in (p - g)^2; the class-1 minus class-0 logit is
  * s(p, g) = sum_d w_d (p_d - g_d)^2 + c.  The ranking distance F = (1 - beta)(-q.g) + beta(-s), p / g = columns
