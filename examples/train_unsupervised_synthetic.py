@@ -1,0 +1,146 @@
+#!/usr/bin/env python
+"""Cluster-contrast training without labels on a synthetic re-id task: the flow of examples/train_synthetic.py (same
+factory calls, two-group SGD, trainer and evaluator) with the pids hidden from training.  Every epoch the evaluator
+extracts the training tracklets' features, `pseudo_labels` clusters them, the two `ClusterMemoryLoss` memories are seeded
+from the cluster centroids and SEQTrainer trains on the relabelled tracklets (grl_amd.reid.train.pseudo.train_unsupervised).
+The hidden pids are only used to print how good the clusters were.  Run:
+
+    PYTHONPATH=.:dropin python examples/train_unsupervised_synthetic.py --epochs 2
+
+Every identity is a low-frequency colour layout ("a person in front of a background", as grl_amd.synthetic.
+synth_clips_structured); a tracklet is a small deviation from its identity's layout, a frame a smaller one, plus pixel noise.
+Single process: under torch.distributed the flow is the same on every rank (the evaluator gathers the features)."""
+import argparse
+import os.path as osp
+import sys
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+from torch.utils.data import DataLoader, Dataset
+
+ROOT = osp.dirname(osp.dirname(osp.abspath(__file__)))
+for p in (ROOT, osp.join(ROOT, 'dropin')):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+from reid import models                                             # noqa: E402
+from reid.loss import PairLoss, ClusterMemoryLoss                   # noqa: E402
+from reid.train import SEQTrainer, train_unsupervised               # noqa: E402
+from reid.evaluator import ATTEvaluator                             # noqa: E402
+from reid.data import RandomPairSamplerForMars                      # noqa: E402
+from grl_amd.synthetic import synth_state_dict, IMAGENET_MEAN, IMAGENET_STD   # noqa: E402
+
+
+def identity_clip(pid, track, seq_len, seed, h=256, w=128):
+    """float32 [T,3,h,w], ToTensor + Normalize applied: identity layout + tracklet deviation + frame deviation + noise"""
+    base = np.random.Generator(np.random.PCG64([seed, pid])).uniform(0.0, 1.0, (1, 3, 8, 4))
+    g = np.random.Generator(np.random.PCG64([seed, pid, track + 1]))
+    low = base + g.uniform(-0.08, 0.08, (1, 3, 8, 4)) + g.uniform(-0.05, 0.05, (seq_len, 3, 8, 4))
+    low = F.interpolate(torch.from_numpy(low.astype(np.float32)), size=(h, w), mode='bilinear', align_corners=False)
+    noise = torch.from_numpy(g.uniform(-0.1, 0.1, (seq_len, 3, h, w)).astype(np.float32))
+    x = ((low + noise).clamp_(0.0, 1.0) * 255.0).round_().div_(255.0)
+    mean = torch.tensor(IMAGENET_MEAN, dtype=torch.float32).view(1, 3, 1, 1)
+    std = torch.tensor(IMAGENET_STD, dtype=torch.float32).view(1, 3, 1, 1)
+    return x.sub_(mean).div_(std)
+
+
+def tracklets_of(pids, per_cam, cams, first_track=0):
+    """[((pid, track), pid, cam)]: the first element stands for a tracklet's frame paths"""
+    return [((pid, first_track + c * per_cam + t), pid, c) for pid in pids for c in cams for t in range(per_cam)]
+
+
+class Clips(Dataset):
+    def __init__(self, tracklets, seq_len, seed):
+        self.tracklets, self.seq_len, self.seed = list(tracklets), seq_len, seed
+
+    def __len__(self):
+        return len(self.tracklets)
+
+    def __getitem__(self, i):
+        (pid, track), label, cam = self.tracklets[i]
+        return identity_clip(pid, track, self.seq_len, self.seed), label, cam
+
+
+def main(args):
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    device = torch.device('cuda', 0)
+    train = tracklets_of(range(args.ids), args.per_cam, (0, 1))
+    hidden = np.array([t[1] for t in train])
+    train = [(paths, -1, cam) for paths, _, cam in train]                        # the pids are hidden from here on
+    test_ids = range(1000, 1000 + args.test_ids)
+    query, gallery = tracklets_of(test_ids, 1, (0,)), tracklets_of(test_ids, 2, (1, 2), first_track=10)
+    query_loader = DataLoader(Clips(query, args.seq_len, args.seed), batch_size=8)
+    gallery_loader = DataLoader(Clips(gallery, args.seq_len, args.seed), batch_size=8)
+
+    cnn_model = models.create('resnet50_grl', num_features=2048, dropout=0, numclasses=args.ids, pretrained=False)
+    siamese_model = models.create('siamese', input_num=2048, output_num=512, class_num=2)
+    siamese_model_uncorr = models.create('siamese_video', input_num=2048, output_num=512, class_num=2)
+    cnn_model.load_state_dict(synth_state_dict(cnn_model, seed=0))
+    siamese_model.load_state_dict(synth_state_dict(siamese_model, seed=0, prefix='siamese.'))
+    siamese_model_uncorr.load_state_dict(synth_state_dict(siamese_model_uncorr, seed=0, prefix='siamese_video.'))
+    cnn_model, siamese_model, siamese_model_uncorr = (m.to(device) for m in (cnn_model, siamese_model, siamese_model_uncorr))
+
+    # the memories are seeded every epoch (reset): the size given here is only a placeholder
+    criterion_corr = ClusterMemoryLoss(2048, 2, temp=args.temp, momentum=args.momentum, mode=args.mode).to(device)
+    criterion_uncorr = ClusterMemoryLoss(2048, 2, temp=args.temp, momentum=args.momentum, mode=args.mode).to(device)
+    criterion_veri = PairLoss().to(device)
+
+    base_param_ids = set(map(id, cnn_model.backbone.parameters()))
+    new_params = [p for p in cnn_model.parameters() if id(p) not in base_param_ids]
+    param_groups = [{'params': cnn_model.backbone.parameters(), 'lr_mult': 1}, {'params': new_params, 'lr_mult': 2},
+                    {'params': siamese_model.parameters(), 'lr_mult': 2},
+                    {'params': siamese_model_uncorr.parameters(), 'lr_mult': 2}]
+    optimizer = torch.optim.SGD(param_groups, lr=args.lr, momentum=0.9, weight_decay=5e-4, nesterov=True)
+    for g in optimizer.param_groups:
+        g['lr'] = args.lr * g.get('lr_mult', 1)
+
+    evaluator = ATTEvaluator(cnn_model, siamese_model, only_eval=False)
+    trainer = SEQTrainer(cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr, criterion_uncorr,
+                         osp.join(args.logs_dir, 'train_log'))
+
+    def make_eval_loader(tracklets):
+        return DataLoader(Clips(tracklets, args.seq_len, args.seed), batch_size=8, shuffle=False)
+
+    def make_train_loader(relabelled):
+        return DataLoader(Clips(relabelled, args.seq_len, args.seed), batch_size=args.batch_size,
+                          sampler=RandomPairSamplerForMars(relabelled), drop_last=True)
+
+    def on_epoch(epoch, labels):
+        s = labels.pair_scores(hidden)
+        print('epoch {}: n_clusters {} n_noise {} of {} | against the hidden pids: precision {:.3f} recall {:.3f} F1 {:.3f} '
+              'ARI {:.3f} | loss {:.3f}'.format(epoch, labels.n_clusters, labels.n_noise, len(labels), s['precision'],
+                                                s['recall'], s['f1'], s['ari'], trainer.meters['loss'].avg))
+        evaluator.evaluate(None, None, query_loader, gallery_loader, args.logs_dir, False, False)   # prints Mean AP / Rank-k
+
+    print('before training:')
+    evaluator.evaluate(None, None, query_loader, gallery_loader, args.logs_dir, False, False)
+    label_kwargs = dict(method=args.method, eps=args.eps, min_samples=args.min_samples, k1=args.k1, k2=args.k2, k=args.k,
+                        min_cluster_size=args.min_cluster_size)
+    train_unsupervised(trainer, evaluator, optimizer, train, make_eval_loader, make_train_loader, args.epochs,
+                       label_kwargs=label_kwargs, on_epoch=on_epoch)
+
+
+if __name__ == '__main__':
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--ids', type=int, default=12, help='training identities (hidden)')
+    ap.add_argument('--per-cam', type=int, default=3, help='tracklets per identity and camera (two cameras)')
+    ap.add_argument('--test-ids', type=int, default=8)
+    ap.add_argument('-b', '--batch-size', type=int, default=8)
+    ap.add_argument('--seq_len', type=int, default=4)
+    ap.add_argument('--epochs', type=int, default=2)
+    ap.add_argument('--lr', type=float, default=1e-3)
+    ap.add_argument('--method', default='jaccard', choices=['jaccard', 'cosine', 'hdbscan', 'kmeans'])
+    ap.add_argument('--eps', type=float, default=0.5)
+    ap.add_argument('--min-samples', type=int, default=2)
+    ap.add_argument('--k1', type=int, default=5)
+    ap.add_argument('--k2', type=int, default=1)
+    ap.add_argument('--k', type=int, default=None, help="clusters of method 'kmeans'")
+    ap.add_argument('--min-cluster-size', type=int, default=3)
+    ap.add_argument('--temp', type=float, default=0.05)
+    ap.add_argument('--momentum', type=float, default=0.2)
+    ap.add_argument('--mode', default='hard', choices=['hard', 'mean', 'instance'])
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--logs-dir', type=str, default='/tmp/grl_logs')
+    main(ap.parse_args())

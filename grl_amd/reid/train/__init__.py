@@ -1,1 +1,2 @@
 from .trainer import SEQTrainer
+from .pseudo import PseudoLabels, pseudo_labels, train_unsupervised

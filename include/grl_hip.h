@@ -534,6 +534,25 @@ int grl_pair_sqdiff_bwd(const float* p, const float* g, const float* ddiff, floa
 int grl_oim_update(float* lut, const float* x, const int64_t* labels, int n, int D, int num_classes,
                    float momentum, void* stream);
 
+/* Cluster-memory update of cluster-contrast training (cmem.hip, ClusterMemoryLoss).  Additive:
+ * GRL_ABI_VERSION stays 10.  cent [K][D] is updated in place, x is [n][D], labels int64 [n]; D % 4 == 0, n >= 1, K >= 1,
+ * cent and x 16-byte aligned.  A label outside [0, K) updates nothing (DBSCAN's noise label -1).  For every label y
+ * present, its members are the ascending j with labels[j] == y.
+ *   mode 0 (hard): s_j = sum_c x[j][c] * cent[y][c] on the row as it is BEFORE this launch; j* = the member with the
+ *     smallest s_j under a strict < against a running best that starts at the first member (the first member wins ties, a
+ *     NaN never replaces the running best); v = x[j*].
+ *   mode 1 (mean): v = (sum over the members of x[j], added in ascending j from 0) / (float)count.
+ *   then, as grl_oim_update: cent[y] = momentum * cent[y] + (1 - momentum) * v, and the row is scaled by
+ *     1 / sqrtf(sum c^2) (a zero-norm row becomes NaN, as there).
+ * sel (int32 [n], may be NULL): 1 where row i contributed (hard: the selected member; mean: every member), 0 elsewhere
+ * and on rows whose label is out of range.
+ * One 256-lane workgroup per batch row; the workgroup of a label's first row is the only writer of that centroid row
+ * and of its members' sel.  Every dot product and sum of squares: lane t adds dot4 of the floats 4 t + 1024 k .. + 3 for
+ * k = 0, 1, ..., the wave's 64 partials meet in an xor tree, the four waves' totals are added in sequence from 0.  No
+ * atomics: the result is the same bits on every run, and a row's result does not depend on the batch's other labels. */
+int grl_cmem_update(float* cent, const float* x, const int64_t* labels, int n, int D, int K, float momentum, int mode,
+                    int32_t* sel, void* stream);
+
 /* ---- the trainer's loss block, forward and backward on the device ---- */
 /* F.cross_entropy of OIMLoss.forward (reid/loss/oim.py:52; mean reduction, optional class
  * weight): loss[0] = sum_i w[y_i] (logsumexp(z_i) - z_i[y_i]) / sum_i w[y_i];
