@@ -6,6 +6,9 @@ from the cluster centroids and SEQTrainer trains on the relabelled tracklets (gr
 The hidden pids are only used to print how good the clusters were.  Run:
 
     PYTHONPATH=.:dropin python examples/train_unsupervised_synthetic.py --epochs 2
+    PYTHONPATH=.:dropin python examples/train_unsupervised_synthetic.py --epochs 2 --camera-proxies --k-neg 8 --inter-from-epoch 1
+
+(the second form: camera-aware proxies, one memory row per cluster and camera -- ProxyMemoryLoss under CameraSEQTrainer)
 
 Every identity is a low-frequency colour layout ("a person in front of a background", as grl_amd.synthetic.
 synth_clips_structured); a tracklet is a small deviation from its identity's layout, a frame a smaller one, plus pixel noise.
@@ -25,8 +28,8 @@ for p in (ROOT, osp.join(ROOT, 'dropin')):
         sys.path.insert(0, p)
 
 from reid import models                                             # noqa: E402
-from reid.loss import PairLoss, ClusterMemoryLoss                   # noqa: E402
-from reid.train import SEQTrainer, train_unsupervised               # noqa: E402
+from reid.loss import PairLoss, ClusterMemoryLoss, ProxyMemoryLoss  # noqa: E402
+from reid.train import SEQTrainer, CameraSEQTrainer, train_unsupervised   # noqa: E402
 from reid.evaluator import ATTEvaluator                             # noqa: E402
 from reid.data import RandomPairSamplerForMars                      # noqa: E402
 from grl_amd.synthetic import synth_state_dict, IMAGENET_MEAN, IMAGENET_STD   # noqa: E402
@@ -83,8 +86,13 @@ def main(args):
     cnn_model, siamese_model, siamese_model_uncorr = (m.to(device) for m in (cnn_model, siamese_model, siamese_model_uncorr))
 
     # the memories are seeded every epoch (reset): the size given here is only a placeholder
-    criterion_corr = ClusterMemoryLoss(2048, 2, temp=args.temp, momentum=args.momentum, mode=args.mode).to(device)
-    criterion_uncorr = ClusterMemoryLoss(2048, 2, temp=args.temp, momentum=args.momentum, mode=args.mode).to(device)
+    if args.camera_proxies:
+        # one memory row per (cluster, camera) pair, DESIGN.md 4aj: the trainer that keeps the batch's camera ids
+        criterion_corr, criterion_uncorr = (ProxyMemoryLoss(2048, temp=args.temp, momentum=args.momentum, mode=args.mode,
+                                                            k_neg=args.k_neg).to(device) for _ in range(2))
+    else:
+        criterion_corr = ClusterMemoryLoss(2048, 2, temp=args.temp, momentum=args.momentum, mode=args.mode).to(device)
+        criterion_uncorr = ClusterMemoryLoss(2048, 2, temp=args.temp, momentum=args.momentum, mode=args.mode).to(device)
     criterion_veri = PairLoss().to(device)
 
     base_param_ids = set(map(id, cnn_model.backbone.parameters()))
@@ -97,8 +105,9 @@ def main(args):
         g['lr'] = args.lr * g.get('lr_mult', 1)
 
     evaluator = ATTEvaluator(cnn_model, siamese_model, only_eval=False)
-    trainer = SEQTrainer(cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr, criterion_uncorr,
-                         osp.join(args.logs_dir, 'train_log'))
+    trainer = (CameraSEQTrainer if args.camera_proxies else SEQTrainer)(
+        cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr, criterion_uncorr,
+        osp.join(args.logs_dir, 'train_log'))
 
     def make_eval_loader(tracklets):
         return DataLoader(Clips(tracklets, args.seq_len, args.seed), batch_size=8, shuffle=False)
@@ -109,6 +118,9 @@ def main(args):
 
     def on_epoch(epoch, labels):
         s = labels.pair_scores(hidden)
+        if args.camera_proxies:
+            print('epoch {}: {} proxies, inter-camera term {}'.format(epoch, criterion_corr.num_proxies,
+                                                                      'on' if criterion_corr.inter_on else 'off'))
         print('epoch {}: n_clusters {} n_noise {} of {} | against the hidden pids: precision {:.3f} recall {:.3f} F1 {:.3f} '
               'ARI {:.3f} | loss {:.3f}'.format(epoch, labels.n_clusters, labels.n_noise, len(labels), s['precision'],
                                                 s['recall'], s['f1'], s['ari'], trainer.meters['loss'].avg))
@@ -119,7 +131,8 @@ def main(args):
     label_kwargs = dict(method=args.method, eps=args.eps, min_samples=args.min_samples, k1=args.k1, k2=args.k2, k=args.k,
                         min_cluster_size=args.min_cluster_size)
     train_unsupervised(trainer, evaluator, optimizer, train, make_eval_loader, make_train_loader, args.epochs,
-                       label_kwargs=label_kwargs, on_epoch=on_epoch)
+                       label_kwargs=label_kwargs, on_epoch=on_epoch, cameras=args.camera_proxies,
+                       inter_from_epoch=args.inter_from_epoch)
 
 
 if __name__ == '__main__':
@@ -141,6 +154,10 @@ if __name__ == '__main__':
     ap.add_argument('--temp', type=float, default=0.05)
     ap.add_argument('--momentum', type=float, default=0.2)
     ap.add_argument('--mode', default='hard', choices=['hard', 'mean', 'instance'])
+    ap.add_argument('--camera-proxies', action='store_true',
+                    help='camera-aware proxies: ProxyMemoryLoss under CameraSEQTrainer (DESIGN.md 4aj)')
+    ap.add_argument('--k-neg', type=int, default=50, help='hardest proxies of other clusters in the inter-camera term')
+    ap.add_argument('--inter-from-epoch', type=int, default=0, help='first epoch with the inter-camera term')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--logs-dir', type=str, default='/tmp/grl_logs')
     main(ap.parse_args())

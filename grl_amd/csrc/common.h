@@ -83,7 +83,27 @@ static __device__ __forceinline__ float block_sum(float v, float* red) {
     return t;
 }
 
-// gemm_bf16.hip: 256 x 256 bf16-storage tile.  1 = launched, 0 = shape not covered (use the
+// wave64 max (all lanes receive it)
+static __device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+
+// block-wide max for <= 16 waves; all threads receive it.
+static __device__ __forceinline__ float block_max(float v, float* red) {
+    v = wave_max(v);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nw = (blockDim.x + 63) >> 6;
+    __syncthreads();
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    float t = red[0];
+    for (int i = 1; i < nw; ++i) t = fmaxf(t, red[i]);
+    return t;
+}
+
+// gemm_bf16.hip: 256 x 256 bf16-storage tile. 1 = launched, 0 = shape not covered (use the
 // 128 x 128 family), < 0 = error.
 struct GrlGemm;
 int grl_gemm_bf16_256(const GrlGemm& d, hipStream_t s);

@@ -13,25 +13,6 @@
 
 namespace {
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
-// block-wide max for <= 16 waves; all threads receive it.
-__device__ __forceinline__ float block_max(float v, float* red) {
-    v = wave_max(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nw = (blockDim.x + 63) >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    float t = red[0];
-    for (int i = 1; i < nw; ++i) t = fmaxf(t, red[i]);
-    return t;
-}
-
 __device__ __forceinline__ bool label_ok(int64_t y, int c) { return y >= 0 && y < c; }
 
 // One workgroup per row: log-softmax, weighted row loss, gradient of the MEAN loss, arg-max hit.

@@ -1,2 +1,3 @@
 from .trainer import SEQTrainer
-from .pseudo import PseudoLabels, pseudo_labels, train_unsupervised
+from .camera import CameraSEQTrainer
+from .pseudo import PseudoLabels, ProxyLabels, pseudo_labels, train_unsupervised

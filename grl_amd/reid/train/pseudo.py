@@ -3,7 +3,9 @@ clusterings into a relabelled training set and seeded cluster memories.
 
   pseudo_labels(xf, method, ..)   one of engine.cluster_jaccard / cluster / hdbscan / kmeans  ->  PseudoLabels
   PseudoLabels                    the labels on the device and on the host, the kept (non-noise) tracklets, unit centroids
+  ProxyLabels                     ``PseudoLabels.proxies(cams)``: one proxy per (cluster, camera) pair
   train_unsupervised(..)          per epoch: extract, cluster, seed ``ClusterMemoryLoss.reset``, ``SEQTrainer.train``
+                                  (``cameras=True``: ``ProxyMemoryLoss.reset`` from the proxies, ``CameraSEQTrainer``)
 
 SEQTrainer itself is unchanged: it takes any criterion pair, and ``RandomPairSamplerForMars`` / ``RawVideoDataset`` take the
 relabelled ``[(paths, label, cam)]`` list as they take a dataset's own."""
@@ -70,11 +72,65 @@ class PseudoLabels(object):
             xf = xf[:, c0:c1]
         return engine.cluster_centroids(xf, self.labels.to(xf.device), self.n_clusters, reduce='unit')[0]
 
+    def proxies(self, cams):
+        """Camera-aware proxy labels: ``cams`` holds one non-negative integer per sample; the distinct
+        (cluster, cam) pairs of the kept samples are numbered in ascending (cluster, cam) order -> ``ProxyLabels``.  Runs
+        on the host copy of the labels: no further read-back."""
+        return ProxyLabels(self, cams)
+
     def pair_scores(self, pids):
         """``Clustering.pair_scores`` of the labels against true identities (for data whose truth is known): pairwise
         precision / recall / F1 / ARI on the host, a noise sample being a cluster of its own."""
         from grl_amd import engine
         return engine._pair_scores(torch.from_numpy(self.host), self.n_clusters, pids)
+
+
+class ProxyLabels(object):
+    """One proxy per (cluster, camera) pair that occurs among the kept samples of ``labels`` (a PseudoLabels).
+
+      proxy_cluster, proxy_cam   int32 numpy [n_proxies]: the pair of every proxy, ascending in (cluster, cam)
+      proxy_cluster_dev, proxy_cam_dev   the same as int32 tensors on the labels' device (``ProxyMemoryLoss.reset`` takes them)
+      sample_proxy               int64 numpy [n]: the proxy of every sample, -1 for noise
+      sample_proxy_dev           the same on the labels' device
+      n_proxies"""
+
+    def __init__(self, labels, cams):
+        if torch.is_tensor(cams):
+            cams = cams.detach().cpu().numpy()
+        cams = np.asarray(cams)
+        if cams.ndim != 1 or cams.size != labels.host.size or cams.dtype.kind not in 'iu':
+            raise ValueError('PseudoLabels.proxies: cams must be %d integers, one per sample (got %s %s)' % (
+                labels.host.size, cams.dtype, cams.shape))
+        cams = cams.astype(np.int64)
+        if cams.size and cams.min() < 0:
+            raise ValueError('PseudoLabels.proxies: a camera id is negative (%d)' % cams.min())
+        if cams.size and cams.max() >= 2 ** 31:
+            raise ValueError('PseudoLabels.proxies: a camera id does not fit int32 (%d)' % cams.max())
+        keep = labels.keep
+        span = int(cams.max()) + 1 if cams.size else 1
+        pair = labels.host[keep] * span + cams[keep]        # ascending in (cluster, cam)
+        ids = np.unique(pair)
+        self.labels = labels
+        self.n_proxies = int(ids.size)
+        self.proxy_cluster = (ids // span).astype(np.int32)
+        self.proxy_cam = (ids % span).astype(np.int32)
+        self.sample_proxy = np.full(labels.host.size, -1, np.int64)
+        self.sample_proxy[keep] = np.searchsorted(ids, pair)
+        dev = labels.labels.device
+        self.proxy_cluster_dev = torch.from_numpy(self.proxy_cluster).to(dev)
+        self.proxy_cam_dev = torch.from_numpy(self.proxy_cam).to(dev)
+        self.sample_proxy_dev = torch.from_numpy(self.sample_proxy).to(dev)
+
+    def centroids(self, xf, cols=None):
+        """Unit proxy centroids [n_proxies, d'] of the columns ``cols = (c0, c1)`` (default: all) of the rows the labels were
+        computed from: ``engine.cluster_centroids(xf[:, c0:c1], sample_proxy, n_proxies, reduce='unit')``, noise ignored."""
+        from grl_amd import engine
+        if cols is not None:
+            c0, c1 = cols
+            if not 0 <= c0 < c1 <= xf.shape[1]:
+                raise ValueError('ProxyLabels.centroids: cols = %r is no column range of %d columns' % (cols, xf.shape[1]))
+            xf = xf[:, c0:c1]
+        return engine.cluster_centroids(xf, self.sample_proxy_dev.to(xf.device), self.n_proxies, reduce='unit')[0]
 
 
 def pseudo_labels(xf, method='jaccard', eps=0.5, min_samples=4, k1=20, k2=6, k=None, min_cluster_size=5, metric='cosine'):
@@ -108,7 +164,7 @@ def pseudo_labels(xf, method='jaccard', eps=0.5, min_samples=4, k1=20, k2=6, k=N
 
 
 def train_unsupervised(trainer, evaluator, optimizer, tracklets, make_eval_loader, make_train_loader, epochs,
-                       label_kwargs=None, on_epoch=None):
+                       label_kwargs=None, on_epoch=None, cameras=False, inter_from_epoch=0):
     """Cluster-contrast training of ``trainer`` (a SEQTrainer whose ``criterion_corr`` / ``criterion_uncorr`` are
     ``ClusterMemoryLoss``) on ``tracklets`` = [(paths, pid, cam)] whose pids are never used.  Every epoch:
 
@@ -120,9 +176,24 @@ def train_unsupervised(trainer, evaluator, optimizer, tracklets, make_eval_loade
       trainer.train(epoch, make_train_loader(labels.relabel(tracklets)), optimizer)
       on_epoch(epoch, labels)                                             if given
 
+    ``cameras=True`` (camera-aware proxies): ``trainer`` is a ``CameraSEQTrainer`` whose two criteria are
+    ``ProxyMemoryLoss`` (checked before any device call); both memories are seeded from
+    ``proxies = labels.proxies([t[2] for t in tracklets])`` -- ``reset(proxies.centroids(xf, cols), proxies.proxy_cluster_dev,
+    proxies.proxy_cam_dev)`` over the same column ranges -- and their ``inter_on`` is ``epoch >= inter_from_epoch``.
+
     Returns the epochs' ``PseudoLabels``.  Under torch.distributed ``extract_feature`` gathers every row on every rank, so
     all ranks compute the same labels and seed the same memories."""
     tracklets = list(tracklets)
+    if cameras:
+        from grl_amd.reid.loss import ProxyMemoryLoss
+        from grl_amd.reid.train.camera import CameraSEQTrainer
+        if not isinstance(trainer, CameraSEQTrainer):
+            raise ValueError('train_unsupervised: cameras=True needs a CameraSEQTrainer (got %s): SEQTrainer drops the '
+                             "batch's camera ids" % type(trainer).__name__)
+        for name in ('criterion_corr', 'criterion_uncorr'):
+            if not isinstance(getattr(trainer, name), ProxyMemoryLoss):
+                raise ValueError('train_unsupervised: cameras=True needs %s to be a ProxyMemoryLoss (got %s)' % (
+                    name, type(getattr(trainer, name)).__name__))
     history = []
     for epoch in range(epochs):
         xf = evaluator.extract_feature(make_eval_loader(tracklets))[0]
@@ -130,8 +201,14 @@ def train_unsupervised(trainer, evaluator, optimizer, tracklets, make_eval_loade
             raise ValueError('train_unsupervised: the eval loader gave features %s for %d tracklets (one row of at least '
                              '%d columns per tracklet is needed)' % (tuple(xf.shape), len(tracklets), CORR_COLS[1]))
         labels = pseudo_labels(xf, **(label_kwargs or {}))
-        trainer.criterion_uncorr.reset(labels.centroids(xf, cols=UNCORR_COLS))
-        trainer.criterion_corr.reset(labels.centroids(xf, cols=CORR_COLS))
+        if cameras:
+            proxies = labels.proxies([t[2] for t in tracklets])
+            for crit, cols in ((trainer.criterion_uncorr, UNCORR_COLS), (trainer.criterion_corr, CORR_COLS)):
+                crit.reset(proxies.centroids(xf, cols=cols), proxies.proxy_cluster_dev, proxies.proxy_cam_dev)
+                crit.inter_on = epoch >= inter_from_epoch
+        else:
+            trainer.criterion_uncorr.reset(labels.centroids(xf, cols=UNCORR_COLS))
+            trainer.criterion_corr.reset(labels.centroids(xf, cols=CORR_COLS))
         trainer.train(epoch, make_train_loader(labels.relabel(tracklets)), optimizer)
         history.append(labels)
         if on_epoch is not None:

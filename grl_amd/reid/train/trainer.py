@@ -250,6 +250,12 @@ class SEQTrainer(BaseTrainer):
         """softmax over the two verification logits, class-1 column (trainer.py:146-148)."""
         return pair_prob(encode_scores)
 
+    def _id_loss(self, criterion, feats, targets, rows):
+        """One identity criterion of ``_forward``; ``rows`` says which rows ``targets`` label: 'frame' (the batch's targets
+        expanded over T) or 'clip' (probe-then-gallery).  A subclass overrides it to hand a criterion more than the targets
+        (``CameraSEQTrainer``: the rows' cameras)."""
+        return criterion(feats, targets)
+
     def _forward(self, inputs, targets, i, epoch):
         """trainer.py:107-170: id loss on frames + id loss on pooled clips (same LUT) +
         20 x pair verification + batch-hard triplet on the correlated branch, id loss on
@@ -274,14 +280,14 @@ class SEQTrainer(BaseTrainer):
         fk = _HeadFork(x_uncorr)
         with fk:
             encode_scores_u, siamese_out_u = self.siamese_model_uncorr(x_uncorr)
-            uncorr_id_loss_vid, output_id = self.criterion_uncorr(siamese_out_u, target)
+            uncorr_id_loss_vid, output_id = self._id_loss(self.criterion_uncorr, siamese_out_u, target, 'clip')
             uncorr_prec_id_vid = self._top1(output_id, target)
         # (the reference also evaluates the uncorr verification loss but never adds it)
-        corr_id_loss_frame, output_id = self.criterion_corr(frame_corr, targetX)
+        corr_id_loss_frame, output_id = self._id_loss(self.criterion_corr, frame_corr, targetX, 'frame')
         corr_prec_id_frame = self._top1(output_id, targetX)
 
         encode_scores, siamese_out = self.siamese_model(x_corr)
-        corr_id_loss_vid, output_id = self.criterion_corr(siamese_out, target)
+        corr_id_loss_vid, output_id = self._id_loss(self.criterion_corr, siamese_out, target, 'clip')
         corr_prec_id_vid = self._top1(output_id, target)
         corr_loss_tri = criterion_triplet(siamese_out, target).mean()
         corr_loss_ver, _ = self.criterion_ver(self._pair_prob(encode_scores), tar_probe, tar_gallery)

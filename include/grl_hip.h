@@ -553,6 +553,44 @@ int grl_oim_update(float* lut, const float* x, const int64_t* labels, int n, int
 int grl_cmem_update(float* cent, const float* x, const int64_t* labels, int n, int D, int K, float momentum, int mode,
                     int32_t* sel, void* stream);
 
+/* Camera-aware proxy cross entropy of unsupervised training (proxy.hip, ProxyMemoryLoss): a cross entropy
+ * over per-row sets of columns with a deterministic top-k selection of hard negatives, forward and gradient in one call.
+ * Additive: GRL_ABI_VERSION stays 10.  logits [n][ld] (P columns used) are the scaled similarities of the n rows to the
+ * P proxies; labels / cams int64 [n] are the row's cluster id and camera id; proxy_cluster / proxy_cam int32 [P] say
+ * which (cluster, camera) pair every proxy stands for.
+ * Row i:
+ *   own_i = the smallest j with proxy_cluster[j] == labels[i] and proxy_cam[j] == cams[i].  If there is none (the noise
+ *     label -1, a pair without a proxy) the row is INVALID: own[i] = -1, its dlogits row is zeros, its negsel row is -1,
+ *     and it adds nothing to loss or correct.
+ *   For a valid row:  A_i = {j : proxy_cam[j] == cams[i]},  Pos_i = {j : proxy_cluster[j] == labels[i]} (holds own_i),
+ *     N_i = {j : proxy_cluster[j] != labels[i]},  Neg_i = the first min(k_neg, |N_i|) members of N_i in the order
+ *     logit descending, then index ascending -- compared as fp32 values as given (-0 == +0),  U_i = Pos_i + Neg_i.
+ *   L_i = w_intra (lse_{A_i}(z) - z[own_i]) + w_inter (lse_{U_i}(z) - (1 / |Pos_i|) sum_{j in Pos_i} z[j]);
+ *     each lse is shifted by the maximum over its own set, and the mean over Pos_i is taken of the shifted logits.
+ * nv = the number of valid rows.  loss[0] = (sum over the valid rows of L_i) / nv, 0 if nv = 0: the terms fl(fl(1 / nv) L_i)
+ * are added in index order from 0, as the rows of grl_softmax_ce.
+ * dlogits[i][j] (may be NULL) = (1 / nv) ( w_intra [j in A_i] (p^A_j - [j == own_i])
+ *                                        + w_inter [j in U_i] (p^U_j - [j in Pos_i] / |Pos_i|) ),  p^S the softmax over S.
+ * correct[0] (may be NULL) = the number of valid rows with proxy_cluster[arg] == labels[i], arg the arg-max over all P
+ *   columns (first index on ties, as grl_softmax_ce).
+ * own (int64 [n], may be NULL) = own_i.  negsel (int32 [n][k_neg], may be NULL; ignored when k_neg = 0) = Neg_i in
+ *   ascending j, padded with -1.  k_neg = 0: no negatives.
+ * ws: 3 * n floats of scratch.
+ * Limits, each refused with GRL_EINVAL before anything is launched: n < 1, P < 1, k_neg outside 0 .. P, ld < P,
+ * dlogits given and ldd < P, a NULL logits / labels / cams / proxy_cluster / proxy_cam / loss / ws, P > GRL_PROXY_MAX_P
+ * (the row and its set flags live in LDS, under the 64 KB a workgroup gets without an opt-in).
+ * A NaN logit gives unspecified values, never an access outside the arrays.
+ * Two launches.  First one 256-lane workgroup per row: lane t takes the columns t + 256 k; every max, sum and count is
+ * a wave64 xor tree followed by the four waves' totals in sequence; the selection threshold is the k-th largest
+ * order-preserving key of N_i, found bit by bit from exact integer counts, and the columns that equal it are admitted by a
+ * prefix count in index order.  Then the rows' losses, hits and valid flags are added in index order, every workgroup of
+ * that launch re-derives nv from the same flags, and dlogits is scaled by fl(1 / nv).  No atomics: the same bits on every run. */
+#define GRL_PROXY_MAX_P 8192
+int grl_proxy_ce(const float* logits, int64_t ld, const int64_t* labels, const int64_t* cams,
+                 const int32_t* proxy_cluster, const int32_t* proxy_cam, int n, int P, int k_neg, float w_intra,
+                 float w_inter, float* loss, float* correct, float* dlogits, int64_t ldd, int64_t* own,
+                 int32_t* negsel, float* ws, void* stream);
+
 /* ---- the trainer's loss block, forward and backward on the device ---- */
 /* F.cross_entropy of OIMLoss.forward (reid/loss/oim.py:52; mean reduction, optional class
  * weight): loss[0] = sum_i w[y_i] (logsumexp(z_i) - z_i[y_i]) / sum_i w[y_i];
