@@ -8,7 +8,11 @@ The hidden pids are only used to print how good the clusters were.  Run:
     PYTHONPATH=.:dropin python examples/train_unsupervised_synthetic.py --epochs 2
     PYTHONPATH=.:dropin python examples/train_unsupervised_synthetic.py --epochs 2 --camera-proxies --k-neg 8 --inter-from-epoch 1
 
-(the second form: camera-aware proxies, one memory row per cluster and camera -- ProxyMemoryLoss under CameraSEQTrainer)
+    PYTHONPATH=.:dropin python examples/train_unsupervised_synthetic.py --epochs 2 --hybrid-memory --self-paced 0.02
+
+(the second form: camera-aware proxies, one memory row per cluster and camera -- ProxyMemoryLoss under CameraSEQTrainer;
+the third: a hybrid memory with one row per tracklet, the samples the clustering calls noise trained on as classes of their
+own, and only the clusters that are stable under eps -/+ 0.02 kept -- HybridMemoryLoss under HybridSEQTrainer)
 
 Every identity is a low-frequency colour layout ("a person in front of a background", as grl_amd.synthetic.
 synth_clips_structured); a tracklet is a small deviation from its identity's layout, a frame a smaller one, plus pixel noise.
@@ -28,8 +32,8 @@ for p in (ROOT, osp.join(ROOT, 'dropin')):
         sys.path.insert(0, p)
 
 from reid import models                                             # noqa: E402
-from reid.loss import PairLoss, ClusterMemoryLoss, ProxyMemoryLoss  # noqa: E402
-from reid.train import SEQTrainer, CameraSEQTrainer, train_unsupervised   # noqa: E402
+from reid.loss import PairLoss, ClusterMemoryLoss, ProxyMemoryLoss, HybridMemoryLoss  # noqa: E402
+from reid.train import SEQTrainer, CameraSEQTrainer, HybridSEQTrainer, train_unsupervised   # noqa: E402
 from reid.evaluator import ATTEvaluator                             # noqa: E402
 from reid.data import RandomPairSamplerForMars                      # noqa: E402
 from grl_amd.synthetic import synth_state_dict, IMAGENET_MEAN, IMAGENET_STD   # noqa: E402
@@ -54,15 +58,18 @@ def tracklets_of(pids, per_cam, cams, first_track=0):
 
 
 class Clips(Dataset):
-    def __init__(self, tracklets, seq_len, seed):
-        self.tracklets, self.seq_len, self.seed = list(tracklets), seq_len, seed
+    """``index=True``: every item ends with its dataset index, as RawVideoDataset(index=True) -- the sample's memory row"""
+
+    def __init__(self, tracklets, seq_len, seed, index=False):
+        self.tracklets, self.seq_len, self.seed, self.index = list(tracklets), seq_len, seed, index
 
     def __len__(self):
         return len(self.tracklets)
 
     def __getitem__(self, i):
         (pid, track), label, cam = self.tracklets[i]
-        return identity_clip(pid, track, self.seq_len, self.seed), label, cam
+        item = (identity_clip(pid, track, self.seq_len, self.seed), label, cam)
+        return item + (torch.tensor(i, dtype=torch.int64),) if self.index else item
 
 
 def main(args):
@@ -86,7 +93,15 @@ def main(args):
     cnn_model, siamese_model, siamese_model_uncorr = (m.to(device) for m in (cnn_model, siamese_model, siamese_model_uncorr))
 
     # the memories are seeded every epoch (reset): the size given here is only a placeholder
-    if args.camera_proxies:
+    if args.camera_proxies and args.hybrid_memory:
+        raise SystemExit('--camera-proxies and --hybrid-memory exclude each other')
+    if args.self_paced is not None and not args.hybrid_memory:
+        raise SystemExit('--self-paced needs --hybrid-memory')
+    if args.hybrid_memory:
+        # one memory row per tracklet, DESIGN.md 4ak: the trainer that keeps the batch's instance indices
+        criterion_corr, criterion_uncorr = (HybridMemoryLoss(2048, temp=args.temp, momentum=args.momentum).to(device)
+                                            for _ in range(2))
+    elif args.camera_proxies:
         # one memory row per (cluster, camera) pair, DESIGN.md 4aj: the trainer that keeps the batch's camera ids
         criterion_corr, criterion_uncorr = (ProxyMemoryLoss(2048, temp=args.temp, momentum=args.momentum, mode=args.mode,
                                                             k_neg=args.k_neg).to(device) for _ in range(2))
@@ -105,7 +120,7 @@ def main(args):
         g['lr'] = args.lr * g.get('lr_mult', 1)
 
     evaluator = ATTEvaluator(cnn_model, siamese_model, only_eval=False)
-    trainer = (CameraSEQTrainer if args.camera_proxies else SEQTrainer)(
+    trainer = (HybridSEQTrainer if args.hybrid_memory else CameraSEQTrainer if args.camera_proxies else SEQTrainer)(
         cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr, criterion_uncorr,
         osp.join(args.logs_dir, 'train_log'))
 
@@ -113,11 +128,13 @@ def main(args):
         return DataLoader(Clips(tracklets, args.seq_len, args.seed), batch_size=8, shuffle=False)
 
     def make_train_loader(relabelled):
-        return DataLoader(Clips(relabelled, args.seq_len, args.seed), batch_size=args.batch_size,
+        return DataLoader(Clips(relabelled, args.seq_len, args.seed, index=args.hybrid_memory), batch_size=args.batch_size,
                           sampler=RandomPairSamplerForMars(relabelled), drop_last=True)
 
     def on_epoch(epoch, labels):
         s = labels.pair_scores(hidden)
+        if args.hybrid_memory:
+            print('epoch {}: {} instances in {} classes'.format(epoch, criterion_corr.num_instances, criterion_corr.num_classes))
         if args.camera_proxies:
             print('epoch {}: {} proxies, inter-camera term {}'.format(epoch, criterion_corr.num_proxies,
                                                                       'on' if criterion_corr.inter_on else 'off'))
@@ -132,7 +149,10 @@ def main(args):
                         min_cluster_size=args.min_cluster_size)
     train_unsupervised(trainer, evaluator, optimizer, train, make_eval_loader, make_train_loader, args.epochs,
                        label_kwargs=label_kwargs, on_epoch=on_epoch, cameras=args.camera_proxies,
-                       inter_from_epoch=args.inter_from_epoch)
+                       inter_from_epoch=args.inter_from_epoch, hybrid=args.hybrid_memory,
+                       self_paced=None if args.self_paced is None else dict(
+                           delta=args.self_paced, method=args.method, eps=args.eps, min_samples=args.min_samples, k1=args.k1,
+                           k2=args.k2))
 
 
 if __name__ == '__main__':
@@ -158,6 +178,10 @@ if __name__ == '__main__':
                     help='camera-aware proxies: ProxyMemoryLoss under CameraSEQTrainer (DESIGN.md 4aj)')
     ap.add_argument('--k-neg', type=int, default=50, help='hardest proxies of other clusters in the inter-camera term')
     ap.add_argument('--inter-from-epoch', type=int, default=0, help='first epoch with the inter-camera term')
+    ap.add_argument('--hybrid-memory', action='store_true',
+                    help='hybrid memory: HybridMemoryLoss under HybridSEQTrainer, noise samples stay in the epoch (DESIGN.md 4ak)')
+    ap.add_argument('--self-paced', type=float, default=None, metavar='DELTA',
+                    help="with --hybrid-memory and --method jaccard / cosine: keep only the clusters stable under eps -/+ DELTA")
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--logs-dir', type=str, default='/tmp/grl_logs')
     main(ap.parse_args())

@@ -13,6 +13,7 @@
 #include "../../include/grl_hip.h"
 #include "common.h"
 #include "sort_order.h"
+#include "ce_finish.h"
 
 namespace {
 
@@ -45,7 +46,7 @@ __device__ __forceinline__ int block_imin(int v, int* red) {
 }
 
 // One workgroup per row.  Every branch on `own`, k, thr or a block total is uniform across the workgroup.  dlogits comes
-// out WITHOUT the 1 / nv of the contract (proxy_finish_kernel applies it): a row does not know the other rows' validity.
+// out WITHOUT the 1 / nv of the contract (ce_finish_kernel applies it): a row does not know the other rows' validity.
 __global__ __launch_bounds__(256) void proxy_ce_kernel(const float* __restrict__ z, int64_t ld,
                                                        const int64_t* __restrict__ labels,
                                                        const int64_t* __restrict__ cams,
@@ -182,25 +183,6 @@ __global__ __launch_bounds__(256) void proxy_ce_kernel(const float* __restrict__
     }
 }
 
-// nv = the valid rows (every workgroup re-derives it from the same flags, serially: n is small); dlogits *= fl(1 / nv);
-// workgroup 0 adds the rows' fl(fl(1 / nv) L_i) and hits in index order.
-__global__ __launch_bounds__(256) void proxy_finish_kernel(const float* __restrict__ rows, int n, int P,
-                                                           float* __restrict__ loss, float* __restrict__ correct,
-                                                           float* __restrict__ dz, int64_t ldd) {
-    float nv = 0.f;
-    for (int r = 0; r < n; ++r) nv += rows[2 * n + r];
-    const float inv = nv > 0.f ? 1.f / nv : 0.f;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-        float s = 0.f, h = 0.f;
-        for (int r = 0; r < n; ++r) { s += inv * rows[r]; h += rows[n + r]; }     // (term by term as grl_softmax_ce's rows)
-        loss[0] = s;
-        if (correct) correct[0] = h;
-    }
-    if (!dz) return;
-    float* d = dz + (int64_t)blockIdx.y * ldd;            // grid: (1024-column blocks, rows)
-    for (int j = blockIdx.x * 1024 + threadIdx.x; j < min(P, (int)(blockIdx.x + 1) * 1024); j += 256) d[j] = inv * d[j];
-}
-
 }  // namespace
 
 extern "C" int grl_proxy_ce(const float* logits, int64_t ld, const int64_t* labels, const int64_t* cams,
@@ -216,7 +198,7 @@ extern "C" int grl_proxy_ce(const float* logits, int64_t ld, const int64_t* labe
     const size_t lds = (size_t)P * sizeof(float) + (size_t)((P + 3) & ~3);
     hipLaunchKernelGGL(proxy_ce_kernel, dim3(n), dim3(256), lds, s, logits, ld, labels, cams, proxy_cluster, proxy_cam, n, P,
                        k_neg, w_intra, w_inter, ws, dlogits, ldd, own, k_neg > 0 ? negsel : nullptr);
-    hipLaunchKernelGGL(proxy_finish_kernel, dlogits ? dim3(grl_ceil_div(P, 1024), n) : dim3(1), dim3(256), 0, s, ws, n, P,
+    hipLaunchKernelGGL(ce_finish_kernel, dlogits ? dim3(grl_ceil_div(P, 1024), n) : dim3(1), dim3(256), 0, s, ws, n, P,
                        loss, correct, dlogits, ldd);
     return grl_check_launch("grl_proxy_ce");
 }

@@ -106,10 +106,11 @@ class RawVideoDataset(Dataset):
     [n_clips,T,3,H,W] -- plus, with ``augment=True`` (training), the int32 block of
     ``augment.draw_clip_params`` that SEQTrainer hands to grl_augment_normalize_u8.  MARS crops are all
     256 x 128; another uniform size is RectScale'd on the device; frames of DIFFERENT sizes (DukeMTMC-VideoReID):
-    see ``host_rect_scale`` below."""
+    see ``host_rect_scale`` below.  With ``index=True`` every item ends with its dataset index (int64, after the
+    augmentation block when there is one): the memory row of the sample for ``HybridSEQTrainer``."""
 
     def __init__(self, tracklets, seq_len=4, sample='rrs_train', augment=False, height=256, width=128, decode='host',
-                 host_rect_scale=False):
+                 host_rect_scale=False, index=False):
         """``decode``: 'host' -- the worker decodes with Pillow (items carry uint8 tensors); 'device' -- the worker only
         reads the files, items carry the JPEG byte strings, the loader uses ``jpeg.jpeg_collate`` and
         engine.DevicePrefetcher decodes the batch on the GPU (grl_jpeg_decode_batch, bit-identical to Pillow).
@@ -121,6 +122,7 @@ class RawVideoDataset(Dataset):
         self.tracklets, self.seq_len, self.sample = list(tracklets), seq_len, sample
         self.augment, self.height, self.width, self.decode = augment, height, width, decode
         self.host_rect_scale = host_rect_scale
+        self.index = index
 
     def __len__(self):
         return len(self.tracklets)
@@ -147,6 +149,8 @@ class RawVideoDataset(Dataset):
                 item = ([read_file(paths[int(i)], keep_path=True) for i in idx], pid, camid)
             if self.augment:
                 item += (torch.tensor(draw_clip_params(self.seq_len, self.height, self.width), dtype=torch.int32),)
+            if self.index:
+                item += (torch.tensor(int(index), dtype=torch.int64),)
             return item
         if self.sample == 'dense':
             clip = torch.stack([torch.stack([self._decode(paths[int(i)]) for i in row]) for row in idx])
@@ -155,4 +159,6 @@ class RawVideoDataset(Dataset):
         item = (clip, pid, camid)
         if self.augment:
             item += (torch.tensor(draw_clip_params(self.seq_len, self.height, self.width), dtype=torch.int32),)
+        if self.index:
+            item += (torch.tensor(int(index), dtype=torch.int64),)
         return item

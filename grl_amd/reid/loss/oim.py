@@ -52,7 +52,10 @@ class OIM(autograd.Function):
         c = lut.size(0)
         scale = torch.full((c,), float(scalar), dtype=torch.float32, device=x.device)
         logits = torch.empty((n, c), dtype=torch.float32, device=x.device)
-        engine.gemm(x, lut, logits, n, c, D, scale=scale, math=MATH_F32, kblock=True)      # (K-blocked: split over K, include/grl_hip.h)
+        # (K-blocked: split over K, include/grl_hip.h.  The GEMM takes K % 32 == 0: another D gets zero columns -- copies, +0 to
+        #  every dot product -- as the engine pads the evaluator's features; D % 32 == 0 hands over x and lut themselves)
+        xk, lk = engine._pad_features(x), engine._pad_features(lut)
+        engine.gemm(xk, lk, logits, n, c, xk.size(1), scale=scale, math=MATH_F32, kblock=True)
         loss = torch.empty((), dtype=torch.float32, device=x.device)
         dlogits = torch.empty_like(logits)
         ws = torch.empty(2 * n, dtype=torch.float32, device=x.device)

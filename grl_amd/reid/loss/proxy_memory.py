@@ -43,7 +43,8 @@ class ProxyMemory(autograd.Function):
         P = mem.size(0)
         scale = torch.full((P,), float(scalar), dtype=torch.float32, device=x.device)
         logits = torch.empty((n, P), dtype=torch.float32, device=x.device)
-        engine.gemm(x, mem, logits, n, P, D, scale=scale, math=MATH_F32, kblock=True)
+        xk, mk = engine._pad_features(x), engine._pad_features(mem)        # (D % 32 != 0: zero columns for the GEMM, as OIM.forward)
+        engine.gemm(xk, mk, logits, n, P, xk.size(1), scale=scale, math=MATH_F32, kblock=True)
         loss = torch.empty((), dtype=torch.float32, device=x.device)
         correct = torch.empty((), dtype=torch.float32, device=x.device)
         dlogits = torch.empty_like(logits)

@@ -1,3 +1,5 @@
 from .trainer import SEQTrainer
 from .camera import CameraSEQTrainer
-from .pseudo import PseudoLabels, ProxyLabels, pseudo_labels, train_unsupervised
+from .hybrid import HybridSEQTrainer
+from .pseudo import (PseudoLabels, ProxyLabels, HybridLabels, SelfPacedState, pseudo_labels, self_paced_labels,
+                     train_unsupervised)

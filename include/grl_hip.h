@@ -591,6 +591,41 @@ int grl_proxy_ce(const float* logits, int64_t ld, const int64_t* labels, const i
                  float w_inter, float* loss, float* correct, float* dlogits, int64_t ldd, int64_t* own,
                  int32_t* negsel, float* ws, void* stream);
 
+/* Hybrid-memory cross entropy of self-paced unsupervised training (hybrid.hip, HybridMemoryLoss; SpCL, Ge
+ * et al. 2020): a cross entropy whose classes are SETS of columns, forward and gradient in one call.  Additive:
+ * GRL_ABI_VERSION stays 10.  logits [n][ld] (N columns used) are the scaled similarities of the n rows to the N rows of an
+ * instance memory; targets int64 [n] is the class of every row.
+ * The classes: class_ptr int32 [C + 1], class_members int32 [N] and inst_class int32 [N] describe a partition of 0 .. N - 1
+ * into C non-empty classes -- the members of class c are class_members[class_ptr[c] .. class_ptr[c + 1]), in ascending
+ * index, and inst_class[j] is the class of column j (the inverse of the two).  The caller validates the tables
+ * (HybridMemoryLoss.reset does); the kernel assumes a valid partition.
+ * A row whose target is outside [0, C) is INVALID: its dlogits row is zeros and it adds nothing to loss or correct.
+ * For a valid row i with target y:
+ *   z_c = (sum of logits[i][j] over the members j of c, added one by one in list order starting from the first member)
+ *         / (float)|c| -- a singleton's z_c is its logit, bit for bit.
+ *   L_i = lse_C(z) - z_y, the lse shifted by the maximum of z;  p = softmax_C(z).
+ * nv = the number of valid rows.  loss[0] = (sum over the valid rows of L_i) / nv, 0 if nv = 0: the terms fl(fl(1 / nv) L_i)
+ * are added in index order from 0, as the rows of grl_softmax_ce.
+ * dlogits[i][j] (may be NULL) = fl(1 / nv) * fl((p_c - [c == y]) / (float)|c|) with c = inst_class[j].
+ * correct[0] (may be NULL) = the number of valid rows whose arg-max CLASS equals y (first class index on ties).
+ * ws: 3 * n floats of scratch.
+ * With C = N singleton classes in identity order, loss, dlogits and correct are grl_softmax_ce's (weight = NULL) bit for bit.
+ * Limits, each refused with GRL_EINVAL before anything is launched: n < 1, N < 1, C < 1, C > N, ld < N, dlogits given and
+ * ldd < N, a NULL logits / targets / class_ptr / class_members / inst_class / loss / ws, C > GRL_HYBRID_MAX_CLASSES (z lives
+ * in LDS next to the reduction scratch, under the 64 KB a workgroup gets without an opt-in; MARS has 8298 training
+ * tracklets).  The logits row stays in global memory: N has no limit of its own.
+ * A NaN logit gives unspecified values, never an access outside the arrays.
+ * Two launches.  First one 256-lane workgroup per row: lane t takes the classes t + 256 k, sums each class's members
+ * through the table (every logit is read once) and keeps z in LDS; max, sum and arg-max are a wave64 xor tree followed by
+ * the four waves' totals in sequence, as grl_softmax_ce; every class's gradient is computed once, then lane t takes the
+ * COLUMNS t + 256 k and writes dlogits through inst_class.  The second launch is grl_proxy_ce's: the rows' losses, hits
+ * and valid flags are added in index order, every workgroup re-derives nv, dlogits is scaled by fl(1 / nv).  No atomics:
+ * the same bits on every run. */
+#define GRL_HYBRID_MAX_CLASSES 15360
+int grl_hybrid_ce(const float* logits, int64_t ld, const int64_t* targets, const int32_t* class_ptr,
+                  const int32_t* class_members, const int32_t* inst_class, int n, int N, int C, float* loss,
+                  float* correct, float* dlogits, int64_t ldd, float* ws, void* stream);
+
 /* ---- the trainer's loss block, forward and backward on the device ---- */
 /* F.cross_entropy of OIMLoss.forward (reid/loss/oim.py:52; mean reduction, optional class
  * weight): loss[0] = sum_i w[y_i] (logsumexp(z_i) - z_i[y_i]) / sum_i w[y_i];
