@@ -9,10 +9,14 @@ The hidden pids are only used to print how good the clusters were.  Run:
     PYTHONPATH=.:dropin python examples/train_unsupervised_synthetic.py --epochs 2 --camera-proxies --k-neg 8 --inter-from-epoch 1
 
     PYTHONPATH=.:dropin python examples/train_unsupervised_synthetic.py --epochs 2 --hybrid-memory --self-paced 0.02
+    PYTHONPATH=.:dropin python examples/train_unsupervised_synthetic.py --epochs 2 --mean-teacher 0.999 --soft-weight 0.5 --eval-teacher
 
 (the second form: camera-aware proxies, one memory row per cluster and camera -- ProxyMemoryLoss under CameraSEQTrainer;
 the third: a hybrid memory with one row per tracklet, the samples the clustering calls noise trained on as classes of their
-own, and only the clusters that are stable under eps -/+ 0.02 kept -- HybridMemoryLoss under HybridSEQTrainer)
+own, and only the clusters that are stable under eps -/+ 0.02 kept -- HybridMemoryLoss under HybridSEQTrainer, DESIGN.md 4ak;
+the fourth: a mean teacher -- an averaged copy of the model whose softmax over the cluster memory is a soft target next to
+the hard cluster id, SoftClusterMemoryLoss under MeanTeacherSEQTrainer, and with --eval-teacher the model that is evaluated
+and clustered with)
 
 Every identity is a low-frequency colour layout ("a person in front of a background", as grl_amd.synthetic.
 synth_clips_structured); a tracklet is a small deviation from its identity's layout, a frame a smaller one, plus pixel noise.
@@ -32,8 +36,9 @@ for p in (ROOT, osp.join(ROOT, 'dropin')):
         sys.path.insert(0, p)
 
 from reid import models                                             # noqa: E402
-from reid.loss import PairLoss, ClusterMemoryLoss, ProxyMemoryLoss, HybridMemoryLoss  # noqa: E402
-from reid.train import SEQTrainer, CameraSEQTrainer, HybridSEQTrainer, train_unsupervised   # noqa: E402
+from reid.loss import PairLoss, ClusterMemoryLoss, ProxyMemoryLoss, HybridMemoryLoss, SoftClusterMemoryLoss  # noqa: E402
+from reid.train import (SEQTrainer, CameraSEQTrainer, HybridSEQTrainer, MeanTeacher, MeanTeacherSEQTrainer,   # noqa: E402
+                        train_unsupervised)
 from reid.evaluator import ATTEvaluator                             # noqa: E402
 from reid.data import RandomPairSamplerForMars                      # noqa: E402
 from grl_amd.synthetic import synth_state_dict, IMAGENET_MEAN, IMAGENET_STD   # noqa: E402
@@ -72,7 +77,21 @@ class Clips(Dataset):
         return item + (torch.tensor(i, dtype=torch.int64),) if self.index else item
 
 
+def refuse_conflicts(args):
+    """SystemExit with a message for flags that exclude each other, before anything is built"""
+    if args.camera_proxies and args.hybrid_memory:
+        raise SystemExit('--camera-proxies and --hybrid-memory exclude each other')
+    if args.self_paced is not None and not args.hybrid_memory:
+        raise SystemExit('--self-paced needs --hybrid-memory')
+    if args.mean_teacher is None and (args.eval_teacher or args.soft_weight is not None):
+        raise SystemExit('--soft-weight and --eval-teacher need --mean-teacher ALPHA')
+    if args.mean_teacher is not None and (args.camera_proxies or args.hybrid_memory):
+        raise SystemExit('--mean-teacher is built for the plain cluster memory: it excludes --camera-proxies and '
+                         '--hybrid-memory (DESIGN.md 4al, out of scope)')
+
+
 def main(args):
+    refuse_conflicts(args)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
     device = torch.device('cuda', 0)
@@ -93,10 +112,6 @@ def main(args):
     cnn_model, siamese_model, siamese_model_uncorr = (m.to(device) for m in (cnn_model, siamese_model, siamese_model_uncorr))
 
     # the memories are seeded every epoch (reset): the size given here is only a placeholder
-    if args.camera_proxies and args.hybrid_memory:
-        raise SystemExit('--camera-proxies and --hybrid-memory exclude each other')
-    if args.self_paced is not None and not args.hybrid_memory:
-        raise SystemExit('--self-paced needs --hybrid-memory')
     if args.hybrid_memory:
         # one memory row per tracklet, DESIGN.md 4ak: the trainer that keeps the batch's instance indices
         criterion_corr, criterion_uncorr = (HybridMemoryLoss(2048, temp=args.temp, momentum=args.momentum).to(device)
@@ -106,8 +121,10 @@ def main(args):
         criterion_corr, criterion_uncorr = (ProxyMemoryLoss(2048, temp=args.temp, momentum=args.momentum, mode=args.mode,
                                                             k_neg=args.k_neg).to(device) for _ in range(2))
     else:
-        criterion_corr = ClusterMemoryLoss(2048, 2, temp=args.temp, momentum=args.momentum, mode=args.mode).to(device)
-        criterion_uncorr = ClusterMemoryLoss(2048, 2, temp=args.temp, momentum=args.momentum, mode=args.mode).to(device)
+        # (with a mean teacher: the criterion that takes the teacher's rows as a soft target)
+        crit = SoftClusterMemoryLoss if args.mean_teacher is not None else ClusterMemoryLoss
+        criterion_corr = crit(2048, 2, temp=args.temp, momentum=args.momentum, mode=args.mode).to(device)
+        criterion_uncorr = crit(2048, 2, temp=args.temp, momentum=args.momentum, mode=args.mode).to(device)
     criterion_veri = PairLoss().to(device)
 
     base_param_ids = set(map(id, cnn_model.backbone.parameters()))
@@ -120,9 +137,18 @@ def main(args):
         g['lr'] = args.lr * g.get('lr_mult', 1)
 
     evaluator = ATTEvaluator(cnn_model, siamese_model, only_eval=False)
-    trainer = (HybridSEQTrainer if args.hybrid_memory else CameraSEQTrainer if args.camera_proxies else SEQTrainer)(
-        cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr, criterion_uncorr,
-        osp.join(args.logs_dir, 'train_log'))
+    if args.mean_teacher is not None:
+        teacher = MeanTeacher(cnn_model, siamese_model, alpha=args.mean_teacher)
+        trainer = MeanTeacherSEQTrainer(cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr,
+                                        criterion_uncorr, osp.join(args.logs_dir, 'train_log'), teacher=teacher,
+                                        soft_weight=0.5 if args.soft_weight is None else args.soft_weight)
+        teacher_evaluator = ATTEvaluator(*teacher.models, only_eval=False)
+        if args.eval_teacher:                                # the teacher's features are clustered, and it is what is scored
+            evaluator, student_evaluator = teacher_evaluator, evaluator
+    else:
+        trainer = (HybridSEQTrainer if args.hybrid_memory else CameraSEQTrainer if args.camera_proxies else SEQTrainer)(
+            cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr, criterion_uncorr,
+            osp.join(args.logs_dir, 'train_log'))
 
     def make_eval_loader(tracklets):
         return DataLoader(Clips(tracklets, args.seq_len, args.seed), batch_size=8, shuffle=False)
@@ -141,6 +167,12 @@ def main(args):
         print('epoch {}: n_clusters {} n_noise {} of {} | against the hidden pids: precision {:.3f} recall {:.3f} F1 {:.3f} '
               'ARI {:.3f} | loss {:.3f}'.format(epoch, labels.n_clusters, labels.n_noise, len(labels), s['precision'],
                                                 s['recall'], s['f1'], s['ari'], trainer.meters['loss'].avg))
+        if args.mean_teacher is not None:
+            print('epoch {}: teacher after {} updates, alpha {}'.format(epoch, teacher.step, teacher.alpha))
+            other = student_evaluator if args.eval_teacher else teacher_evaluator
+            print('the {}:'.format('student' if args.eval_teacher else 'teacher'))
+            other.evaluate(None, None, query_loader, gallery_loader, args.logs_dir, False, False)
+            print('the {}:'.format('teacher' if args.eval_teacher else 'student'))
         evaluator.evaluate(None, None, query_loader, gallery_loader, args.logs_dir, False, False)   # prints Mean AP / Rank-k
 
     print('before training:')
@@ -182,6 +214,12 @@ if __name__ == '__main__':
                     help='hybrid memory: HybridMemoryLoss under HybridSEQTrainer, noise samples stay in the epoch (DESIGN.md 4ak)')
     ap.add_argument('--self-paced', type=float, default=None, metavar='DELTA',
                     help="with --hybrid-memory and --method jaccard / cosine: keep only the clusters stable under eps -/+ DELTA")
+    ap.add_argument('--mean-teacher', type=float, default=None, metavar='ALPHA',
+                    help='mean teacher with this EMA coefficient: SoftClusterMemoryLoss under MeanTeacherSEQTrainer (DESIGN.md 4al)')
+    ap.add_argument('--soft-weight', type=float, default=None, metavar='W',
+                    help="with --mean-teacher: weight of the teacher's softmax in the identity losses (default 0.5)")
+    ap.add_argument('--eval-teacher', action='store_true',
+                    help='with --mean-teacher: evaluate and cluster with the teacher (ATTEvaluator on teacher.models)')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--logs-dir', type=str, default='/tmp/grl_logs')
     main(ap.parse_args())

@@ -57,6 +57,14 @@ class GrlPrepEntry(C.Structure):
                 ('tiled', _i32), ('out_bf16', _i32)]
 
 
+class GrlEmaEntry(C.Structure):
+    """include/grl_hip.h: one (teacher, student) tensor pair of grl_ema_update's device table"""
+    _fields_ = [('dst', _fp), ('src', _fp), ('numel', _i64)]
+
+
+EMA_CHUNK = 4096      # = GRL_EMA_CHUNK
+
+
 class GrlJpegFrame(C.Structure):
     """include/grl_hip.h: one parsed JPEG frame (filled by grl_jpeg_parse on the host, read by the decode kernels)"""
     _fields_ = [('scan_off', C.c_uint32), ('scan_len', C.c_uint32), ('width', C.c_uint16), ('height', C.c_uint16),
@@ -147,6 +155,8 @@ _SIGNATURES = {
     'grl_proxy_ce': ([_fp, _i64, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _fp, _fp, _fp, _i64,
                       _fp, _fp, _fp, _fp], C.c_int),
     'grl_hybrid_ce': ([_fp, _i64, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _i64, _fp, _fp], C.c_int),
+    'grl_soft_ce': ([_fp, _i64, _fp, _i64, _fp, C.c_float, C.c_int, C.c_int, _fp, _fp, _fp, _i64, _fp, _fp], C.c_int),
+    'grl_ema_update': ([_fp, _fp, C.c_int, C.c_float, C.c_float, _fp], C.c_int),
     'grl_softmax_ce': ([_fp, _i64, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _i64, _fp, _fp], C.c_int),
     'grl_oim_grad': ([_fp, _i64, _fp, _fp, C.c_float, _fp, C.c_int, C.c_int, C.c_int, _fp], C.c_int),
     'grl_triplet_fwd': ([_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp, _fp, _fp], C.c_int),

@@ -2,8 +2,9 @@ from .oim import oim, OIM, OIMLoss
 from .cluster_memory import ClusterMemory, ClusterMemoryLoss
 from .proxy_memory import ProxyMemory, ProxyMemoryLoss
 from .hybrid_memory import HybridMemory, HybridMemoryLoss
+from .soft_memory import SoftClusterMemory, SoftClusterMemoryLoss
 from .pairloss import PairLoss
 from .triplet import TripletLoss, TripletLoss_OIM
 
 __all__ = ['oim', 'OIM', 'OIMLoss', 'ClusterMemory', 'ClusterMemoryLoss', 'ProxyMemory', 'ProxyMemoryLoss', 'HybridMemory',
-           'HybridMemoryLoss', 'PairLoss', 'TripletLoss', 'TripletLoss_OIM']
+           'HybridMemoryLoss', 'SoftClusterMemory', 'SoftClusterMemoryLoss', 'PairLoss', 'TripletLoss', 'TripletLoss_OIM']

@@ -337,6 +337,10 @@ def train_unsupervised(trainer, evaluator, optimizer, tracklets, make_eval_loade
     method's knobs (``method``, ``eps``, ``min_samples``, ``k1``, ``k2``, ``metric``); the labels then come from
     ``self_paced_labels(xf, state, **self_paced)`` with one ``SelfPacedState`` for the run, and ``label_kwargs`` is unused.
 
+    A mean teacher needs nothing here: a ``MeanTeacherSEQTrainer`` with two ``SoftClusterMemoryLoss`` goes
+    through the plain branch -- ``reset(centroids)`` is ``ClusterMemoryLoss``'s -- and the caller chooses the model that is
+    clustered by the evaluator it passes: ``ATTEvaluator(*teacher.models)`` clusters with the teacher.
+
     Returns the epochs' ``PseudoLabels``.  Under torch.distributed ``extract_feature`` gathers every row on every rank, so
     all ranks compute the same labels and seed the same memories."""
     tracklets = list(tracklets)

@@ -626,6 +626,60 @@ int grl_hybrid_ce(const float* logits, int64_t ld, const int64_t* targets, const
                   const int32_t* class_members, const int32_t* inst_class, int n, int N, int C, float* loss,
                   float* correct, float* dlogits, int64_t ldd, float* ws, void* stream);
 
+/* Cross entropy against a hard label blended with a teacher's softmax (softce.hip, SoftClusterMemoryLoss, DESIGN.md 4al;
+ * Mean Teacher, Tarvainen & Valpola 2017; MMT, Ge et al. 2020), forward and gradient in one call.  Additive:
+ * GRL_ABI_VERSION stays 10.  logits [n][ld] and tlogits [n][ldt] (c columns used of each) are the student's and the
+ * teacher's scaled similarities to the same c memory rows; labels int64 [n].
+ * A row whose label is outside [0, c) is INVALID: its dlogits row is +0 and it adds nothing to loss or correct.
+ * For a valid row i with label y, z = logits[i], t = tlogits[i], w = w_soft, omw = fl(1 - w):
+ *   mx = max_j z_j;  lse = logf(sum_j expf(z_j - mx));  p_j = expf(fl(fl(z_j - mx) - lse))
+ *   mt = max_j t_j;  lt  = logf(sum_j expf(t_j - mt));  q_j = expf(fl(fl(t_j - mt) - lt))
+ *   X   = sum_j fl(q_j * fl(z_j - mx))
+ *   L_i = fl(fl(lse - fl(omw * fl(z_y - mx))) - fl(w * X))
+ *       = lse(z) - (1 - w) z_y - w sum_j q_j z_j: the cross-entropy form of MMT (not the KL divergence: the two differ by
+ *         the teacher's entropy, a constant in the student), the shift mx cancelling because (1 - w) + w sum_j q_j = 1
+ *   d_ij = fl(fl(p_j - fl(omw * [j == y])) - fl(w * q_j))
+ * With w = 0 the terms in w are not evaluated and tlogits is never read (it may be NULL).
+ * nv = the number of valid rows.  loss[0] = sum over the valid rows of fl(fl(1 / nv) L_i), added in index order from 0
+ * (0 if nv = 0), as the rows of grl_softmax_ce.  dlogits[i][j] (may be NULL) = fl(fl(1 / nv) d_ij).
+ * correct[0] (may be NULL) = the number of valid rows whose arg-max of the STUDENT row is y (first index on ties).
+ * ws: 3 * n floats of scratch.
+ * With w_soft = 0, loss, dlogits and correct are grl_softmax_ce's (weight = NULL) bit for bit.
+ * Limits, each refused with GRL_EINVAL before anything is launched: n < 1, c < 1, ld < c, dlogits given and ldd < c, a
+ * NULL logits / labels / loss / ws, w_soft outside [0, 1] (a NaN included), w_soft != 0 with tlogits NULL or ldt < c.
+ * A NaN logit gives unspecified values, never an access outside the arrays.
+ * Two launches.  First one 256-lane workgroup per row: lane t takes the columns t + 256 k, adding its terms in that
+ * order from 0; every max and sum is a wave64 xor tree followed by the four waves' totals in sequence, as
+ * grl_softmax_ce.  Both rows stay in global memory: c has no limit of its own.  The second launch is grl_proxy_ce's: the
+ * rows' losses, hits and valid flags are added in index order, every workgroup re-derives nv, dlogits is scaled by
+ * fl(1 / nv).  No atomics: the same bits on every run. */
+int grl_soft_ce(const float* logits, int64_t ld, const float* tlogits, int64_t ldt, const int64_t* labels,
+                float w_soft, int n, int c, float* loss, float* correct, float* dlogits, int64_t ldd,
+                float* ws, void* stream);
+
+/* Exponential moving average of a set of tensors in ONE launch (ema.hip, MeanTeacher).  Additive:
+ * GRL_ABI_VERSION stays 10.  table_dev: `count` entries in DEVICE memory, built once per model by the host; for every
+ * entry and every element
+ *   dst[k] = fl(fl(alpha * dst[k]) + fl(one_minus_alpha * src[k]))
+ * (both factors from the host, as lambda_value / one_minus_lambda below; two products and one sum, no fused multiply-add:
+ * a float32 restatement reproduces the bits).  alpha = 0 copies src, alpha = 1 leaves the finite values of dst as they
+ * are (numerically: -0 becomes +0 against a finite positive src), NaN and inf propagate as the formula says.
+ * The tensors are cut into chunks of GRL_EMA_CHUNK = 4096 floats (16 KB of dst and of src: four 16-byte loads of each
+ * per lane, all in flight before the first store).  chunk_first_dev: int64 [count + 1] in device memory,
+ * chunk_first[e] = sum over e' < e of ceil(numel[e'] / GRL_EMA_CHUNK), so chunk_first[count] is the number of chunks.  A
+ * workgroup of 256 lanes finds the entry of its chunk by binary search in chunk_first; the grid is capped (2048
+ * workgroups) and strides over the chunks.  16-byte loads and stores where the chunk's dst and src are both 16-byte
+ * aligned, scalar ones otherwise and for the last numel % 4 floats.  Every element has one writer: no atomics, the same
+ * bits on every run.
+ * The entries are device memory and are NOT validated here: the caller guarantees that every dst / src holds numel
+ * floats, that no dst overlaps another dst or any src, and that chunk_first matches the entries (MeanTeacher checks
+ * what it puts into the table).
+ * GRL_EINVAL, before anything is launched: count < 1, a NULL table_dev, a NULL chunk_first_dev. */
+#define GRL_EMA_CHUNK 4096
+typedef struct GrlEmaEntry { float* dst; const float* src; int64_t numel; } GrlEmaEntry;
+int grl_ema_update(const GrlEmaEntry* table_dev, const int64_t* chunk_first_dev, int count,
+                   float alpha, float one_minus_alpha, void* stream);
+
 /* ---- the trainer's loss block, forward and backward on the device ---- */
 /* F.cross_entropy of OIMLoss.forward (reid/loss/oim.py:52; mean reduction, optional class
  * weight): loss[0] = sum_i w[y_i] (logsumexp(z_i) - z_i[y_i]) / sum_i w[y_i];
