@@ -23,6 +23,7 @@ from . import _lib
 from ._lib import GrlGemm, GrlBneckTail, GrlBneckTailF32, EPI_AFFINE, EPI_NEGDOT, EPI_EUCLID, EPI_SQDIFF, check, ptr, require_device
 
 import contextlib
+import numbers
 import os
 
 from ._lib import MATH_F32, MATH_BF16, MATH_BF16X3, MATH_BF16S, MATH_MXFP8
@@ -1256,7 +1257,6 @@ def verify_metric(siam, col0, beta=1.0):
     accepted as ``metric`` by ``search``, ``rank_metrics_streaming`` (and their sharded forms) and ``verify_dist``; the
     pairs x d tensor of (p - g)^2 is never built.  ValueError: a head with class_num != 2, beta outside
     (0, 1], a negative or unaligned col0, a head width the kernels or the GEMM cannot take."""
-    import numbers
     ncls = siam.classifierlinear.out_features
     if ncls != 2:
         raise ValueError('verify_metric: the head has class_num = %d; the logit difference needs 2' % ncls)
@@ -1305,9 +1305,117 @@ def verify_prob(dist):
 # ----------------------------------------------------------------------------
 SEARCH_BLOCK_BYTES = int(os.environ.get('GRL_SEARCH_BLOCK_BYTES', str(256 << 20)))   # distance block budget
 SEARCH_K_MAX = 1024
+_INT_MAX = 2 ** 31 - 1               # what a C int of the ABI holds
 
 
-class _ColumnBlocks(object):
+def _int_arg(v, lo, hi, what, name, bound=None):
+    """``v`` as an int, or ValueError: an integer (never a bool) in lo..hi; ``hi`` None = no upper limit.  The message
+    names the range as 'in lo..hi', as '>= lo' without ``hi``, or as ``bound`` where the caller words it."""
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < lo or (hi is not None and v > hi):
+        if bound is None:
+            bound = '>= %d' % lo if hi is None else 'in %d..%d' % (lo, hi)
+        raise ValueError('%s: %s must be an integer %s (got %r)' % (what, name, bound, v))
+    return int(v)
+
+
+def _search_k(k, what):
+    """The list length ``k`` of a search as an int, or ValueError: 1 <= k <= SEARCH_K_MAX, not a bool."""
+    if isinstance(k, bool) or not 1 <= int(k) <= SEARCH_K_MAX:
+        raise ValueError('%s: k must be in 1..%d (got %r)' % (what, SEARCH_K_MAX, k))
+    return int(k)
+
+
+def _check_index(index, cls, what):
+    if not isinstance(index, cls):
+        name = cls.__name__
+        raise ValueError('%s: index must be %s %s (got %s)' % (what, 'an' if name[0] in 'AEIOU' else 'a', name,
+                                                               type(index).__name__))
+
+
+def _block_budget(block_bytes):
+    """The bytes one distance block may take: ``block_bytes``, or GRL_SEARCH_BLOCK_BYTES as it stands at the call."""
+    return SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
+
+
+def _block_cols(nq, block_bytes, granule=256):
+    """The default block width: the float32 columns of ``nq`` rows that fit the budget, rounded down to a multiple of
+    ``granule`` and at least one granule; ``granule`` None: as many as fit, unrounded (0 when not even one does)."""
+    cols = _block_budget(block_bytes) // (4 * max(nq, 1))
+    return max(granule, cols // granule * granule) if granule else cols
+
+
+def _block_spans(nq, lo, hi, block_cols=None, block_bytes=None, granule=256):
+    """``(width, spans)``: the columns [lo, hi) cut into blocks of ``block_cols`` (default ``_block_cols``) columns, the
+    last one shorter; the width is at least 1 and at most hi - lo."""
+    if block_cols is None:
+        block_cols = _block_cols(nq, block_bytes, granule)
+    width = max(1, min(int(block_cols), hi - lo))
+    return width, [(c, min(c + width, hi)) for c in range(lo, hi, width)]
+
+
+def _sample_block_cols(n, block_bytes):
+    """The default width of the n x n sample passes (``_SampleBlocks``, ``_JaccardSet``): the multiple of 32 samples whose
+    three buffers fit the budget, and never the whole matrix in one block."""
+    cols = max(32, _block_budget(block_bytes) // (12 * n) // 32 * 32)
+    return min(cols, max(32, -(-n // 64) * 32))
+
+
+class _BlockSource(object):
+    """The block-source contract, which every streamed consumer (``_search_blocks``, ``_rank_blocks``,
+    ``_roc_blocks``, ``_eps_graph_blocks``, ``_mst_blocks``, ``_dist_from_blocks``) relies on.  A source provides
+
+      qf, nq         the query rows (a device tensor: consumers take the device from it) and their number
+      spans          [(c0, c1), ...]: the source's columns in ascending, disjoint blocks
+      block(c0, c1)  the [nq, c1 - c0] float32 distances of one span, a view of the ONE reused buffer ``buf``: valid
+                     until the next ``block`` call, and the consumer may overwrite it
+
+    A block comes back with the same bits every time it is asked for (the two-pass consumers ask twice), and an entry's
+    bits do not depend on the block width: every width gives the full matrix's bits.  ``_cut`` is the one width rule:
+    ``block_cols`` columns, else what fits ``block_bytes`` (``_block_cols``)."""
+
+    def _cut(self, lo, hi, block_cols, block_bytes, granule=256):
+        """``width``, ``spans`` and ``buf`` for the columns [lo, hi); ``nq`` and ``qf`` are set already."""
+        self.width, self.spans = _block_spans(self.nq, lo, hi, block_cols, block_bytes, granule)
+        self.buf = _new((self.nq * self.width,), self.qf) if self.spans and self.nq else None
+
+    def _view(self, n):
+        """the [nq, n] view of the buffer that a block of ``n`` columns is written to"""
+        return self.buf[:self.nq * n].view(self.nq, n)
+
+
+class _TopK(object):
+    """The running top-k lists of ``n`` rows as grl_topk_block keeps them: ``key`` int64 [n, k], the composites (all ones
+    = an empty slot), and ``val`` float32 [n, k] (+inf there)."""
+
+    def __init__(self, n, k, dev):
+        self.n, self.k = n, k
+        self.key = torch.full((n, k), -1, dtype=torch.int64, device=dev)
+        self.val = torch.full((n, k), float('inf'), dtype=torch.float32, device=dev)
+
+    def push(self, d, ld, ncols, c0, cidx=None, ldc=0, junk=None, rows=None):
+        """Merge the block ``d`` (``ncols`` columns, row stride ``ld``; column j is entry ``c0 + j``, or ``cidx[.][j]``
+        with ``cidx`` int32 of row stride ``ldc``, < 0 = skipped) into the lists of all rows, or of ``rows = (q0, q1)``.
+        ``junk``: the arrays of ``_junk_ids`` for all n rows; the block then goes through grl_topk_block_filtered."""
+        key, val, nrows = self.key, self.val, self.n
+        if rows is not None:
+            q0, nrows = rows[0], rows[1] - rows[0]
+            key, val = key[q0:], val[q0:]
+            if junk is not None:
+                junk = (junk[0][q0:], junk[1][q0:], junk[2], junk[3])
+        args = (ptr(d), ld, ptr(cidx), ldc, nrows, ncols, c0, self.k, ptr(key), ptr(val))
+        if junk is None:
+            _call('grl_topk_block', *args)
+        else:
+            _call('grl_topk_block_filtered', *args + (ptr(junk[0]), ptr(junk[1]), ptr(junk[2]), ptr(junk[3])))
+
+    def result(self):
+        """``(dist [n, k] float32, idx [n, k] int64)`` as ``search`` returns them: an empty slot is index -1, +inf."""
+        idx = self.key & 0xffffffff
+        idx[idx == 0xffffffff] = -1
+        return self.val, idx
+
+
+class _ColumnBlocks(_BlockSource):
     """Column blocks D[:, c0:c1] of the distance matrix of ``qf`` against gallery rows [lo, hi) of ``gf``
     ('cosine' = cosin_dist, 'euclidean' = pairwise_distance_tensor), one GEMM per block into one reused
     buffer.  Every entry is computed by the same fma chain as in the full matrix (the GEMM's order does not
@@ -1324,21 +1432,15 @@ class _ColumnBlocks(object):
             vm.check_rows(int(torch.Size(qf.shape[1:]).numel()))
         require_device(qf, 'qf'); require_device(gf, 'gf')
         nq, ng = qf.shape[0], gf.shape[0]
-        self.qf = qf.contiguous().view(nq, -1)
-        self.gf = gf.contiguous().view(ng, -1)
+        self.qf = qf.contiguous().view(nq, torch.Size(qf.shape[1:]).numel())      # (-1 cannot be inferred for 0 rows)
+        self.gf = gf.contiguous().view(ng, torch.Size(gf.shape[1:]).numel())
         if self.qf.shape[1] != self.gf.shape[1]:
             raise ValueError('qf and gf have different feature sizes (%d, %d)' % (self.qf.shape[1], self.gf.shape[1]))
         hi = ng if hi is None else hi
         self.nq, self.ng, self.metric = nq, ng, metric
-        if block_cols is None:
-            budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
-            block_cols = max(256, budget // (4 * max(nq, 1)) // 256 * 256)
-        width = max(1, min(int(block_cols), hi - lo))
-        self.width = width
-        self.spans = [(c, min(c + width, hi)) for c in range(lo, hi, width)]
-        self.buf = _new((nq * width,), self.qf) if self.spans and nq else None
+        self._cut(lo, hi, block_cols, block_bytes)
         self.rn = self.cn = None
-        if metric == 'euclidean' and self.spans:
+        if metric == 'euclidean' and self.spans and nq:
             k = self.qf.shape[1]
             self.rn, self.cn = _new((nq,), self.qf), _new((hi - lo,), self.qf)
             _call('grl_row_sqnorm', ptr(self.qf), ptr(self.rn), nq, k, k)
@@ -1359,7 +1461,7 @@ class _ColumnBlocks(object):
 
     def block(self, c0, c1):
         n, k = c1 - c0, self.qf.shape[1]
-        out = self.buf[:self.nq * n].view(self.nq, n)
+        out = self._view(n)
         if self.qv is not None:
             vm = self.metric
             if vm.full:
@@ -1412,9 +1514,7 @@ def search(qf, gf, k, metric='cosine', exclude=None, block_cols=None, block_byte
     truncated to ``k`` (padded as above when fewer are left), and ``D`` at those indices, bit for bit.  The rule is
     applied on the device while the blocks are ranked (grl_topk_block_filtered); no nq x ng mask is built.
     ``exclude=None`` makes the calls it made before the argument existed."""
-    if not 1 <= int(k) <= SEARCH_K_MAX:
-        raise ValueError('search: k must be in 1..%d (got %r)' % (SEARCH_K_MAX, k))
-    k = int(k)
+    k = _search_k(k, 'search')
     nq, ng = qf.shape[0], gf.shape[0]
     junk = _junk_ids(exclude, nq, ng, qf.device)
     lo, hi, sharded = _shard(ng)
@@ -1423,38 +1523,71 @@ def search(qf, gf, k, metric='cosine', exclude=None, block_cols=None, block_byte
 
 
 def _search_blocks(blocks, nq, k, sharded, junk=None):
-    """The running top-k of search over a block source (``spans``, ``block(c0, c1)``, ``qf``).  ``junk``: the
-    device arrays of _junk_ids; every distance block then goes through grl_topk_block_filtered.  The merge of the
-    ranks' lists stays unfiltered: its inputs are clean already."""
-    dev = blocks.qf.device
-    run_key = torch.full((nq, k), -1, dtype=torch.int64, device=dev)          # all-ones composite = empty slot
-    run_val = torch.full((nq, k), float('inf'), dtype=torch.float32, device=dev)
+    """The running top-k of search over a block source (``_BlockSource``).  ``junk``: the device arrays of _junk_ids;
+    every distance block then goes through grl_topk_block_filtered.  The merge of the ranks' lists stays unfiltered: its
+    inputs are clean already."""
+    top = _TopK(nq, k, blocks.qf.device)
     if nq == 0:
-        return run_val, run_key
+        return top.result()
     for c0, c1 in blocks.spans:
-        d = blocks.block(c0, c1)
-        if junk is None:
-            _call('grl_topk_block', ptr(d), c1 - c0, None, 0, nq, c1 - c0, c0, k, ptr(run_key), ptr(run_val))
-        else:
-            _call('grl_topk_block_filtered', ptr(d), c1 - c0, None, 0, nq, c1 - c0, c0, k, ptr(run_key), ptr(run_val),
-                  ptr(junk[0]), ptr(junk[1]), ptr(junk[2]), ptr(junk[3]))
+        top.push(blocks.block(c0, c1), c1 - c0, c1 - c0, c0, junk=junk)
     if sharded:
         import torch.distributed as tdist
         from . import dist as grl_dist
         world = tdist.get_world_size()
-        vals = [torch.empty_like(run_val) for _ in range(world)]
-        keys = [torch.empty_like(run_key) for _ in range(world)]
-        grl_dist._all_gather(vals, run_val)
-        grl_dist._all_gather(keys, run_key)
+        vals = [torch.empty_like(top.val) for _ in range(world)]
+        keys = [torch.empty_like(top.key) for _ in range(world)]
+        grl_dist._all_gather(vals, top.val)
+        grl_dist._all_gather(keys, top.key)
         cand_v = torch.cat(vals, 1).contiguous()                         # rank order; the merge is order-free
         cand_i = (torch.cat(keys, 1) & 0xffffffff).to(torch.int32).contiguous()   # empty slots: -1 = skipped
-        run_key.fill_(-1)
-        run_val.fill_(float('inf'))
-        _call('grl_topk_block', ptr(cand_v), world * k, ptr(cand_i), world * k, nq, world * k, 0, k, ptr(run_key),
-              ptr(run_val))
-    idx = run_key & 0xffffffff
-    idx[idx == 0xffffffff] = -1
-    return run_val, idx
+        top.key.fill_(-1)
+        top.val.fill_(float('inf'))
+        top.push(cand_v, world * k, world * k, 0, cand_i, world * k)
+    return top.result()
+
+
+def _dist_from_blocks(blocks, n):
+    """The materialised [nq, n] matrix of a block source over the columns [0, n)."""
+    out = _new((blocks.nq, n), blocks.qf)
+    if blocks.nq:
+        for c0, c1 in blocks.spans:
+            out[:, c0:c1] = blocks.block(c0, c1)
+    return out
+
+
+def _search_by_query_rows(make_blocks, qf, rows, k, junk):
+    """``_search_blocks`` (unsharded) over ``make_blocks(qf[q0:q1])`` for chunks of ``rows`` query rows, whose results
+    are independent and concatenated: for sources that keep per-query state (tables) within a byte limit."""
+    nq = qf.shape[0]
+    dist, idx = [], []
+    for q0 in range(0, max(nq, 1), rows):
+        q1 = min(q0 + rows, nq)
+        blocks = make_blocks(qf[q0:q1])
+        j = None if junk is None else (junk[0][q0:q1], junk[1][q0:q1], junk[2], junk[3])
+        dv, di = _search_blocks(blocks, q1 - q0, k, False, j)
+        dist.append(dv)
+        idx.append(di)
+    return (dist[0], idx[0]) if len(dist) == 1 else (torch.cat(dist), torch.cat(idx))
+
+
+def _metrics_from_blocks(blocks, nq, ng, q_pids, g_pids, q_camids, g_camids, max_rank, sharded):
+    """(cmc[max_rank] float32, mAP float) of the distances of a block source: the tail of every *_metrics_streaming."""
+    first, nhit, ap = _rank_blocks(blocks, nq, ng, q_pids, g_pids, q_camids, g_camids, sharded)
+    return _cmc_map(first, nhit, ap, ng, max_rank)
+
+
+def _two_stage(what, qf, index, d, metric, store, k, R, shortlist, block_bytes):
+    """The checks of a two-stage search that all indexes share (the store is a RefineStore of the index's rows, 1 <= k <=
+    R <= 1024), then ``refine_lists`` on the index lists of ``shortlist(R)``, the first stage's (dist, idx)."""
+    if not isinstance(store, RefineStore):
+        raise ValueError('%s: store must be a RefineStore (got %s)' % (what, type(store).__name__))
+    if store.n != index.n or store.d != d:
+        raise ValueError('%s: store must hold the rows of the index: store is [%d, %d], the index [%d, %d]'
+                         % (what, store.n, store.d, index.n, d))
+    k = _int_arg(k, 1, SEARCH_K_MAX, what, 'k')
+    R = _int_arg(R, k, SEARCH_K_MAX, what, 'R (k <= R <= %d)' % SEARCH_K_MAX)
+    return refine_lists(qf, store, shortlist(R)[1], k, metric, block_bytes)
 
 
 # ----------------------------------------------------------------------------
@@ -1465,7 +1598,6 @@ EXPAND_ALPHA_MAX = 8
 
 def _expand_args(m, alpha, m_max, what):
     """(m, alpha) as ints, or ValueError: 1 <= m <= m_max, 0 <= alpha <= 8, both integers."""
-    import numbers
     for name, v in (('m', m), ('alpha', alpha)):
         if isinstance(v, bool) or not isinstance(v, numbers.Integral):
             raise ValueError('%s: %s must be an integer (got %r)' % (what, name, v))
@@ -1556,8 +1688,7 @@ def _rank_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, metric='cosine',
 
 
 def _rank_blocks(blocks, nq, ng, q_pids, g_pids, q_camids, g_camids, sharded):
-    """The two passes of _rank_streaming over a block source (``spans``, ``block(c0, c1)``, ``qf``); a block
-    must come back with the same bits every time it is asked for."""
+    """The two passes of _rank_streaming over a block source (``_BlockSource``: a block is asked for twice)."""
     import numpy as np
     from . import dist as grl_dist
     dev = blocks.qf.device
@@ -1619,10 +1750,7 @@ ROC_FPR_TARGETS = (1e-4, 1e-3, 1e-2, 1e-1)
 
 
 def _roc_bits(bits, what):
-    import numbers
-    if isinstance(bits, bool) or not isinstance(bits, numbers.Integral) or not ROC_BITS_MIN <= bits <= ROC_BITS_MAX:
-        raise ValueError('%s: bits must be an integer in %d..%d (got %r)' % (what, ROC_BITS_MIN, ROC_BITS_MAX, bits))
-    return int(bits)
+    return _int_arg(bits, ROC_BITS_MIN, ROC_BITS_MAX, what, 'bits')
 
 
 class PairRoc(object):
@@ -1730,8 +1858,7 @@ def _pair_hist_block(d, c0, ids, bits, pos, neg):
 
 
 def _roc_blocks(blocks, nq, ng, q_pids, g_pids, q_camids, g_camids, bits, sharded):
-    """The histogram pass of pair_roc over a block source (``spans``, ``block(c0, c1)``, ``qf``): one block, one
-    launch.  Under sharding every rank has counted its own gallery columns; the sum is the whole."""
+    """The histogram pass of pair_roc over a block source (``_BlockSource``): one block, one launch.  Under sharding every rank has counted its own gallery columns; the sum is the whole."""
     bits = _roc_bits(bits, 'pair ROC')
     dev = blocks.qf.device
     ids = (_ids(q_pids, nq, 'q_pids', dev), _ids(q_camids, nq, 'q_camids', dev), _ids(g_pids, ng, 'g_pids', dev),
@@ -1796,7 +1923,6 @@ CLUSTER_ROUND_BATCH = 4                    # component rounds enqueued per read-
 
 def _cluster_eps(eps, what):
     """eps as the float32 the kernel compares with (a Python float; +inf stays +inf and means FLT_MAX there)."""
-    import numbers
     import numpy as np
     if isinstance(eps, bool) or not isinstance(eps, numbers.Real) or eps != eps:
         raise ValueError('%s: eps must be a number and not NaN (got %r)' % (what, eps))
@@ -1805,10 +1931,7 @@ def _cluster_eps(eps, what):
 
 
 def _cluster_min_samples(m, what):
-    import numbers
-    if isinstance(m, bool) or not isinstance(m, numbers.Integral) or not 1 <= m <= 2 ** 31 - 1:
-        raise ValueError('%s: min_samples must be an integer >= 1 (got %r)' % (what, m))
-    return int(m)
+    return _int_arg(m, 1, _INT_MAX, what, 'min_samples', '>= 1')
 
 
 class Clustering(object):
@@ -1880,8 +2003,7 @@ def _pair_scores(labels, n_clusters, pids):
 
 
 def _eps_graph_blocks(blocks, n, eps, max_edges=None):
-    """``eps_graph`` over any block source (``spans``, ``block(c0, c1)`` -> the [n, c1 - c0] columns of the n x n
-    distance matrix, ``qf``): count pass, grl_rrs_scan, one read-back of E = row_ptr[n], fill pass."""
+    """``eps_graph`` over any block source (``_BlockSource``) of the n x n distance matrix, asked for twice: count pass, grl_rrs_scan, one read-back of E = row_ptr[n], fill pass."""
     eps = _cluster_eps(eps, 'eps_graph')
     limit = CLUSTER_MAX_EDGES if max_edges is None else int(max_edges)
     dev = blocks.qf.device
@@ -1942,7 +2064,6 @@ def cluster_from_graph(row_ptr, col, n, min_samples=1, eps=None, _checked=False)
     jumping; the host reads one flag word per ``CLUSTER_ROUND_BATCH`` rounds and raises RuntimeError beyond n + 1
     rounds.  ``eps`` is only recorded.  Not sharded: every rank computes the full result.  ValueError: a malformed
     CSR, a bool or non-integer ``min_samples``."""
-    import numbers
     min_samples = _cluster_min_samples(min_samples, 'cluster_from_graph')
     if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 0:
         raise ValueError('cluster_from_graph: n must be an integer >= 0 (got %r)' % (n,))
@@ -2039,10 +2160,7 @@ KMEANS_REDUCE = {'sum': 0, 'mean': 1, 'unit': 2}         # GRL_KMEANS_SUM / _MEA
 
 
 def _kmeans_int(v, lo, what, name):
-    import numbers
-    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= 2 ** 31 - 1:
-        raise ValueError('%s: %s must be an integer >= %d (got %r)' % (what, name, lo, v))
-    return int(v)
+    return _int_arg(v, lo, _INT_MAX, what, name, '>= %d' % lo)
 
 
 def _kmeans_rows(xf, what):
@@ -2060,13 +2178,11 @@ def _kmeans_top1(xf, centroids, metric, block_cols, block_bytes):
     (the composites) and ``run_val`` float32 [n].  Unsharded: every rank assigns every sample."""
     blocks = _ColumnBlocks(xf, centroids, metric, block_cols, block_bytes)
     n = blocks.nq
-    run_key = torch.full((n, 1), -1, dtype=torch.int64, device=xf.device)
-    run_val = torch.full((n, 1), float('inf'), dtype=torch.float32, device=xf.device)
+    top = _TopK(n, 1, xf.device)
     if n:
         for c0, c1 in blocks.spans:
-            d = blocks.block(c0, c1)
-            _call('grl_topk_block', ptr(d), c1 - c0, None, 0, n, c1 - c0, c0, 1, ptr(run_key), ptr(run_val))
-    return run_key.view(n), run_val.view(n)
+            top.push(blocks.block(c0, c1), c1 - c0, c1 - c0, c0)
+    return top.key.view(n), top.val.view(n)
 
 
 def _kmeans_relabel(run_key, run_val, k, prev_labels=None):
@@ -2195,7 +2311,6 @@ class KMeans(object):
 
 def _kmeans_init(xf, k, init, seed):
     """C0 [k, d] as a fresh device tensor: a [k, d] tensor as it is, k distinct sample indices, or 'random'."""
-    import numbers
     import numpy as np
     n, d = xf.shape
     if torch.is_tensor(init) and init.dim() == 2:
@@ -2281,9 +2396,7 @@ class _SampleBlocks(object):
         self.nq, self.ng, self.N = nq, ng, nq + ng
         hi = self.N if hi is None else hi
         if block_cols is None:
-            budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
-            block_cols = max(32, budget // (12 * self.N) // 32 * 32)
-            block_cols = min(block_cols, max(32, -(-self.N // 64) * 32))          # never the whole N x N matrix
+            block_cols = _sample_block_cols(self.N, block_bytes)
         self.width = w = max(1, min(int(block_cols), hi - lo))
         self.spans = [(i, min(i + w, hi)) for i in range(lo, hi, w)]
         self.qq = _ColumnBlocks(qf, qf, 'euclidean', block_cols=min(w, nq))
@@ -2355,16 +2468,14 @@ class _Rerank(object):
         # pass A1, owned samples: colmax and the first K entries of every D row (grl_row_argsort's order).  A
         # sample's colmax is the maximum over its whole column of S, which its owner holds: gathered, never reduced
         self.colmax = torch.empty(N, dtype=torch.float32, device=dev)
-        run_key = torch.full((hi - lo, K), -1, dtype=torch.int64, device=dev)
-        run_val = torch.full((hi - lo, K), float('inf'), dtype=torch.float32, device=dev)
+        top = _TopK(hi - lo, K, dev)
         for i0, i1 in sb.spans:
-            dr = sb.d_rows(i0, i1, self.colmax)
-            _call('grl_topk_block', ptr(dr), N, None, 0, i1 - i0, N, 0, K, ptr(run_key[i0 - lo:]), ptr(run_val[i0 - lo:]))
+            top.push(sb.d_rows(i0, i1, self.colmax), N, N, 0, rows=(i0 - lo, i1 - lo))
         sb.drows = None
-        del run_val
+        top.val = None
         self.rank = torch.empty((N, K), dtype=torch.int32, device=dev)
-        self.rank[lo:hi] = run_key & 0xffffffff
-        del run_key
+        self.rank[lo:hi] = top.key & 0xffffffff
+        del top
         if sharded:
             grl_dist.gather_row_ranges(self.colmax, bounds)
             grl_dist.gather_row_ranges(self.rank, bounds)
@@ -2430,9 +2541,7 @@ class _RerankBlocks(object):
 
     def __init__(self, qf, gf, rr, block_cols=None, block_bytes=None):
         if block_cols is None:                      # as _ColumnBlocks, but never the whole q x g matrix in one block
-            budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
-            block_cols = max(256, budget // (4 * rr.nq) // 256 * 256)
-            block_cols = min(block_cols, max(256, -(-rr.ng // 512) * 256))
+            block_cols = min(_block_cols(rr.nq, block_bytes), max(256, -(-rr.ng // 512) * 256))
         lo, hi, _ = _shard(rr.ng)                   # under torch.distributed: gallery columns sharded as in search
         self.cos = _ColumnBlocks(qf, gf, 'cosine', block_cols, lo=lo, hi=hi)
         self.spans, self.qf, self.rr = self.cos.spans, self.cos.qf, rr
@@ -2455,11 +2564,10 @@ def rerank_search(qf, gf, k, k1=20, k2=6, lambda_value=0.3, exclude=None, block_
     gallery entries of query q's pid AND camera deleted, truncated to ``k``, and F at those indices, bit for bit.
     Only the ranking of the re-ranked blocks is filtered; the K-nearest lists behind the k-reciprocal sets are
     not, as the reference's re_ranking knows nothing of junk, so F itself does not depend on ``exclude``."""
-    if not 1 <= int(k) <= SEARCH_K_MAX:
-        raise ValueError('rerank_search: k must be in 1..%d (got %r)' % (SEARCH_K_MAX, k))
+    k = _search_k(k, 'rerank_search')
     junk = _junk_ids(exclude, qf.shape[0], gf.shape[0], qf.device)
     rr = _Rerank(qf, gf, k1, k2, lambda_value, block_cols, block_bytes)
-    return _search_blocks(_RerankBlocks(qf, gf, rr, block_cols, block_bytes), rr.nq, int(k), rr.sharded, junk)
+    return _search_blocks(_RerankBlocks(qf, gf, rr, block_cols, block_bytes), rr.nq, k, rr.sharded, junk)
 
 
 def rerank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, k1=20, k2=6, lambda_value=0.3, max_rank=100,
@@ -2470,9 +2578,8 @@ def rerank_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, k1=20, 
     final pass with rank_metrics_streaming's exchange (match keys and rank histograms); first hit, #matches and the
     CMC are the single-process values on every rank, the mAP within the same 1e-12."""
     rr = _Rerank(qf, gf, k1, k2, lambda_value, block_cols, block_bytes)
-    first, nhit, ap = _rank_blocks(_RerankBlocks(qf, gf, rr, block_cols, block_bytes), rr.nq, rr.ng, q_pids, g_pids,
-                                   q_camids, g_camids, rr.sharded)
-    return _cmc_map(first, nhit, ap, rr.ng, max_rank)
+    return _metrics_from_blocks(_RerankBlocks(qf, gf, rr, block_cols, block_bytes), rr.nq, rr.ng, q_pids, g_pids,
+                                q_camids, g_camids, max_rank, rr.sharded)
 
 
 def rerank_pair_roc(qf, gf, q_pids, g_pids, q_camids, g_camids, k1=20, k2=6, lambda_value=0.3, bits=ROC_BITS_DEFAULT,
@@ -2493,7 +2600,6 @@ def _jaccard_args(xf, eps, k1, k2, what):
     """The checks of ``jaccard_graph`` / ``cluster_jaccard``, all before any device work: (n, eps as the float32 the
     kernel compares with, k1, k2)."""
     import math
-    import numbers
     import numpy as np
     if not (torch.is_tensor(xf) and xf.is_cuda and xf.dtype == torch.float32 and xf.dim() == 2):
         raise ValueError('%s: xf must be a 2-d float32 tensor [n, d] on a HIP device (got %s)'
@@ -2543,9 +2649,7 @@ class _JaccardSet(object):
         n = xf.shape[0]
         self.n, self.k1, self.k2, self.K = n, k1, k2, max(k1 + 1, k2)
         if block_cols is None:
-            budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
-            block_cols = max(32, budget // (12 * n) // 32 * 32)
-            block_cols = min(block_cols, max(32, -(-n // 64) * 32))               # never the whole n x n matrix
+            block_cols = _sample_block_cols(n, block_bytes)
         self.width = w = max(1, min(int(block_cols), n))
         spans = [(i, min(i + w, n)) for i in range(0, n, w)]
         xf = _pad_features(xf)
@@ -2557,15 +2661,15 @@ class _JaccardSet(object):
             return ptr(s), i1 - i0, ptr(s[1:]), i1 - i0, 1, 1, n - 1, i1 - i0
         # pass A1: colmax and the first K entries of every D row (grl_topk_block's order)
         self.colmax = torch.empty(n, dtype=torch.float32, device=dev)
-        run_key = torch.full((n, K), -1, dtype=torch.int64, device=dev)
-        run_val = torch.full((n, K), float('inf'), dtype=torch.float32, device=dev)
+        top = _TopK(n, K, dev)
         drows = _new((w * n,), cb.qf)
         for i0, i1 in spans:
             _call('grl_rrs_segment_rows', *segment(i0, i1) + (ptr(self.colmax[i0:]), ptr(drows), n))
-            _call('grl_topk_block', ptr(drows), n, None, 0, i1 - i0, n, 0, K, ptr(run_key[i0:]), ptr(run_val[i0:]))
-        del drows, run_val
-        self.rank = (run_key & 0xffffffff).to(torch.int32)
-        del run_key
+            top.push(drows, n, n, 0, rows=(i0, i1))
+        del drows
+        top.val = None
+        self.rank = (top.key & 0xffffffff).to(torch.int32)
+        del top
         # expansion lists, then pass A2: their weights
         self.lcnt = torch.empty(n, dtype=torch.int32, device=dev)
         self.lidx = torch.empty((n, RERANK_LMAX), dtype=torch.int32, device=dev)
@@ -2710,10 +2814,7 @@ def _silhouette_labels(labels, n, noise, what):
 
 
 def _silhouette_width(n, m, block_cols, block_bytes):
-    if block_cols is None:
-        budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
-        block_cols = max(256, budget // (4 * max(n, 1)) // 256 * 256)
-    return max(1, min(int(block_cols), m))
+    return _block_spans(n, 0, m, block_cols, block_bytes)[0]
 
 
 def _silhouette_pass(block, n, width, cl, rinv, metric, noise):
@@ -2889,13 +2990,6 @@ class Hdbscan(object):
         return silhouette(xf, self.labels, metric, noise)
 
 
-def _hdbscan_int(v, lo, hi, what, name):
-    import numbers
-    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= hi:
-        raise ValueError('%s: %s must be an integer in %d..%d (got %r)' % (what, name, lo, hi, v))
-    return int(v)
-
-
 def _hdbscan_method(method, what):
     if method not in HDBSCAN_METHODS:
         raise ValueError("%s: method must be 'eom' or 'leaf' (got %r)" % (what, method))
@@ -2903,12 +2997,12 @@ def _hdbscan_method(method, what):
 
 def _hdbscan_args(min_cluster_size, min_samples, method, what):
     """(min_cluster_size, min_samples) as ints: the checks that need neither the device nor n."""
-    mcs = _hdbscan_int(min_cluster_size, 2, 2 ** 31 - 1, what, 'min_cluster_size')
+    mcs = _int_arg(min_cluster_size, 2, _INT_MAX, what, 'min_cluster_size')
     ms = mcs if min_samples is None else min_samples
     if min_samples is None and ms > SEARCH_K_MAX:
         raise ValueError('%s: min_samples defaults to min_cluster_size = %d, beyond %d; give min_samples' %
                          (what, ms, SEARCH_K_MAX))
-    ms = _hdbscan_int(ms, 1, SEARCH_K_MAX, what, 'min_samples')
+    ms = _int_arg(ms, 1, SEARCH_K_MAX, what, 'min_samples')
     _hdbscan_method(method, what)
     return mcs, ms
 
@@ -2926,22 +3020,21 @@ def _hdbscan_core_dist(blocks, n, min_samples, rinv):
     if min_samples == 1:
         return torch.zeros(n, dtype=torch.float32, device=dev)
     k = min_samples
-    run_key = torch.full((n, k), -1, dtype=torch.int64, device=dev)
-    run_val = torch.full((n, k), float('inf'), dtype=torch.float32, device=dev)
+    top = _TopK(n, k, dev)
     for c0, c1 in blocks.spans:
         d = blocks.block(c0, c1)
         if rinv is not None:
             _call('grl_hdbscan_cosine_block', ptr(d), d.stride(0), n, n, 0, c0, c1 - c0, ptr(rinv))
-        _call('grl_topk_block', ptr(d), d.stride(0), None, 0, n, c1 - c0, c0, k, ptr(run_key), ptr(run_val))
-    idx = run_key & 0xffffffff
+        top.push(d, d.stride(0), c1 - c0, c0)
+    idx = top.key & 0xffffffff
     own = (idx == torch.arange(n, device=dev).unsqueeze(1)) & (torch.arange(k, device=dev) < k - 1).unsqueeze(0)
     # the sample is in its list before the last place: the last entry stays; otherwise the last one goes
-    return torch.where(own.any(1), run_val[:, k - 1], run_val[:, k - 2]).contiguous()
+    return torch.where(own.any(1), top.val[:, k - 1], top.val[:, k - 2]).contiguous()
 
 
 def _mst_blocks(blocks, n, min_samples, rinv):
-    """``mutual_reachability_mst`` over any block source (``spans``, ``block(c0, c1)`` -> the [n, c1 - c0] columns of
-    the n x n distance matrix, ``qf``); ``rinv``: the factors of the cosine form when the blocks hold -dot."""
+    """``mutual_reachability_mst`` over any block source (``_BlockSource``) of the n x n distance matrix;
+    ``rinv``: the factors of the cosine form when the blocks hold -dot."""
     import numpy as np
     dev = blocks.qf.device
     prinv = ptr(rinv) if rinv is not None else None
@@ -3036,7 +3129,7 @@ def mutual_reachability_mst(xf, min_samples, metric='cosine', block_cols=None, b
     torch.distributed every rank computes the full, identical result.  ValueError: a ``verify_metric``, an unknown
     metric, ``min_samples`` outside 1..min(n, 1024) or not an integer."""
     _cluster_metric(metric, 'mutual_reachability_mst')
-    min_samples = _hdbscan_int(min_samples, 1, SEARCH_K_MAX, 'mutual_reachability_mst', 'min_samples')
+    min_samples = _int_arg(min_samples, 1, SEARCH_K_MAX, 'mutual_reachability_mst', 'min_samples')
     if not torch.is_tensor(xf) or xf.dim() < 2:
         raise ValueError('mutual_reachability_mst: xf must be a tensor [n, d] (got %s)'
                          % (tuple(xf.shape) if torch.is_tensor(xf) else type(xf).__name__,))
@@ -3176,9 +3269,8 @@ def hdbscan_from_mst(lo, hi, w, n, min_cluster_size, method='eom'):
     allow_single_cluster=False); with two or more, each is a selectable cluster born at lambda = 0; smaller components
     are noise.  ValueError: arrays that are not E edges with 0 <= lo < hi < n, edges that close a cycle,
     ``min_cluster_size`` < 2, an unknown method."""
-    import numbers
     import numpy as np
-    mcs = _hdbscan_int(min_cluster_size, 2, 2 ** 31 - 1, 'hdbscan_from_mst', 'min_cluster_size')
+    mcs = _int_arg(min_cluster_size, 2, _INT_MAX, 'hdbscan_from_mst', 'min_cluster_size')
     _hdbscan_method(method, 'hdbscan_from_mst')
     if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 0:
         raise ValueError('hdbscan_from_mst: n must be an integer >= 0 (got %r)' % (n,))
@@ -3278,7 +3370,6 @@ class Tsne(object):
 
 def _tsne_real(v, what, name):
     import math
-    import numbers
     if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v):
         raise ValueError('%s: %s must be a finite number (got %r)' % (what, name, v))
     return float(v)
@@ -3311,10 +3402,8 @@ def _tsne_rows(xf, perplexity, metric, what):
 
 def _tsne_optimiser(n_iter, learning_rate, early_exaggeration, exaggeration_iter, seed, init, n, what):
     """The optimiser arguments checked without device work: (n_iter, lr or None for 'auto', alpha, switch, seed)."""
-    import numbers
-    for v, name, lo in ((n_iter, 'n_iter', 1), (exaggeration_iter, 'exaggeration_iter', 0)):
-        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < lo:
-            raise ValueError('%s: %s must be an integer >= %d (got %r)' % (what, name, lo, v))
+    n_iter = _int_arg(n_iter, 1, None, what, 'n_iter')
+    exaggeration_iter = _int_arg(exaggeration_iter, 0, None, what, 'exaggeration_iter')
     lr = None
     if not (isinstance(learning_rate, str) and learning_rate == 'auto'):
         lr = _tsne_real(learning_rate, what, 'learning_rate')
@@ -3334,7 +3423,7 @@ def _tsne_optimiser(n_iter, learning_rate, early_exaggeration, exaggeration_iter
         seed = int(seed)
     else:
         raise ValueError("%s: init must be 'random' or a float32 [n, 2] device tensor (got %r)" % (what, init))
-    return int(n_iter), lr, alpha, int(exaggeration_iter), seed
+    return n_iter, lr, alpha, exaggeration_iter, seed
 
 
 def _tsne_csr(row_ptr, col, val, isolated, what, checked=False):
@@ -3392,26 +3481,24 @@ def tsne_affinities(xf, perplexity=30.0, metric='cosine', block_cols=None, block
         sq, rinv = _new((n,), xf), _new((n,), xf)
         _call('grl_row_sqnorm', ptr(xf), ptr(sq), n, d, d)
         _call('grl_silhouette_rinv', ptr(sq), n, ptr(rinv))
-    k = K + 1
-    run_key = torch.full((n, k), -1, dtype=torch.int64, device=dev)
-    run_val = torch.full((n, k), float('inf'), dtype=torch.float32, device=dev)
+    top = _TopK(n, K + 1, dev)
     for c0, c1 in blocks.spans:
         d = blocks.block(c0, c1)
         if rinv is not None:
             _call('grl_hdbscan_cosine_block', ptr(d), d.stride(0), n, n, 0, c0, c1 - c0, ptr(rinv))
         else:
             _call('grl_tsne_square_block', ptr(d), d.stride(0), n, c1 - c0)
-        _call('grl_topk_block', ptr(d), d.stride(0), None, 0, n, c1 - c0, c0, k, ptr(run_key), ptr(run_val))
+        top.push(d, d.stride(0), c1 - c0, c0)
     del blocks
     # the sample's own entry goes, or the last one when it is not in the list
-    idx = run_key & 0xffffffff
+    idx = top.key & 0xffffffff
     own = idx == torch.arange(n, device=dev).unsqueeze(1)
     drop = torch.where(own.any(1), own.to(torch.int32).argmax(1), torch.full((n,), K, dtype=torch.int64, device=dev))
     take = torch.arange(K, device=dev).unsqueeze(0)
     take = take + (take >= drop.unsqueeze(1)).to(torch.int64)
-    e = run_val.gather(1, take).contiguous()
+    e = top.val.gather(1, take).contiguous()
     idx = idx.gather(1, take).to(torch.int32).contiguous()
-    del run_key, run_val
+    del top
     cond = torch.empty((n, K), dtype=torch.float32, device=dev)
     beta = torch.empty(n, dtype=torch.float32, device=dev)
     iso = torch.empty(n, dtype=torch.uint8, device=dev)
@@ -3523,7 +3610,6 @@ def tsne_from_affinities(row_ptr, col, val, n_iter=1000, seed=0, init='random', 
     or more iterations cost no distance pass.  The arguments are ``tsne``'s.  ``init`` = an earlier run's ``embedding``
     (with its NaN rows replaced), ``gains`` / ``update`` its state and ``first_iter`` the iterations it ran continue that
     run bit for bit.  Returns a ``Tsne`` (``perplexity``, ``metric`` and ``beta`` are None)."""
-    import numbers
     what = 'tsne_from_affinities'
     n, iso = _tsne_csr(row_ptr, col, val, isolated, what, checked=True)            # (the checks without device work first)
     n_iter, lr, alpha, switch, seed = _tsne_optimiser(n_iter, learning_rate, early_exaggeration, exaggeration_iter, seed,
@@ -3600,13 +3686,6 @@ def _pca_tail(L, dev):
     tail = torch.zeros(16 + _pad32(L), dtype=torch.int32, device=dev)
     tail[:5] = torch.tensor([0x7f800000, 0, -1, -1, 0], dtype=torch.int32)      # {+inf, no failure, no index, no call, 0 calls}
     return tail
-
-
-def _pca_int(v, lo, what, name):
-    import numbers
-    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < lo:
-        raise ValueError('%s: %s must be an integer >= %d (got %r)' % (what, name, lo, v))
-    return int(v)
 
 
 def _pca_matrix(t, what, name):
@@ -3831,10 +3910,10 @@ def _pca_args(xf, n_components, oversample, n_iter, seed, what):
     """The checks of ``pca`` that need no device work: (n, d, r, p, q, seed)."""
     _pca_matrix(xf, what, 'xf')
     n, d = int(xf.shape[0]), int(xf.shape[1])
-    r = _pca_int(n_components, 1, what, 'n_components')
-    p = _pca_int(oversample, 0, what, 'oversample')
-    q = _pca_int(n_iter, 0, what, 'n_iter')
-    seed = _pca_int(seed, 0, what, 'seed')
+    r = _int_arg(n_components, 1, None, what, 'n_components')
+    p = _int_arg(oversample, 0, None, what, 'oversample')
+    q = _int_arg(n_iter, 0, None, what, 'n_iter')
+    seed = _int_arg(seed, 0, None, what, 'seed')
     if n < 2:
         raise ValueError('%s: needs n >= 2 samples (got %s)' % (what, tuple(xf.shape)))
     if r + p > min(n - 1, d) or r + p > PCA_LMAX:
@@ -3973,10 +4052,7 @@ class DiffusionGraph(object):
 
 
 def _diffusion_int(v, lo, hi, what, name):
-    import numbers
-    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= hi:
-        raise ValueError('%s: %s must be an integer in %d..%s (got %r)' % (what, name, lo, hi if hi < 2 ** 31 - 1 else '', v))
-    return int(v)
+    return _int_arg(v, lo, hi, what, name, 'in %d..' % lo if hi >= _INT_MAX else None)
 
 
 def _diffusion_graph_args(k, gamma, what):
@@ -3984,12 +4060,11 @@ def _diffusion_graph_args(k, gamma, what):
 
 
 def _diffusion_solve_args(alpha, n_iter, what):
-    import numbers
     if isinstance(alpha, bool) or not isinstance(alpha, numbers.Real) or not 0.0 <= alpha < 1.0:    # (NaN fails both)
         raise ValueError('%s: alpha must be a number in [0, 1) (got %r)' % (what, alpha))
     if not 0.0 <= float(torch.tensor(float(alpha), dtype=torch.float32)) < 1.0:
         raise ValueError('%s: alpha must stay below 1 in float32 (got %r)' % (what, alpha))
-    return float(alpha), _diffusion_int(n_iter, 0, 2 ** 31 - 1, what, 'n_iter')
+    return float(alpha), _diffusion_int(n_iter, 0, _INT_MAX, what, 'n_iter')
 
 
 def _diffusion_kq(kq, k, what):
@@ -4092,9 +4167,8 @@ def _diffusion_query_block(query_block, block_bytes, n, nq, vectors, what):
     """Queries per block: ``query_block``, or what fits ``block_bytes`` (GRL_SEARCH_BLOCK_BYTES) counting ``vectors``
     [n][B] float arrays -- a multiple of 64 from 256 on, which keeps the 16-byte accesses of the state."""
     if query_block is not None:
-        return _diffusion_int(query_block, 1, 2 ** 31 - 1, what, 'query_block')
-    budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
-    B = max(1, min(nq, budget // (4 * vectors * max(n, 1))))
+        return _diffusion_int(query_block, 1, _INT_MAX, what, 'query_block')
+    B = max(1, min(nq, _block_budget(block_bytes) // (4 * vectors * max(n, 1))))
     return B // 64 * 64 if B >= 256 else B
 
 
@@ -4144,21 +4218,14 @@ def diffusion_search(qf, gf, k_out, graph=None, kq=10, alpha=0.99, n_iter=20, k=
     qf, gf, kq, alpha, n_iter, k, gamma = _diffusion_prepare(qf, gf, graph, kq, alpha, n_iter, k, gamma, what)
     nq, n, dev = qf.shape[0], gf.shape[0], qf.device
     junk = _junk_ids(exclude, nq, n, dev)
-    run_key = torch.full((nq, k_out), -1, dtype=torch.int64, device=dev)
-    run_val = torch.full((nq, k_out), float('inf'), dtype=torch.float32, device=dev)
+    top = _TopK(nq, k_out, dev)
     if nq and n:
         B = _diffusion_query_block(query_block, block_bytes, n, nq, 5, what)
         if graph is None:
             graph = diffusion_graph(gf, k, gamma, block_bytes=block_bytes)
         for q0, q1, d in _diffusion_blocks(qf, gf, graph, kq, alpha, n_iter, B, block_bytes):
-            if junk is None:
-                _call('grl_topk_block', ptr(d), n, None, 0, q1 - q0, n, 0, k_out, ptr(run_key[q0:q1]), ptr(run_val[q0:q1]))
-            else:
-                _call('grl_topk_block_filtered', ptr(d), n, None, 0, q1 - q0, n, 0, k_out, ptr(run_key[q0:q1]),
-                      ptr(run_val[q0:q1]), ptr(junk[0][q0:q1]), ptr(junk[1][q0:q1]), ptr(junk[2]), ptr(junk[3]))
-    idx = run_key & 0xffffffff
-    idx[idx == 0xffffffff] = -1
-    return run_val, idx
+            top.push(d, n, n, 0, junk=junk, rows=(q0, q1))
+    return top.result()
 
 
 def diffusion_metrics_streaming(qf, gf, q_pids, g_pids, q_camids, g_camids, graph=None, kq=10, alpha=0.99, n_iter=20,
@@ -4257,10 +4324,9 @@ def _set_ranges(ptr_, t0, t1, cap):
     return out
 
 
-class _SetBlocks(object):
-    """Column blocks of the tracklet x tracklet set distance of ``qset`` against the tracklets [lo, hi) of ``gset``: the
-    block-source contract of ``_ColumnBlocks`` (``spans``, ``block(c0, c1)``, ``qf``, ``nq``; a block comes back with the
-    same bits every time it is asked for) with spans in TRACKLET columns.  No tracklet is ever cut.  Without ``block_cols``
+class _SetBlocks(_BlockSource):
+    """Column blocks of the tracklet x tracklet set distance of ``qset`` against the tracklets [lo, hi) of ``gset``: a
+    ``_BlockSource`` with spans in TRACKLET columns.  No tracklet is ever cut.  Without ``block_cols``
     a span takes as many whole gallery tracklets as keep the [nq, c1 - c0] output block within ``block_bytes``
     (GRL_SEARCH_BLOCK_BYTES).  Inside ``block`` the clip-level work is tiled over ranges of whole query tracklets and whole
     gallery tracklets whose clip x clip scratch stays within ``block_bytes`` too (a pair of tracklets that alone exceeds it
@@ -4276,13 +4342,8 @@ class _SetBlocks(object):
         hi = gset.n if hi is None else hi
         self.qset, self.gset, self.reduce, self.metric = qset, gset, SET_REDUCE[reduce], metric
         self.qf, self.nq, self.ng, self.lo = qset.clips, qset.n, gset.n, lo
-        self.budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
-        if block_cols is None:
-            block_cols = self.budget // (4 * max(self.nq, 1))
-        width = max(1, min(int(block_cols), hi - lo))
-        self.width = width
-        self.spans = [(c, min(c + width, hi)) for c in range(lo, hi, width)]
-        self.buf = _new((self.nq * width,), self.qf) if self.spans and self.nq else None
+        self.budget = _block_budget(block_bytes)
+        self._cut(lo, hi, block_cols, block_bytes, granule=None)      # whole tracklets: no rounding, no floor of 256
         self.scratch = None
         self.rn = self.cn = None
         if metric == 'euclidean' and self.spans and self.nq:
@@ -4306,7 +4367,7 @@ class _SetBlocks(object):
 
     def block(self, c0, c1):
         n, k = c1 - c0, self.qf.shape[1]
-        out = self.buf[:self.nq * n].view(self.nq, n)
+        out = self._view(n)
         qs, gs = self.qset, self.gset
         for a0, a1, b0, b1 in self.tiles(c0, c1):
             q0, q1, g0, g1 = int(qs.ptr[a0]), int(qs.ptr[a1]), int(gs.ptr[b0]), int(gs.ptr[b1])
@@ -4354,12 +4415,11 @@ def set_search(qset, gset, k, reduce='chamfer', metric='cosine', exclude=None, b
     and only the per-rank top-k lists are exchanged, as in ``search``."""
     _set_pair(qset, gset, 'set_search')
     _set_args(reduce, metric, 'set_search')
-    if not 1 <= int(k) <= SEARCH_K_MAX:
-        raise ValueError('set_search: k must be in 1..%d (got %r)' % (SEARCH_K_MAX, k))
+    k = _search_k(k, 'set_search')
     junk = _junk_ids(exclude, qset.n, gset.n, qset.clips.device)
     lo, hi, sharded = _shard(gset.n)
     blocks = _SetBlocks(qset, gset, reduce, metric, block_cols, block_bytes, lo, hi)
-    return _search_blocks(blocks, qset.n, int(k), sharded, junk)
+    return _search_blocks(blocks, qset.n, k, sharded, junk)
 
 
 def set_metrics_streaming(qset, gset, q_pids, g_pids, q_camids, g_camids, reduce='chamfer', metric='cosine', max_rank=100,
@@ -4371,8 +4431,7 @@ def set_metrics_streaming(qset, gset, q_pids, g_pids, q_camids, g_camids, reduce
     _set_args(reduce, metric, 'set_metrics_streaming')
     lo, hi, sharded = _shard(gset.n)
     blocks = _SetBlocks(qset, gset, reduce, metric, block_cols, block_bytes, lo, hi)
-    first, nhit, ap = _rank_blocks(blocks, qset.n, gset.n, q_pids, g_pids, q_camids, g_camids, sharded)
-    return _cmc_map(first, nhit, ap, gset.n, max_rank)
+    return _metrics_from_blocks(blocks, qset.n, gset.n, q_pids, g_pids, q_camids, g_camids, max_rank, sharded)
 
 
 def set_pair_roc(qset, gset, q_pids, g_pids, q_camids, g_camids, reduce='chamfer', metric='cosine', bits=ROC_BITS_DEFAULT,
@@ -4396,16 +4455,9 @@ PQ_LUT_BYTES = int(os.environ.get('GRL_PQ_LUT_BYTES', str(1 << 30)))  # resident
 PQ_NQ_MAX = 262140                                                    # queries per grl_pq_scan call (its grid: 4 * 65535)
 
 
-def _pq_int(v, lo, hi, what, name):
-    import numbers
-    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= hi:
-        raise ValueError('%s: %s must be an integer in %d..%d (got %r)' % (what, name, lo, hi, v))
-    return int(v)
-
-
 def _pq_split(d, M, what):
     """dsub = d / M, or ValueError naming M (d % M) or dsub (the sub-products go through the fp32 GEMM: K % 32 == 0)."""
-    M = _pq_int(M, 1, PQ_M_MAX, what, 'M')
+    M = _int_arg(M, 1, PQ_M_MAX, what, 'M')
     if d % M:
         raise ValueError('%s: M must divide the feature size (d = %d, got M = %d)' % (what, d, M))
     if (d // M) % 32:
@@ -4531,7 +4583,7 @@ def pq_train(xf, M, nbits=8, metric='cosine', max_iter=25, seed=0):
     xf = _kmeans_rows(xf, 'pq_train')
     n, d = xf.shape
     M, dsub = _pq_split(d, M, 'pq_train')
-    nbits = _pq_int(nbits, 4, 8, 'pq_train', 'nbits')
+    nbits = _int_arg(nbits, 4, 8, 'pq_train', 'nbits')
     max_iter = _kmeans_int(max_iter, 1, 'pq_train', 'max_iter')
     seed = _kmeans_int(seed, 0, 'pq_train', 'seed')
     ksub = 1 << nbits
@@ -4567,41 +4619,28 @@ def pq_index(xf, codebook):
     return PqIndex(codebook, codes, scan)
 
 
-def _pq_check(index, what):
-    if not isinstance(index, PqIndex):
-        raise ValueError('%s: index must be a PqIndex (got %s)' % (what, type(index).__name__))
-
-
-class _PqBlocks(object):
-    """Column blocks of the ADC distance matrix of ``qf`` against the code rows of ``index``: the block-source contract of
-    ``_ColumnBlocks`` (``spans``, ``block(c0, c1)``, ``qf``, ``nq``, ``ng``; widths chosen the same way; one reused
-    buffer).  The constructor makes the tables of all its queries (``codebook.lut``) and, for 'euclidean', their
+class _PqBlocks(_BlockSource):
+    """Column blocks of the ADC distance matrix of ``qf`` against the code rows of ``index``: a ``_BlockSource`` (widths
+    chosen as ``_ColumnBlocks`` does).  The constructor makes the tables of all its queries (``codebook.lut``) and, for 'euclidean', their
     grl_row_sqnorm; a block is one grl_pq_scan over the code rows [c0, c1).  An entry's bits depend on its codes and its
     query's table alone (include/grl_hip.h), so a block holds the full matrix's bits whatever its width."""
 
     def __init__(self, qf, index, block_cols=None, block_bytes=None):
-        _pq_check(index, '_PqBlocks')
+        _check_index(index, PqIndex, '_PqBlocks')
         book = index.codebook
         self.qf = _pq_rows(qf, book.d, '_PqBlocks', 'qf')
         self.index, self.nq, self.ng = index, self.qf.shape[0], index.n
-        nq, hi = self.nq, index.n
-        if block_cols is None:
-            budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
-            block_cols = max(256, budget // (4 * max(nq, 1)) // 256 * 256)
-        width = max(1, min(int(block_cols), hi))
-        self.width = width
-        self.spans = [(c, min(c + width, hi)) for c in range(0, hi, width)]
-        self.buf = _new((nq * width,), self.qf) if self.spans and nq else None
+        self._cut(0, index.n, block_cols, block_bytes)
         self.lut = self.rn = None
-        if self.spans and nq:
+        if self.spans and self.nq:
             self.lut = book.lut(self.qf)
             if book.metric == 'euclidean':
-                self.rn = _new((nq,), self.qf)
-                _call('grl_row_sqnorm', ptr(self.qf), ptr(self.rn), nq, book.d, book.d)
+                self.rn = _new((self.nq,), self.qf)
+                _call('grl_row_sqnorm', ptr(self.qf), ptr(self.rn), self.nq, book.d, book.d)
 
     def block(self, c0, c1):
         n, book = c1 - c0, self.index.codebook
-        out = self.buf[:self.nq * n].view(self.nq, n)
+        out = self._view(n)
         scan = self.index._scan
         if n != self.ng:                                   # the kernel's row stride is its column count
             scan = scan[:, c0:c1].contiguous()
@@ -4615,13 +4654,9 @@ def pq_dist(qf, index, block_cols=None, block_bytes=None):
     sum S of the M table entries its codes select, in the fixed fp32 order of include/grl_hip.h (four partials, adds only);
     'cosine': S; 'euclidean': sqrt(max(|q|^2 + S, 1e-12)), a NaN argument giving 1e-12 as in pairwise_distance_tensor.
     tests/pq_ref.py gives the same bits from the tables.  The same bits for every ``block_cols``."""
-    _pq_check(index, 'pq_dist')
+    _check_index(index, PqIndex, 'pq_dist')
     blocks = _PqBlocks(qf, index, index.n if block_cols is None and block_bytes is None else block_cols, block_bytes)
-    out = _new((blocks.nq, index.n), blocks.qf)
-    if blocks.nq:
-        for c0, c1 in blocks.spans:
-            out[:, c0:c1] = blocks.block(c0, c1)
-    return out
+    return _dist_from_blocks(blocks, index.n)
 
 
 def pq_search(qf, index, k, exclude=None, block_cols=None, block_bytes=None):
@@ -4631,30 +4666,19 @@ def pq_search(qf, index, k, exclude=None, block_cols=None, block_bytes=None):
     smaller gallery index.  ``exclude`` is search's junk rule; padding is index -1, distance +inf; k <= 1024.  The tables
     of the queries are resident (nq * M * ksub * 4 bytes); beyond GRL_PQ_LUT_BYTES (1 GiB) the queries are served in row
     blocks, whose results are independent and concatenated.  Not sharded: every rank computes the full result."""
-    _pq_check(index, 'pq_search')
-    if not 1 <= int(k) <= SEARCH_K_MAX:
-        raise ValueError('pq_search: k must be in 1..%d (got %r)' % (SEARCH_K_MAX, k))
-    k, book = int(k), index.codebook
+    _check_index(index, PqIndex, 'pq_search')
+    k, book = _search_k(k, 'pq_search'), index.codebook
     qf = _pq_rows(qf, book.d, 'pq_search', 'qf')
-    nq = qf.shape[0]
-    junk = _junk_ids(exclude, nq, index.n, qf.device)
+    junk = _junk_ids(exclude, qf.shape[0], index.n, qf.device)
     rows = max(1, PQ_LUT_BYTES // (4 * book.M * book.ksub))          # queries whose tables fit (at least one)
-    dist, idx = [], []
-    for q0 in range(0, max(nq, 1), rows):
-        q1 = min(q0 + rows, nq)
-        blocks = _PqBlocks(qf[q0:q1], index, block_cols, block_bytes)
-        j = None if junk is None else (junk[0][q0:q1], junk[1][q0:q1], junk[2], junk[3])
-        dv, di = _search_blocks(blocks, q1 - q0, k, False, j)
-        dist.append(dv)
-        idx.append(di)
-    return (dist[0], idx[0]) if len(dist) == 1 else (torch.cat(dist), torch.cat(idx))
+    return _search_by_query_rows(lambda q: _PqBlocks(q, index, block_cols, block_bytes), qf, rows, k, junk)
 
 
 def pq_metrics_streaming(qf, index, q_pids, g_pids, q_camids, g_camids, max_rank=100, block_cols=None, block_bytes=None):
     """``rank_metrics(rank_rows(D), ...)`` for D = pq_dist(qf, index) without D: (cmc[max_rank] float32, mAP float) with
     rank_metrics_streaming's contract.  The tables of ALL queries must fit GRL_PQ_LUT_BYTES: ValueError otherwise, naming
     the bytes (the two passes walk every query's matches together).  Not sharded."""
-    _pq_check(index, 'pq_metrics_streaming')
+    _check_index(index, PqIndex, 'pq_metrics_streaming')
     book = index.codebook
     qf = _pq_rows(qf, book.d, 'pq_metrics_streaming', 'qf')
     need = 4 * qf.shape[0] * book.M * book.ksub
@@ -4662,8 +4686,7 @@ def pq_metrics_streaming(qf, index, q_pids, g_pids, q_camids, g_camids, max_rank
         raise ValueError('pq_metrics_streaming: the query tables take %d bytes (nq * M * ksub * 4 = %d * %d * %d * 4), above '
                          'GRL_PQ_LUT_BYTES = %d' % (need, qf.shape[0], book.M, book.ksub, PQ_LUT_BYTES))
     blocks = _PqBlocks(qf, index, block_cols, block_bytes)
-    first, nhit, ap = _rank_blocks(blocks, blocks.nq, index.n, q_pids, g_pids, q_camids, g_camids, False)
-    return _cmc_map(first, nhit, ap, index.n, max_rank)
+    return _metrics_from_blocks(blocks, blocks.nq, index.n, q_pids, g_pids, q_camids, g_camids, max_rank, False)
 
 
 def topk_recall(approx_idx, exact_idx, ks):
@@ -4678,7 +4701,7 @@ def topk_recall(approx_idx, exact_idx, ks):
                          % (a.shape, e.shape))
     out = []
     for k in ks:
-        k = _pq_int(k, 1, 2 ** 31 - 1, 'topk_recall', 'k')
+        k = _int_arg(k, 1, _INT_MAX, 'topk_recall', 'k')
         part = []
         for ra, re_ in zip(a[:, :k], e[:, :k]):
             valid = re_[re_ >= 0]
@@ -4748,8 +4771,8 @@ def ivf_train(xf, nlist, M, nbits=8, metric='cosine', max_iter=25, seed=0):
     xf = _kmeans_rows(xf, 'ivf_train')
     n, d = xf.shape
     M, dsub = _pq_split(d, M, 'ivf_train')
-    nbits = _pq_int(nbits, 4, 8, 'ivf_train', 'nbits')
-    nlist = _pq_int(nlist, 1, IVF_NLIST_MAX, 'ivf_train', 'nlist')
+    nbits = _int_arg(nbits, 4, 8, 'ivf_train', 'nbits')
+    nlist = _int_arg(nlist, 1, IVF_NLIST_MAX, 'ivf_train', 'nlist')
     max_iter = _kmeans_int(max_iter, 1, 'ivf_train', 'max_iter')
     seed = _kmeans_int(seed, 0, 'ivf_train', 'seed')
     if n < max(nlist, 1 << nbits):
@@ -4881,10 +4904,9 @@ def ivf_index(xf, book):
 
 
 def _ivf_args(qf, index, nprobe, what):
-    if not isinstance(index, IvfPqIndex):
-        raise ValueError('%s: index must be an IvfPqIndex (got %s)' % (what, type(index).__name__))
+    _check_index(index, IvfPqIndex, what)
     hi = min(index.book.nlist, IVF_NPROBE_MAX)
-    nprobe = _pq_int(nprobe, 1, hi, what, 'nprobe')
+    nprobe = _int_arg(nprobe, 1, hi, what, 'nprobe')
     return _pq_rows(qf, index.book.d, what, 'qf'), nprobe
 
 
@@ -4943,7 +4965,7 @@ def _ivf_plan(index, nq, nprobe, block_bytes):
     holds at least one probe, and where one probe already exceeds the budget the queries go in row blocks.  The tables
     obey GRL_PQ_LUT_BYTES and a launch serves at most 65535 queries."""
     pq = index.book.pq
-    budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
+    budget = _block_budget(block_bytes)
     rows = max(1, min(65535, PQ_LUT_BYTES // (4 * pq.M * pq.ksub), max(nq, 1)))
     one = max(index._longest[1], 1)
     if 8 * rows * one > budget:
@@ -4965,15 +4987,12 @@ def ivf_search(qf, index, k, nprobe, exclude=None, block_bytes=None):
     The candidates are served in chunks of probe ranks sized by ``block_bytes`` (default GRL_SEARCH_BLOCK_BYTES), the
     queries in row blocks where one probe exceeds it or the tables exceed GRL_PQ_LUT_BYTES: the same bits for every
     chunking.  Not sharded: every rank computes the full result."""
-    if not isinstance(index, IvfPqIndex):
-        raise ValueError('ivf_search: index must be an IvfPqIndex (got %s)' % type(index).__name__)
-    if not 1 <= int(k) <= SEARCH_K_MAX:
-        raise ValueError('ivf_search: k must be in 1..%d (got %r)' % (SEARCH_K_MAX, k))
+    _check_index(index, IvfPqIndex, 'ivf_search')
+    k = _search_k(k, 'ivf_search')
     qf, nprobe = _ivf_args(qf, index, nprobe, 'ivf_search')
-    k, nq, dev = int(k), qf.shape[0], qf.device
+    nq, dev = qf.shape[0], qf.device
     junk = _junk_ids(exclude, nq, index.n, dev)
-    run_key = torch.full((nq, k), -1, dtype=torch.int64, device=dev)          # all-ones composite = empty slot
-    run_val = torch.full((nq, k), float('inf'), dtype=torch.float32, device=dev)
+    top = _TopK(nq, k, dev)
     if nq and index.n:
         rows, per = _ivf_plan(index, nq, nprobe, block_bytes)
         for q0 in range(0, nq, rows):
@@ -4985,15 +5004,8 @@ def ivf_search(qf, index, k, nprobe, exclude=None, block_bytes=None):
                 if width == 0:
                     continue
                 d, cidx = qs.chunk(j0, j1, width)
-                if junk is None:
-                    _call('grl_topk_block', ptr(d), width, ptr(cidx), width, q1 - q0, width, 0, k, ptr(run_key[q0:]),
-                          ptr(run_val[q0:]))
-                else:
-                    _call('grl_topk_block_filtered', ptr(d), width, ptr(cidx), width, q1 - q0, width, 0, k, ptr(run_key[q0:]),
-                          ptr(run_val[q0:]), ptr(junk[0][q0:]), ptr(junk[1][q0:]), ptr(junk[2]), ptr(junk[3]))
-    idx = run_key & 0xffffffff
-    idx[idx == 0xffffffff] = -1
-    return run_val, idx
+                top.push(d, width, width, 0, cidx, width, junk, (q0, q1))
+    return top.result()
 
 
 def ivf_dist(qf, index, nprobe):
@@ -5128,24 +5140,20 @@ def refine_lists(qf, store, cand, k, metric='cosine', block_bytes=None):
     1 <= k <= 1024.  The distance block and the id block (8 bytes per pair) are served in query row blocks that fit
     ``block_bytes`` (default GRL_SEARCH_BLOCK_BYTES), each ranked by grl_topk_block with the id block as its cidx: the
     same bits for every blocking.  A ``verify_metric`` is refused.  Not sharded: every rank computes the full result."""
-    k = _pq_int(k, 1, SEARCH_K_MAX, 'refine_lists', 'k')
+    k = _int_arg(k, 1, SEARCH_K_MAX, 'refine_lists', 'k')
     qf, cand = _refine_args(qf, store, cand, metric, 'refine_lists')
     nq, L = cand.shape
     dev = qf.device
-    run_key = torch.full((nq, k), -1, dtype=torch.int64, device=dev)          # all-ones composite = empty slot
-    run_val = torch.full((nq, k), float('inf'), dtype=torch.float32, device=dev)
+    top = _TopK(nq, k, dev)
     if nq and L and store.n:
-        budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
-        rows = max(1, min(65535, nq, budget // (8 * L)))
+        rows = max(1, min(65535, nq, _block_budget(block_bytes) // (8 * L)))
         d = _new((rows, L), qf)
         cidx = torch.empty((rows, L), dtype=torch.int32, device=dev)
         for q0 in range(0, nq, rows):
             q1 = min(q0 + rows, nq)
             _refine_scan(qf[q0:q1], store, cand[q0:q1], metric, d, cidx)
-            _call('grl_topk_block', ptr(d), L, ptr(cidx), L, q1 - q0, L, 0, k, ptr(run_key[q0:]), ptr(run_val[q0:]))
-    idx = run_key & 0xffffffff
-    idx[idx == 0xffffffff] = -1
-    return run_val, idx
+            top.push(d, L, L, 0, cidx, L, rows=(q0, q1))
+    return top.result()
 
 
 def refine_search(qf, index, store, k, R, nprobe=None, exclude=None, block_bytes=None):
@@ -5164,18 +5172,11 @@ def refine_search(qf, index, store, k, R, nprobe=None, exclude=None, block_bytes
             raise ValueError('refine_search: nprobe is required for an IvfPqIndex')
     else:
         raise ValueError('refine_search: index must be a PqIndex or an IvfPqIndex (got %s)' % type(index).__name__)
-    if not isinstance(store, RefineStore):
-        raise ValueError('refine_search: store must be a RefineStore (got %s)' % type(store).__name__)
-    if store.n != index.n or store.d != d:
-        raise ValueError('refine_search: store must hold the rows of the index: store is [%d, %d], the index [%d, %d]'
-                         % (store.n, store.d, index.n, d))
-    k = _pq_int(k, 1, SEARCH_K_MAX, 'refine_search', 'k')
-    R = _pq_int(R, k, SEARCH_K_MAX, 'refine_search', 'R (k <= R <= %d)' % SEARCH_K_MAX)
-    if flat:
-        cand = pq_search(qf, index, R, exclude=exclude, block_bytes=block_bytes)[1]
-    else:
-        cand = ivf_search(qf, index, R, nprobe, exclude=exclude, block_bytes=block_bytes)[1]
-    return refine_lists(qf, store, cand, k, metric, block_bytes)
+    def shortlist(R):
+        if flat:
+            return pq_search(qf, index, R, exclude=exclude, block_bytes=block_bytes)
+        return ivf_search(qf, index, R, nprobe, exclude=exclude, block_bytes=block_bytes)
+    return _two_stage('refine_search', qf, index, d, metric, store, k, R, shortlist, block_bytes)
 
 
 # ----------------------------------------------------------------------------
@@ -5201,7 +5202,7 @@ def nng_knn(store_or_xf, K, metric='cosine', block_bytes=None):
     or a float32 device tensor [n, d]), nearest first -- ``search`` of the rows against themselves with the row itself
     removed by its junk rule (pids = the row numbers, one camera); -1 pads a row when n - 1 < K.  2 <= K <= 128."""
     _cluster_metric(metric, 'nng_knn')
-    K = _pq_int(K, 2, NNG_K_MAX, 'nng_knn', 'K')
+    K = _int_arg(K, 2, NNG_K_MAX, 'nng_knn', 'K')
     if isinstance(store_or_xf, RefineStore):
         if store_or_xf.dtype != 'f32':
             raise ValueError("nng_knn: store_or_xf must be an 'f32' RefineStore: the exact lists are taken on the fp32 rows "
@@ -5230,7 +5231,7 @@ def nng_optimize(knn, D):
         raise ValueError('nng_optimize: knn must have K columns with K in 2..%d (got K = %d)' % (NNG_K_MAX, K))
     if n >= 2 ** 31:
         raise ValueError('nng_optimize: knn must have fewer than 2**31 rows (got %d)' % n)
-    D = _pq_int(D, 2, min(K, NNG_D_MAX), 'nng_optimize', 'D (even, 2 <= D <= min(K, %d))' % NNG_D_MAX)
+    D = _int_arg(D, 2, min(K, NNG_D_MAX), 'nng_optimize', 'D (even, 2 <= D <= min(K, %d))' % NNG_D_MAX)
     if D % 2:
         raise ValueError('nng_optimize: D must be even (got %d)' % D)
     dev = knn.device
@@ -5309,7 +5310,7 @@ def nng_build(xf_or_store, K=64, D=32, metric='cosine', dtype='f32', knn=None):
         store, owned = _nng_store(xf_or_store, dtype, 'nng_build', 'xf_or_store')
         rows = xf_or_store.contiguous()
     if knn is None:
-        K = _pq_int(K, 2, NNG_K_MAX, 'nng_build', 'K')
+        K = _int_arg(K, 2, NNG_K_MAX, 'nng_build', 'K')
         knn = nng_knn(rows, K, metric)
     elif torch.is_tensor(knn) and knn.dim() == 2 and knn.shape[0] != store.n:
         raise ValueError('nng_build: knn must have one row per store row: the store has %d, knn %d' % (store.n, knn.shape[0]))
@@ -5350,14 +5351,14 @@ def nng_search(qf, index, k, L=64, w=1, T=64, seeds=None, exclude=None, return_s
     require_device(qf, 'qf')
     qf = qf.contiguous()
     nq, dev = int(qf.shape[0]), qf.device
-    L = _pq_int(L, NNG_L_MIN, NNG_L_MAX, what, 'L (a power of two)')
+    L = _int_arg(L, NNG_L_MIN, NNG_L_MAX, what, 'L (a power of two)')
     if L & (L - 1):
         raise ValueError('%s: L must be a power of two in %d..%d (got %d)' % (what, NNG_L_MIN, NNG_L_MAX, L))
-    k = _pq_int(k, 1, L, what, 'k (k <= L = %d)' % L)
-    w = _pq_int(w, 1, NNG_W_MAX, what, 'w')
+    k = _int_arg(k, 1, L, what, 'k (k <= L = %d)' % L)
+    w = _int_arg(w, 1, NNG_W_MAX, what, 'w')
     if w * D > NNG_WD_MAX:
         raise ValueError('%s: w must keep w * D <= %d (got w = %d with D = %d)' % (what, NNG_WD_MAX, w, D))
-    T = _pq_int(T, 1, 2 ** 31 - 1, what, 'T')
+    T = _int_arg(T, 1, _INT_MAX, what, 'T')
     if seeds is None:
         if n == 0:
             seeds_t, S, stride = torch.zeros(1, dtype=torch.int32, device=dev), 1, 0
@@ -5418,7 +5419,6 @@ BIN_MODES = ('hamming', 'asymmetric')
 
 
 def _bin_nbits(nbits, what):
-    import numbers
     if isinstance(nbits, bool) or not isinstance(nbits, numbers.Integral) or nbits % 32 or not 32 <= nbits <= BIN_NBITS_MAX:
         raise ValueError('%s: nbits must be an integer multiple of 32 in 32..%d (got %r)' % (what, BIN_NBITS_MAX, nbits))
     return int(nbits)
@@ -5619,33 +5619,22 @@ def bin_index(xf, codebook):
     return BinaryIndex(codebook, codes, scan)
 
 
-def _bin_check(index, what):
-    if not isinstance(index, BinaryIndex):
-        raise ValueError('%s: index must be a BinaryIndex (got %s)' % (what, type(index).__name__))
-
-
-class _BinBlocks(object):
-    """Column blocks of the distance matrix of ``qf`` against the code rows of ``index``: ``_PqBlocks``' block-source
-    contract (``spans``, ``block(c0, c1)``, ``qf``, ``nq``, ``ng``; one reused buffer).  'hamming': the constructor encodes
+class _BinBlocks(_BlockSource):
+    """Column blocks of the distance matrix of ``qf`` against the code rows of ``index``: a ``_BlockSource`` like
+    ``_PqBlocks``.  'hamming': the constructor encodes
     the queries and a block is grl_bin_scan over the word rows [c0, c1) in place (the kernel takes the row stride);
     'asymmetric': the constructor makes the tables of all its queries (``codebook.lut``) and a block is grl_pq_scan with
     M = nbits / 8, ksub = 256 over a contiguous copy of the block's words.  An entry depends on its codes and its query
     alone, so a block holds the full matrix's bits whatever its width."""
 
     def __init__(self, qf, index, mode='hamming', block_cols=None, block_bytes=None):
-        _bin_check(index, '_BinBlocks')
+        _check_index(index, BinaryIndex, '_BinBlocks')
         _bin_mode(mode, '_BinBlocks')
         book = index.codebook
         xp = book._rows(qf, '_BinBlocks', 'qf')
-        self.qf, self.index, self.mode, self.nq, self.ng = xp, index, mode, xp.shape[0], index.n
-        nq, hi = self.nq, index.n
-        if block_cols is None:
-            budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
-            block_cols = max(256, budget // (4 * max(nq, 1)) // 256 * 256)
-        width = max(1, min(int(block_cols), hi))
-        self.width = width
-        self.spans = [(c, min(c + width, hi)) for c in range(0, hi, width)]
-        self.buf = _new((nq * width,), xp) if self.spans and nq else None
+        self.qf, self.index, self.mode, self.ng = xp, index, mode, index.n
+        self.nq = nq = xp.shape[0]
+        self._cut(0, index.n, block_cols, block_bytes)
         self.qwords = self.lut = self.z = None
         if self.spans and nq:
             self.z = book._project(xp)
@@ -5657,7 +5646,7 @@ class _BinBlocks(object):
 
     def block(self, c0, c1):
         n, nbits, nq = c1 - c0, self.index.nbits, self.nq
-        out = self.buf[:nq * n].view(nq, n)
+        out = self._view(n)
         scan = self.index._scan
         if self.mode == 'hamming':
             for q0 in range(0, nq, BIN_NQ_MAX):
@@ -5676,14 +5665,10 @@ def bin_dist(qf, index, mode='hamming', block_cols=None, block_bytes=None):
     -sum_b z_q[b] s_g[b] with z_q the query's projection and s_g = +-1 the row's bits, as the ADC sum of include/grl_hip.h
     over ``codebook.lut(qf)`` (tests/pq_ref.adc_dist gives the same bits); smaller = nearer under both.  The same bits for
     every ``block_cols``."""
-    _bin_check(index, 'bin_dist')
+    _check_index(index, BinaryIndex, 'bin_dist')
     _bin_mode(mode, 'bin_dist')
     blocks = _BinBlocks(qf, index, mode, index.n if block_cols is None and block_bytes is None else block_cols, block_bytes)
-    out = _new((blocks.nq, index.n), blocks.qf)
-    if blocks.nq:
-        for c0, c1 in blocks.spans:
-            out[:, c0:c1] = blocks.block(c0, c1)
-    return out
+    return _dist_from_blocks(blocks, index.n)
 
 
 def _bin_query_rows(book, mode):
@@ -5700,24 +5685,13 @@ def bin_search(qf, index, k, mode='hamming', exclude=None, block_cols=None, bloc
     ties are the rule: they go to the smaller gallery index.  ``exclude`` is search's junk rule; padding is index -1,
     distance +inf; k <= 1024.  The asymmetric tables obey GRL_PQ_LUT_BYTES as ``pq_search``'s do: beyond it the queries
     are served in row blocks, whose results are independent and concatenated.  Not sharded."""
-    _bin_check(index, 'bin_search')
+    _check_index(index, BinaryIndex, 'bin_search')
     _bin_mode(mode, 'bin_search')
-    if isinstance(k, bool) or not 1 <= int(k) <= SEARCH_K_MAX:
-        raise ValueError('bin_search: k must be in 1..%d (got %r)' % (SEARCH_K_MAX, k))
-    k, book = int(k), index.codebook
+    k, book = _search_k(k, 'bin_search'), index.codebook
     qf = book._check(qf, 'bin_search', 'qf')
-    nq = qf.shape[0]
-    junk = _junk_ids(exclude, nq, index.n, qf.device)
-    rows = _bin_query_rows(book, mode)
-    dist, idx = [], []
-    for q0 in range(0, max(nq, 1), rows):
-        q1 = min(q0 + rows, nq)
-        blocks = _BinBlocks(qf[q0:q1], index, mode, block_cols, block_bytes)
-        j = None if junk is None else (junk[0][q0:q1], junk[1][q0:q1], junk[2], junk[3])
-        dv, di = _search_blocks(blocks, q1 - q0, k, False, j)
-        dist.append(dv)
-        idx.append(di)
-    return (dist[0], idx[0]) if len(dist) == 1 else (torch.cat(dist), torch.cat(idx))
+    junk = _junk_ids(exclude, qf.shape[0], index.n, qf.device)
+    return _search_by_query_rows(lambda q: _BinBlocks(q, index, mode, block_cols, block_bytes), qf,
+                                 _bin_query_rows(book, mode), k, junk)
 
 
 def bin_metrics_streaming(qf, index, q_pids, g_pids, q_camids, g_camids, mode='hamming', max_rank=100, block_cols=None,
@@ -5726,7 +5700,7 @@ def bin_metrics_streaming(qf, index, q_pids, g_pids, q_camids, g_camids, mode='h
     with rank_metrics_streaming's contract.  'asymmetric': the tables of ALL queries must fit GRL_PQ_LUT_BYTES, as in
     ``pq_metrics_streaming`` (ValueError naming the bytes), and there are at most 262 140 of them (grl_pq_scan's grid).
     Not sharded."""
-    _bin_check(index, 'bin_metrics_streaming')
+    _check_index(index, BinaryIndex, 'bin_metrics_streaming')
     _bin_mode(mode, 'bin_metrics_streaming')
     book = index.codebook
     qf = book._check(qf, 'bin_metrics_streaming', 'qf')
@@ -5739,26 +5713,18 @@ def bin_metrics_streaming(qf, index, q_pids, g_pids, q_camids, g_camids, mode='h
             raise ValueError('bin_metrics_streaming: the query tables take %d bytes (nq * nbits / 8 * 256 * 4 = %d * %d * 256 '
                              '* 4), above GRL_PQ_LUT_BYTES = %d' % (need, qf.shape[0], book.nbits // 8, PQ_LUT_BYTES))
     blocks = _BinBlocks(qf, index, mode, block_cols, block_bytes)
-    first, nhit, ap = _rank_blocks(blocks, blocks.nq, index.n, q_pids, g_pids, q_camids, g_camids, False)
-    return _cmc_map(first, nhit, ap, index.n, max_rank)
+    return _metrics_from_blocks(blocks, blocks.nq, index.n, q_pids, g_pids, q_camids, g_camids, max_rank, False)
 
 
 def bin_refine_search(qf, index, store, k, R, mode='hamming', exclude=None, block_bytes=None):
     """Two-stage search over a ``BinaryIndex``: exactly ``refine_lists(qf, store, bin_search(qf, index, R, mode,
     exclude=exclude)[1], k, index.codebook.metric, block_bytes)``.  The junk rule is applied in the first stage and nowhere
     else.  k <= R <= 1024; store.n and store.d must be the index's.  ValueError names the argument that is wrong."""
-    _bin_check(index, 'bin_refine_search')
+    _check_index(index, BinaryIndex, 'bin_refine_search')
     _bin_mode(mode, 'bin_refine_search')
-    if not isinstance(store, RefineStore):
-        raise ValueError('bin_refine_search: store must be a RefineStore (got %s)' % type(store).__name__)
-    d = index.codebook.d
-    if store.n != index.n or store.d != d:
-        raise ValueError('bin_refine_search: store must hold the rows of the index: store is [%d, %d], the index [%d, %d]'
-                         % (store.n, store.d, index.n, d))
-    k = _pq_int(k, 1, SEARCH_K_MAX, 'bin_refine_search', 'k')
-    R = _pq_int(R, k, SEARCH_K_MAX, 'bin_refine_search', 'R (k <= R <= %d)' % SEARCH_K_MAX)
-    cand = bin_search(qf, index, R, mode, exclude=exclude, block_bytes=block_bytes)[1]
-    return refine_lists(qf, store, cand, k, index.codebook.metric, block_bytes)
+    book = index.codebook
+    return _two_stage('bin_refine_search', qf, index, book.d, book.metric, store, k, R,
+                      lambda R: bin_search(qf, index, R, mode, exclude=exclude, block_bytes=block_bytes), block_bytes)
 
 
 # ----------------------------------------------------------------------------
@@ -5934,38 +5900,26 @@ def sq8_index(xf, codebook):
     return Sq8Index(codebook, codebook.encode(xf))
 
 
-def _sq8_check(index, what):
-    if not isinstance(index, Sq8Index):
-        raise ValueError('%s: index must be a Sq8Index (got %s)' % (what, type(index).__name__))
-
-
-class _Sq8Blocks(object):
-    """Column blocks of the distance matrix of ``qf`` against the code rows of ``index``: ``_PqBlocks``' block-source
-    contract (``spans``, ``block(c0, c1)``, ``qf``, ``nq``, ``ng``; one reused buffer).  The constructor quantises the
+class _Sq8Blocks(_BlockSource):
+    """Column blocks of the distance matrix of ``qf`` against the code rows of ``index``: a ``_BlockSource`` like
+    ``_PqBlocks``.  The constructor quantises the
     queries (``codebook.query``); a block is grl_sq8_scan over the code rows [c0, c1) in place (a pointer offset: the
     kernel takes the row stride).  An entry depends on its two code rows and its query's scale, bias and norm alone, and
     the integer sum has no order, so a block holds the full matrix's bits whatever its width."""
 
     def __init__(self, qf, index, block_cols=None, block_bytes=None):
-        _sq8_check(index, '_Sq8Blocks')
+        _check_index(index, Sq8Index, '_Sq8Blocks')
         book = index.codebook
         xp = _pad_features(book._check(qf, '_Sq8Blocks', 'qf'))
         self.qf, self.index, self.nq, self.ng = xp, index, xp.shape[0], index.n
-        nq, hi = self.nq, index.n
-        if block_cols is None:
-            budget = SEARCH_BLOCK_BYTES if block_bytes is None else int(block_bytes)
-            block_cols = max(256, budget // (4 * max(nq, 1)) // 256 * 256)
-        width = max(1, min(int(block_cols), hi))
-        self.width = width
-        self.spans = [(c, min(c + width, hi)) for c in range(0, hi, width)]
-        self.buf = _new((nq * width,), xp) if self.spans and nq else None
+        self._cut(0, index.n, block_cols, block_bytes)
         self.qcodes = self.scale = self.bias = self.qq = None
-        if self.spans and nq:
+        if self.spans and self.nq:
             self.qcodes, self.scale, self.bias, self.qq = book._query(xp, book.d)
 
     def block(self, c0, c1):
         n, nq, book = c1 - c0, self.nq, self.index.codebook
-        out = self.buf[:nq * n].view(nq, n)
+        out = self._view(n)
         for q0 in range(0, nq, SQ8_NQ_MAX):
             q1 = min(q0 + SQ8_NQ_MAX, nq)
             _call('grl_sq8_scan', ptr(self.qcodes[q0:q1]), book.dpad, ptr(self.index.codes[c0:c1]), book.dpad,
@@ -5979,13 +5933,9 @@ def sq8_dist(qf, index, block_cols=None, block_bytes=None):
     dot = scale * float(qcodes . codes) + bias with the exact int32 sum; 'cosine': -dot; 'euclidean':
     sqrt(max((qq + gg) - 2 dot, 1e-12)), a NaN argument giving 1e-12 as in pairwise_distance_tensor.  tests/sq8_ref.py
     gives the same bits.  The same bits for every ``block_cols``."""
-    _sq8_check(index, 'sq8_dist')
+    _check_index(index, Sq8Index, 'sq8_dist')
     blocks = _Sq8Blocks(qf, index, index.n if block_cols is None and block_bytes is None else block_cols, block_bytes)
-    out = _new((blocks.nq, index.n), blocks.qf)
-    if blocks.nq:
-        for c0, c1 in blocks.spans:
-            out[:, c0:c1] = blocks.block(c0, c1)
-    return out
+    return _dist_from_blocks(blocks, index.n)
 
 
 def sq8_search(qf, index, k, exclude=None, block_cols=None, block_bytes=None):
@@ -5993,10 +5943,8 @@ def sq8_search(qf, index, k, exclude=None, block_cols=None, block_bytes=None):
     ``rank_rows(D)[:, :k]`` and D at those indices, without D: blocks of code rows through grl_sq8_scan, ranked by
     search's running top-k.  Ties go to the smaller gallery index; ``exclude`` is search's junk rule; padding is index -1,
     distance +inf; k <= 1024.  Not sharded: every rank computes the full result."""
-    _sq8_check(index, 'sq8_search')
-    if isinstance(k, bool) or not 1 <= int(k) <= SEARCH_K_MAX:
-        raise ValueError('sq8_search: k must be in 1..%d (got %r)' % (SEARCH_K_MAX, k))
-    k = int(k)
+    _check_index(index, Sq8Index, 'sq8_search')
+    k = _search_k(k, 'sq8_search')
     qf = index.codebook._check(qf, 'sq8_search', 'qf')
     nq = qf.shape[0]
     junk = _junk_ids(exclude, nq, index.n, qf.device)
@@ -6007,25 +5955,17 @@ def sq8_search(qf, index, k, exclude=None, block_cols=None, block_bytes=None):
 def sq8_metrics_streaming(qf, index, q_pids, g_pids, q_camids, g_camids, max_rank=100, block_cols=None, block_bytes=None):
     """``rank_metrics(rank_rows(D), ...)`` for D = sq8_dist(qf, index) without D: (cmc[max_rank] float32, mAP float) with
     rank_metrics_streaming's contract.  Not sharded."""
-    _sq8_check(index, 'sq8_metrics_streaming')
+    _check_index(index, Sq8Index, 'sq8_metrics_streaming')
     qf = index.codebook._check(qf, 'sq8_metrics_streaming', 'qf')
     blocks = _Sq8Blocks(qf, index, block_cols, block_bytes)
-    first, nhit, ap = _rank_blocks(blocks, blocks.nq, index.n, q_pids, g_pids, q_camids, g_camids, False)
-    return _cmc_map(first, nhit, ap, index.n, max_rank)
+    return _metrics_from_blocks(blocks, blocks.nq, index.n, q_pids, g_pids, q_camids, g_camids, max_rank, False)
 
 
 def sq8_refine_search(qf, index, store, k, R, exclude=None, block_bytes=None):
     """Two-stage search over a ``Sq8Index``: exactly ``refine_lists(qf, store, sq8_search(qf, index, R,
     exclude=exclude)[1], k, index.codebook.metric, block_bytes)``.  The junk rule is applied in the first stage and nowhere
     else.  k <= R <= 1024; store.n and store.d must be the index's.  ValueError names the argument that is wrong."""
-    _sq8_check(index, 'sq8_refine_search')
-    if not isinstance(store, RefineStore):
-        raise ValueError('sq8_refine_search: store must be a RefineStore (got %s)' % type(store).__name__)
-    d = index.codebook.d
-    if store.n != index.n or store.d != d:
-        raise ValueError('sq8_refine_search: store must hold the rows of the index: store is [%d, %d], the index [%d, %d]'
-                         % (store.n, store.d, index.n, d))
-    k = _pq_int(k, 1, SEARCH_K_MAX, 'sq8_refine_search', 'k')
-    R = _pq_int(R, k, SEARCH_K_MAX, 'sq8_refine_search', 'R (k <= R <= %d)' % SEARCH_K_MAX)
-    cand = sq8_search(qf, index, R, exclude=exclude, block_bytes=block_bytes)[1]
-    return refine_lists(qf, store, cand, k, index.codebook.metric, block_bytes)
+    _check_index(index, Sq8Index, 'sq8_refine_search')
+    book = index.codebook
+    return _two_stage('sq8_refine_search', qf, index, book.d, book.metric, store, k, R,
+                      lambda R: sq8_search(qf, index, R, exclude=exclude, block_bytes=block_bytes), block_bytes)
