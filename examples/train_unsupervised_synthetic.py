@@ -10,13 +10,15 @@ The hidden pids are only used to print how good the clusters were.  Run:
 
     PYTHONPATH=.:dropin python examples/train_unsupervised_synthetic.py --epochs 2 --hybrid-memory --self-paced 0.02
     PYTHONPATH=.:dropin python examples/train_unsupervised_synthetic.py --epochs 2 --mean-teacher 0.999 --soft-weight 0.5 --eval-teacher
+    PYTHONPATH=.:dropin python examples/train_unsupervised_synthetic.py --epochs 2 --mean-teacher 0.999 --soft-weight 0.5 --soft-tri-weight 0.8
 
 (the second form: camera-aware proxies, one memory row per cluster and camera -- ProxyMemoryLoss under CameraSEQTrainer;
 the third: a hybrid memory with one row per tracklet, the samples the clustering calls noise trained on as classes of their
 own, and only the clusters that are stable under eps -/+ 0.02 kept -- HybridMemoryLoss under HybridSEQTrainer, DESIGN.md 4ak;
 the fourth: a mean teacher -- an averaged copy of the model whose softmax over the cluster memory is a soft target next to
 the hard cluster id, SoftClusterMemoryLoss under MeanTeacherSEQTrainer, and with --eval-teacher the model that is evaluated
-and clustered with)
+and clustered with; the fifth: the teacher's distances at the student's batch-hard indices as a soft target of
+the triplet term too, SoftTripletLoss)
 
 Every identity is a low-frequency colour layout ("a person in front of a background", as grl_amd.synthetic.
 synth_clips_structured); a tracklet is a small deviation from its identity's layout, a frame a smaller one, plus pixel noise.
@@ -85,6 +87,8 @@ def refuse_conflicts(args):
         raise SystemExit('--self-paced needs --hybrid-memory')
     if args.mean_teacher is None and (args.eval_teacher or args.soft_weight is not None):
         raise SystemExit('--soft-weight and --eval-teacher need --mean-teacher ALPHA')
+    if args.mean_teacher is None and getattr(args, 'soft_tri_weight', None) is not None:
+        raise SystemExit('--soft-tri-weight needs --mean-teacher ALPHA')
     if args.mean_teacher is not None and (args.camera_proxies or args.hybrid_memory):
         raise SystemExit('--mean-teacher is built for the plain cluster memory: it excludes --camera-proxies and '
                          '--hybrid-memory (DESIGN.md 4al, out of scope)')
@@ -141,7 +145,8 @@ def main(args):
         teacher = MeanTeacher(cnn_model, siamese_model, alpha=args.mean_teacher)
         trainer = MeanTeacherSEQTrainer(cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr,
                                         criterion_uncorr, osp.join(args.logs_dir, 'train_log'), teacher=teacher,
-                                        soft_weight=0.5 if args.soft_weight is None else args.soft_weight)
+                                        soft_weight=0.5 if args.soft_weight is None else args.soft_weight,
+                                        tri_soft_weight=0.0 if args.soft_tri_weight is None else args.soft_tri_weight)
         teacher_evaluator = ATTEvaluator(*teacher.models, only_eval=False)
         if args.eval_teacher:                                # the teacher's features are clustered, and it is what is scored
             evaluator, student_evaluator = teacher_evaluator, evaluator
@@ -218,6 +223,9 @@ if __name__ == '__main__':
                     help='mean teacher with this EMA coefficient: SoftClusterMemoryLoss under MeanTeacherSEQTrainer (DESIGN.md 4al)')
     ap.add_argument('--soft-weight', type=float, default=None, metavar='W',
                     help="with --mean-teacher: weight of the teacher's softmax in the identity losses (default 0.5)")
+    ap.add_argument('--soft-tri-weight', type=float, default=None, metavar='W',
+                    help="with --mean-teacher: weight of the teacher's soft target in the batch-hard triplet term, SoftTripletLoss "
+                         '(DESIGN.md 4am; default 0: the hard triplet)')
     ap.add_argument('--eval-teacher', action='store_true',
                     help='with --mean-teacher: evaluate and cluster with the teacher (ATTEvaluator on teacher.models)')
     ap.add_argument('--seed', type=int, default=0)

@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include "../../include/grl_hip.h"
 #include "common.h"
+#include "triplet_common.h"
 
 namespace {
 
@@ -121,47 +122,24 @@ __global__ __launch_bounds__(256) void oim_grad_kernel(const float* __restrict__
 // One workgroup per anchor i: the n distances of row i (one wave per j, lanes over the
 // features), then the hardest positive / negative with torch's value formulas and first-index
 // tie rule:  pos value = dist * [same id, j != i],  neg value = dist + 1e5 * [same id].
+// (The distance row, the selection and the backward's gather are triplet_common.h's, shared with soft_triplet.hip.)
 __global__ __launch_bounds__(256) void triplet_fwd_kernel(const float* __restrict__ f,
                                                           const int64_t* __restrict__ ids, int n, int D,
                                                           int soft, float margin,
                                                           float* __restrict__ loss, float* __restrict__ dist,
                                                           int32_t* __restrict__ sel, float* __restrict__ zout) {
     extern __shared__ float drow[];                    // [n]
-    const int i = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const f32x4* fi = reinterpret_cast<const f32x4*>(f + (int64_t)i * D);
-    const int D4 = D >> 2;
-    for (int j = wave; j < n; j += 4) {
-        const f32x4* fj = reinterpret_cast<const f32x4*>(f + (int64_t)j * D);
-        float s = 0.f;
-        for (int k = lane; k < D4; k += 64) {
-            const f32x4 d = fi[k] - fj[k];
-            s += d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
-        }
-        s = wave_sum(s);
-        if (lane == 0) {
-            const float d = sqrtf(s + 1e-12f);
-            drow[j] = d;
-            dist[(int64_t)i * n + j] = d;
-        }
-    }
+    const int i = blockIdx.x;
+    tri_dist_row(f, i, n, D, drow, dist);
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int64_t yi = ids[i];
-        float vp = -INFINITY, vn = INFINITY;
-        int jp = 0, jn = 0;
-        for (int j = 0; j < n; ++j) {
-            const bool same = ids[j] == yi;
-            const float p = drow[j] * ((same && j != i) ? 1.f : 0.f);
-            const float q = drow[j] + 1e5f * (same ? 1.f : 0.f);
-            if (p > vp) { vp = p; jp = j; }
-            if (q < vn) { vn = q; jn = j; }
-        }
-        const float z = vp - vn;
+        const TriSel s = tri_select(drow, ids, i, n);
+        const float z = s.z;
         zout[i] = z;
         loss[i] = soft ? logf(1.f + expf(z)) : fmaxf(z + margin, 0.f);
         // a masked maximum (no positive in the batch) carries no gradient
-        sel[2 * i] = (ids[jp] == yi && jp != i) ? jp : -1;
-        sel[2 * i + 1] = jn;
+        sel[2 * i] = s.has_pos ? s.jp : -1;
+        sel[2 * i + 1] = s.jn;
     }
 }
 
@@ -173,25 +151,10 @@ __global__ __launch_bounds__(256) void triplet_bwd_kernel(const float* __restric
                                                           const float* __restrict__ dloss, int soft,
                                                           float margin, float* __restrict__ df, int n,
                                                           int D4) {
-    const int r = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= D4) return;
-    const f32x4* F = reinterpret_cast<const f32x4*>(f);
-    const f32x4 fr = F[(int64_t)r * D4 + k];
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int i = 0; i < n; ++i) {
-        const int p = sel[2 * i], q = sel[2 * i + 1];
-        if (i != r && p != r && q != r) continue;      // workgroup-uniform
+    tri_bwd_rows(f, dist, sel, df, n, D4, [&](int i) {
         const float ez = expf(z[i]);
-        const float gz = dloss[i] * (soft ? ez / (1.f + ez) : (z[i] + margin > 0.f ? 1.f : 0.f));
-        const f32x4 fi = F[(int64_t)i * D4 + k];
-        if (i == r) {
-            if (p >= 0) acc += (fr - F[(int64_t)p * D4 + k]) * (gz / dist[(int64_t)i * n + p]);
-            acc -= (fr - F[(int64_t)q * D4 + k]) * (gz / dist[(int64_t)i * n + q]);
-        }
-        if (p == r && i != r) acc -= (fi - fr) * (gz / dist[(int64_t)i * n + r]);
-        if (q == r && i != r) acc += (fi - fr) * (gz / dist[(int64_t)i * n + r]);
-    }
-    reinterpret_cast<f32x4*>(df)[(int64_t)r * D4 + k] = acc;
+        return dloss[i] * (soft ? ez / (1.f + ez) : (z[i] + margin > 0.f ? 1.f : 0.f));
+    });
 }
 
 // ---- pair verification -------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """Mean teacher for unsupervised training on MI355X (Mean Teacher, Tarvainen & Valpola 2017; MMT, Ge et al.
 2020): a second copy of the CNN and the Siamese head that holds the exponential moving average of the student's weights,
-gives the soft targets of ``SoftClusterMemoryLoss`` and is the model one evaluates and clusters with.
+gives the soft targets of ``SoftClusterMemoryLoss`` and ``SoftTripletLoss`` and is the model one evaluates and clusters with.
 
 ``MeanTeacher.update()`` is ONE `grl_ema_update` launch over a device table of every float32 parameter and buffer of both
 modules (built once per model), then ``engine.touch_state`` on both copies: the kernel writes through raw pointers, which
@@ -180,14 +180,15 @@ class MeanTeacher(object):
 
 
 class MeanTeacherSEQTrainer(SEQTrainer):
-    """SEQTrainer's constructor plus ``teacher=`` (a ``MeanTeacher`` over ``cnn_model`` and ``siamese_model``) and
-    ``soft_weight=``; ``criterion_corr`` and ``criterion_uncorr`` are two ``SoftClusterMemoryLoss`` and are called as
-    ``criterion(feats, targets, teacher=rows, soft_weight=soft_weight)``.  ``train`` updates the teacher behind every
-    optimizer step."""
+    """SEQTrainer's constructor plus ``teacher=`` (a ``MeanTeacher`` over ``cnn_model`` and ``siamese_model``),
+    ``soft_weight=`` and ``tri_soft_weight=``; ``criterion_corr`` and ``criterion_uncorr`` are two ``SoftClusterMemoryLoss``
+    and are called as ``criterion(feats, targets, teacher=rows, soft_weight=soft_weight)``.  With ``tri_soft_weight`` != 0 the
+    batch-hard triplet term is an owned ``SoftTripletLoss`` against the teacher's ('corr', 'clip') rows; with
+    the default 0 it is SEQTrainer's.  ``train`` updates the teacher behind every optimizer step."""
 
     def __init__(self, cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr, criterion_uncorr, logdir,
-                 teacher=None, soft_weight=0.5):
-        from grl_amd.reid.loss import SoftClusterMemoryLoss
+                 teacher=None, soft_weight=0.5, tri_soft_weight=0.0):
+        from grl_amd.reid.loss import SoftClusterMemoryLoss, SoftTripletLoss
         for name, crit in (('criterion_corr', criterion_corr), ('criterion_uncorr', criterion_uncorr)):
             if not isinstance(crit, SoftClusterMemoryLoss):
                 raise ValueError('MeanTeacherSEQTrainer: %s must be a SoftClusterMemoryLoss (got %s)' % (name, type(crit).__name__))
@@ -198,16 +199,21 @@ class MeanTeacherSEQTrainer(SEQTrainer):
             raise ValueError('MeanTeacherSEQTrainer: teacher must be a MeanTeacher (got %s)' % type(teacher).__name__)
         if not 0.0 <= float(soft_weight) <= 1.0:
             raise ValueError('MeanTeacherSEQTrainer: soft_weight must be in [0, 1] (got %r)' % (soft_weight,))
+        if not 0.0 <= float(tri_soft_weight) <= 1.0:
+            raise ValueError('MeanTeacherSEQTrainer: tri_soft_weight must be in [0, 1] (got %r)' % (tri_soft_weight,))
         super(MeanTeacherSEQTrainer, self).__init__(cnn_model, siamese_model, siamese_model_uncorr, criterion_veri,
                                                     criterion_corr, criterion_uncorr, logdir)
         self.teacher = teacher
         self.soft_weight = float(soft_weight)
+        self.tri_soft_weight = float(tri_soft_weight)
+        self.criterion_soft_triplet = SoftTripletLoss()
         self._teacher_rows = None
 
     def _forward(self, inputs, targets, i, epoch):
         """The teacher's rows first, on the launch stream and BEFORE the base forks its side stream, which reads them (the
-        constraint of ``HybridSEQTrainer._parse_data``).  soft_weight = 0: no teacher pass, SEQTrainer's launches."""
-        self._teacher_rows = (self.teacher.rows(inputs[0], self.siamese_model_uncorr) if self.soft_weight != 0.0 else None)
+        constraint of ``HybridSEQTrainer._parse_data``).  Both weights 0: no teacher pass, SEQTrainer's launches."""
+        need = self.soft_weight != 0.0 or self.tri_soft_weight != 0.0
+        self._teacher_rows = self.teacher.rows(inputs[0], self.siamese_model_uncorr) if need else None
         return super(MeanTeacherSEQTrainer, self)._forward(inputs, targets, i, epoch)
 
     def _id_loss(self, criterion, feats, targets, rows):
@@ -215,6 +221,12 @@ class MeanTeacherSEQTrainer(SEQTrainer):
             return criterion(feats, targets, teacher=None, soft_weight=0.0)
         branch = 'uncorr' if criterion is self.criterion_uncorr else 'corr'
         return criterion(feats, targets, teacher=self._teacher_rows[(branch, rows)], soft_weight=self.soft_weight)
+
+    def _tri_loss(self, feats, target):
+        if self.tri_soft_weight == 0.0:
+            return super(MeanTeacherSEQTrainer, self)._tri_loss(feats, target)
+        return self.criterion_soft_triplet(feats, target, teacher=self._teacher_rows[('corr', 'clip')],
+                                           soft_weight=self.tri_soft_weight).mean()
 
     def train(self, epoch, data_loader, optimizer1):
         hook = optimizer1.register_step_post_hook(lambda *_: self.teacher.update())

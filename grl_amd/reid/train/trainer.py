@@ -256,6 +256,12 @@ class SEQTrainer(BaseTrainer):
         (``CameraSEQTrainer``: the rows' cameras)."""
         return criterion(feats, targets)
 
+    def _tri_loss(self, feats, target):
+        """The batch-hard triplet term of ``_forward`` on the correlated branch's clip rows (``criterion_triplet``, read when
+        called).  A subclass overrides it to hand the loss more than the targets (``MeanTeacherSEQTrainer``: the teacher's
+        rows)."""
+        return criterion_triplet(feats, target).mean()
+
     def _forward(self, inputs, targets, i, epoch):
         """trainer.py:107-170: id loss on frames + id loss on pooled clips (same LUT) +
         20 x pair verification + batch-hard triplet on the correlated branch, id loss on
@@ -289,7 +295,7 @@ class SEQTrainer(BaseTrainer):
         encode_scores, siamese_out = self.siamese_model(x_corr)
         corr_id_loss_vid, output_id = self._id_loss(self.criterion_corr, siamese_out, target, 'clip')
         corr_prec_id_vid = self._top1(output_id, target)
-        corr_loss_tri = criterion_triplet(siamese_out, target).mean()
+        corr_loss_tri = self._tri_loss(siamese_out, target)
         corr_loss_ver, _ = self.criterion_ver(self._pair_prob(encode_scores), tar_probe, tar_gallery)
 
         fk.join(uncorr_id_loss_vid, uncorr_prec_id_vid, siamese_out_u, encode_scores_u)

@@ -703,6 +703,27 @@ int grl_triplet_fwd(const float* feat, const int64_t* ids, int n, int D, int sof
 int grl_triplet_bwd(const float* feat, const float* dist, const int32_t* sel, const float* z,
                     const float* dloss, int soft, float margin, float* dfeat, int n, int D,
                     void* stream);
+/* The soft-margin batch-hard triplet loss blended with a mean teacher's soft target (soft_triplet.hip, SoftTripletLoss,
+ * DESIGN.md 4am; MMT's SoftTripletLoss, Ge et al. 2020).  Additive: GRL_ABI_VERSION stays 10.
+ * Student part: dist, sel and z are what grl_triplet_fwd(feat, ids, n, D, soft = 1, ...) writes, bit for bit (the same
+ * distance row, masks, first-index tie rule and sel[2i] = -1 rule; jp, jn below are the arg-max / arg-min it found).
+ * Teacher part (only when w_soft != 0), from tfeat [n][D], the teacher's rows of the same samples:
+ *   td(i, j) = sqrtf(sum_k (tf_i - tf_j)^2 + 1e-12f), in the student loop's lane stride and wave reduction,
+ *   tp = sel[2i] >= 0 ? td(i, jp) : 0,    tn = fl(td(i, jn) + 1e5f [ids[jn] == ids[i]]),    t = fl(tp - tn),
+ *   q[i] = 1 / (1 + expf(-t))             (finite at both ends: t = -1e5 gives 0),
+ * the student's masks mirrored; where every anchor has a positive and a different-id negative this is MMT's plain gather.
+ *   loss[i] = fl( logf(1 + expf(z)) - fl( fl(w_soft q) z ) )        -- in this order, no fused multiply-add.
+ * With w_soft = 0 tfeat is never read, q is not written (both may be NULL) and loss is grl_triplet_fwd's bit for bit.
+ * Backward: grl_triplet_bwd's gather form and term order with
+ *   gz = dloss[i] * fl( ez / (1 + ez) - fl(w_soft q[i]) ),   ez = expf(z[i]);
+ * with w_soft = 0 q is not read and dfeat is grl_triplet_bwd's (soft = 1) bit for bit.  The teacher gets no gradient.
+ * Limits, each refused with GRL_EINVAL before anything is launched: D % 4 != 0, n < 1, n > 16384, a NULL feat / ids /
+ * loss / dist / sel / z / dloss / dfeat, w_soft outside [0, 1] (a NaN included), w_soft != 0 with tfeat or q NULL.
+ * Forward: one launch, one 256-lane workgroup per anchor, LDS = n floats + 4 words.  Backward: one launch.  No atomics. */
+int grl_soft_triplet_fwd(const float* feat, const float* tfeat, const int64_t* ids, int n, int D, float w_soft,
+                         float* loss, float* dist, int32_t* sel, float* z, float* q, void* stream);
+int grl_soft_triplet_bwd(const float* feat, const float* dist, const int32_t* sel, const float* z, const float* q,
+                         const float* dloss, float w_soft, float* dfeat, int n, int D, void* stream);
 /* prob[t] = softmax(scores[t][0..1])[1] (reid/train/trainer.py:146-148; prob0, optional, keeps the
  * class-0 probability for the backward) and its backward, term for term as torch's softmax backward */
 int grl_softmax2(const float* scores, float* prob, float* prob0, int64_t m, void* stream);
