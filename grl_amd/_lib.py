@@ -156,6 +156,10 @@ _SIGNATURES = {
                       _fp, _fp, _fp, _fp], C.c_int),
     'grl_hybrid_ce': ([_fp, _i64, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _i64, _fp, _fp], C.c_int),
     'grl_soft_ce': ([_fp, _i64, _fp, _i64, _fp, C.c_float, C.c_int, C.c_int, _fp, _fp, _fp, _i64, _fp, _fp], C.c_int),
+    'grl_soft_hybrid_ce': ([_fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, C.c_float, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _i64,
+                            _fp, _fp], C.c_int),
+    'grl_soft_proxy_ce': ([_fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float,
+                           C.c_float, _fp, _fp, _fp, _i64, _fp, _fp, _fp, _fp], C.c_int),
     'grl_ema_update': ([_fp, _fp, C.c_int, C.c_float, C.c_float, _fp], C.c_int),
     'grl_softmax_ce': ([_fp, _i64, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _i64, _fp, _fp], C.c_int),
     'grl_oim_grad': ([_fp, _i64, _fp, _fp, C.c_float, _fp, C.c_int, C.c_int, C.c_int, _fp], C.c_int),

@@ -10,11 +10,10 @@
 #include <stdint.h>
 #include "../../include/grl_hip.h"
 #include "common.h"
+#include "hybrid_common.h"
 #include "ce_finish.h"
 
 namespace {
-
-constexpr int NONE = 0x7fffffff;
 
 // One workgroup per row.  The branch on the target is uniform across the workgroup.  dlogits comes out WITHOUT the 1 / nv
 // of the contract (ce_finish_kernel applies it): a row does not know the other rows' validity.
@@ -28,37 +27,15 @@ __global__ __launch_bounds__(256) void hybrid_ce_kernel(const float* __restrict_
     __shared__ float red[16];
     __shared__ int arg_s[4];
     const int i = blockIdx.x, tid = threadIdx.x;
-    const float* zi = z + (int64_t)i * ld;
     const int64_t y = targets[i];
     if (y < 0 || y >= C) {                                // invalid row
-        if (dz)
-            for (int j = tid; j < N; j += 256) dz[(int64_t)i * ldd + j] = 0.f;
-        if (tid == 0) { rows[i] = 0.f; rows[n + i] = 0.f; rows[2 * n + i] = 0.f; }
+        hyb_invalid_row(rows, n, i, dz, ldd, N);
         return;
     }
 
-    // ---- pass A: the class logits (a lane reads back only the entries it wrote until the first barrier) ----
-    float m = -INFINITY;
-    int am = NONE;
-    for (int c = tid; c < C; c += 256) {
-        const int e0 = cptr[c], e1 = cptr[c + 1];
-        float s = zi[cmem[e0]];                           // (classes are non-empty)
-        for (int e = e0 + 1; e < e1; ++e) s += zi[cmem[e]];
-        const float v = s / (float)(e1 - e0);             // a singleton: its logit, bit for bit
-        sz[c] = v;
-        if (v > m) { m = v; am = c; }
-    }
-    const float mx = block_max(m, red);
-    // first class attaining the maximum (grl_softmax_ce's tie rule)
-    int cand = (m == mx) ? am : NONE;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o));
-    if ((tid & 63) == 0) arg_s[tid >> 6] = cand;
-    float s = 0.f;
-    for (int c = tid; c < C; c += 256) s += expf(sz[c] - mx);
-    s = block_sum(s, red);                                // (its barriers also publish arg_s and sz)
-    const int arg = min(min(arg_s[0], arg_s[1]), min(arg_s[2], arg_s[3]));
-    const float lse = logf(s);                            // of the shifted class logits
+    // ---- pass A: the class logits, their maximum, arg-max and lse (hybrid_common.h) ----
+    const HybRow r = hyb_student_pass(z + (int64_t)i * ld, cptr, cmem, C, sz, red, arg_s);
+    const float mx = r.mx, lse = r.lse;
     const float zy = sz[y];
 
     // ---- pass B: every class's gradient once, in place; then the columns look their class up ----
@@ -69,12 +46,11 @@ __global__ __launch_bounds__(256) void hybrid_ce_kernel(const float* __restrict_
             sz[c] = (p - (c == (int)y ? 1.f : 0.f)) / (float)(cptr[c + 1] - cptr[c]);
         }
         __syncthreads();
-        float* di = dz + (int64_t)i * ldd;
-        for (int j = tid; j < N; j += 256) di[j] = sz[icls[j]];
+        hyb_scatter(dz + (int64_t)i * ldd, sz, icls, N);
     }
     if (tid == 0) {
         rows[i] = lse - (zy - mx);
-        rows[n + i] = arg == (int)y ? 1.f : 0.f;          // (a row of NaN has no arg-max)
+        rows[n + i] = r.arg == (int)y ? 1.f : 0.f;        // (a row of NaN has no arg-max)
         rows[2 * n + i] = 1.f;
     }
 }

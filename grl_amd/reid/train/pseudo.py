@@ -339,7 +339,9 @@ def train_unsupervised(trainer, evaluator, optimizer, tracklets, make_eval_loade
 
     A mean teacher needs nothing here: a ``MeanTeacherSEQTrainer`` with two ``SoftClusterMemoryLoss`` goes
     through the plain branch -- ``reset(centroids)`` is ``ClusterMemoryLoss``'s -- and the caller chooses the model that is
-    clustered by the evaluator it passes: ``ATTEvaluator(*teacher.models)`` clusters with the teacher.
+    clustered by the evaluator it passes: ``ATTEvaluator(*teacher.models)`` clusters with the teacher.  The same holds with
+    ``hybrid=True`` and ``cameras=True``: ``MeanTeacherHybridSEQTrainer`` / ``MeanTeacherCameraSEQTrainer`` and
+    their ``SoftHybridMemoryLoss`` / ``SoftProxyMemoryLoss`` are subclasses of what the checks above ask for.
 
     Returns the epochs' ``PseudoLabels``.  Under torch.distributed ``extract_feature`` gathers every row on every rank, so
     all ranks compute the same labels and seed the same memories."""

@@ -6,7 +6,8 @@ gives the soft targets of ``SoftClusterMemoryLoss`` and ``SoftTripletLoss`` and 
 modules (built once per model), then ``engine.touch_state`` on both copies: the kernel writes through raw pointers, which
 torch's version counters never see, and the packed eval plans (folded BatchNorms, re-laid weights) must be rebuilt before the
 teacher's next forward.  ``MeanTeacherSEQTrainer`` is SEQTrainer with the teacher's rows handed to its identity criteria and
-the update hooked behind ``optimizer.step()``.  There is no CPU path."""
+the update hooked behind ``optimizer.step()``; ``MeanTeacherHybridSEQTrainer`` and ``MeanTeacherCameraSEQTrainer`` are the same
+on ``HybridSEQTrainer`` and ``CameraSEQTrainer``, all three through ``MeanTeacherMixin``.  There is no CPU path."""
 import copy
 import ctypes as C
 
@@ -15,6 +16,8 @@ import torch
 from grl_amd import dist as grl_dist
 from grl_amd._lib import ptr, GrlEmaEntry, EMA_CHUNK
 from grl_amd.reid.loss.oim import _call
+from grl_amd.reid.train.camera import CameraSEQTrainer
+from grl_amd.reid.train.hybrid import HybridSEQTrainer
 from grl_amd.reid.train.trainer import SEQTrainer
 
 
@@ -179,7 +182,70 @@ class MeanTeacher(object):
                     ('corr', 'clip'): self.siamese(x_corr)[1]}
 
 
-class MeanTeacherSEQTrainer(SEQTrainer):
+class MeanTeacherMixin(object):
+    """The teacher's part of a trainer's step, in front of any SEQTrainer in the method resolution order
+    (``MeanTeacherSEQTrainer``, ``MeanTeacherHybridSEQTrainer``, ``MeanTeacherCameraSEQTrainer``): the teacher's rows fetched
+    before the base's forward, the identity criteria called with ``teacher=`` / ``soft_weight=`` next to what the base hands
+    them, the soft triplet term, and the teacher's update hooked behind ``optimizer.step()``.  ``GraphedTrainStep`` refuses
+    every trainer that carries it."""
+
+    def _init_teacher(self, who, soft_class, criterion_corr, criterion_uncorr, teacher, soft_weight, tri_soft_weight):
+        """The constructor's checks, each a ValueError naming the argument, before anything is stored."""
+        for name, crit in (('criterion_corr', criterion_corr), ('criterion_uncorr', criterion_uncorr)):
+            if not isinstance(crit, soft_class):
+                raise ValueError('%s: %s must be a %s (got %s)' % (who, name, soft_class.__name__, type(crit).__name__))
+        if criterion_corr is criterion_uncorr:
+            raise ValueError('%s: criterion_corr and criterion_uncorr must be two objects (the criterion '
+                             "decides which branch's teacher rows it is given)" % who)
+        if not isinstance(teacher, MeanTeacher):
+            raise ValueError('%s: teacher must be a MeanTeacher (got %s)' % (who, type(teacher).__name__))
+        if not 0.0 <= float(soft_weight) <= 1.0:
+            raise ValueError('%s: soft_weight must be in [0, 1] (got %r)' % (who, soft_weight))
+        if not 0.0 <= float(tri_soft_weight) <= 1.0:
+            raise ValueError('%s: tri_soft_weight must be in [0, 1] (got %r)' % (who, tri_soft_weight))
+
+    def _set_teacher(self, teacher, soft_weight, tri_soft_weight):
+        from grl_amd.reid.loss import SoftTripletLoss
+        self.teacher = teacher
+        self.soft_weight = float(soft_weight)
+        self.tri_soft_weight = float(tri_soft_weight)
+        self.criterion_soft_triplet = SoftTripletLoss()
+        self._teacher_rows = None
+
+    def _id_extra(self, rows):
+        """What the base trainer hands its identity criteria besides the targets, as keyword arguments."""
+        return {}
+
+    def _forward(self, inputs, targets, i, epoch):
+        """The teacher's rows first, on the launch stream and BEFORE the base forks its side stream, which reads them (the
+        constraint of ``HybridSEQTrainer._parse_data``).  Both weights 0: no teacher pass, the base's launches."""
+        need = self.soft_weight != 0.0 or self.tri_soft_weight != 0.0
+        self._teacher_rows = self.teacher.rows(inputs[0], self.siamese_model_uncorr) if need else None
+        return super(MeanTeacherMixin, self)._forward(inputs, targets, i, epoch)
+
+    def _id_loss(self, criterion, feats, targets, rows):
+        if self._teacher_rows is None:
+            return criterion(feats, targets, teacher=None, soft_weight=0.0, **self._id_extra(rows))
+        branch = 'uncorr' if criterion is self.criterion_uncorr else 'corr'
+        return criterion(feats, targets, teacher=self._teacher_rows[(branch, rows)], soft_weight=self.soft_weight,
+                         **self._id_extra(rows))
+
+    def _tri_loss(self, feats, target):
+        if self.tri_soft_weight == 0.0:
+            return super(MeanTeacherMixin, self)._tri_loss(feats, target)
+        return self.criterion_soft_triplet(feats, target, teacher=self._teacher_rows[('corr', 'clip')],
+                                           soft_weight=self.tri_soft_weight).mean()
+
+    def train(self, epoch, data_loader, optimizer1):
+        hook = optimizer1.register_step_post_hook(lambda *_: self.teacher.update())
+        try:
+            super(MeanTeacherMixin, self).train(epoch, data_loader, optimizer1)
+        finally:
+            hook.remove()
+            self._teacher_rows = None
+
+
+class MeanTeacherSEQTrainer(MeanTeacherMixin, SEQTrainer):
     """SEQTrainer's constructor plus ``teacher=`` (a ``MeanTeacher`` over ``cnn_model`` and ``siamese_model``),
     ``soft_weight=`` and ``tri_soft_weight=``; ``criterion_corr`` and ``criterion_uncorr`` are two ``SoftClusterMemoryLoss``
     and are called as ``criterion(feats, targets, teacher=rows, soft_weight=soft_weight)``.  With ``tri_soft_weight`` != 0 the
@@ -188,50 +254,46 @@ class MeanTeacherSEQTrainer(SEQTrainer):
 
     def __init__(self, cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr, criterion_uncorr, logdir,
                  teacher=None, soft_weight=0.5, tri_soft_weight=0.0):
-        from grl_amd.reid.loss import SoftClusterMemoryLoss, SoftTripletLoss
-        for name, crit in (('criterion_corr', criterion_corr), ('criterion_uncorr', criterion_uncorr)):
-            if not isinstance(crit, SoftClusterMemoryLoss):
-                raise ValueError('MeanTeacherSEQTrainer: %s must be a SoftClusterMemoryLoss (got %s)' % (name, type(crit).__name__))
-        if criterion_corr is criterion_uncorr:
-            raise ValueError('MeanTeacherSEQTrainer: criterion_corr and criterion_uncorr must be two objects (the criterion '
-                             "decides which branch's teacher rows it is given)")
-        if not isinstance(teacher, MeanTeacher):
-            raise ValueError('MeanTeacherSEQTrainer: teacher must be a MeanTeacher (got %s)' % type(teacher).__name__)
-        if not 0.0 <= float(soft_weight) <= 1.0:
-            raise ValueError('MeanTeacherSEQTrainer: soft_weight must be in [0, 1] (got %r)' % (soft_weight,))
-        if not 0.0 <= float(tri_soft_weight) <= 1.0:
-            raise ValueError('MeanTeacherSEQTrainer: tri_soft_weight must be in [0, 1] (got %r)' % (tri_soft_weight,))
+        from grl_amd.reid.loss import SoftClusterMemoryLoss
+        self._init_teacher('MeanTeacherSEQTrainer', SoftClusterMemoryLoss, criterion_corr, criterion_uncorr, teacher,
+                           soft_weight, tri_soft_weight)
         super(MeanTeacherSEQTrainer, self).__init__(cnn_model, siamese_model, siamese_model_uncorr, criterion_veri,
                                                     criterion_corr, criterion_uncorr, logdir)
-        self.teacher = teacher
-        self.soft_weight = float(soft_weight)
-        self.tri_soft_weight = float(tri_soft_weight)
-        self.criterion_soft_triplet = SoftTripletLoss()
-        self._teacher_rows = None
+        self._set_teacher(teacher, soft_weight, tri_soft_weight)
 
-    def _forward(self, inputs, targets, i, epoch):
-        """The teacher's rows first, on the launch stream and BEFORE the base forks its side stream, which reads them (the
-        constraint of ``HybridSEQTrainer._parse_data``).  Both weights 0: no teacher pass, SEQTrainer's launches."""
-        need = self.soft_weight != 0.0 or self.tri_soft_weight != 0.0
-        self._teacher_rows = self.teacher.rows(inputs[0], self.siamese_model_uncorr) if need else None
-        return super(MeanTeacherSEQTrainer, self)._forward(inputs, targets, i, epoch)
 
-    def _id_loss(self, criterion, feats, targets, rows):
-        if self._teacher_rows is None:
-            return criterion(feats, targets, teacher=None, soft_weight=0.0)
-        branch = 'uncorr' if criterion is self.criterion_uncorr else 'corr'
-        return criterion(feats, targets, teacher=self._teacher_rows[(branch, rows)], soft_weight=self.soft_weight)
+class MeanTeacherHybridSEQTrainer(MeanTeacherMixin, HybridSEQTrainer):
+    """``HybridSEQTrainer`` with a mean teacher (DESIGN.md 4an): ``MeanTeacherSEQTrainer``'s three extra arguments;
+    ``criterion_corr`` and ``criterion_uncorr`` are two ``SoftHybridMemoryLoss`` and are called as
+    ``criterion(feats, targets, index=index, teacher=rows, soft_weight=soft_weight)``.  Batches carry their instance indices
+    as ``HybridSEQTrainer``'s do."""
 
-    def _tri_loss(self, feats, target):
-        if self.tri_soft_weight == 0.0:
-            return super(MeanTeacherSEQTrainer, self)._tri_loss(feats, target)
-        return self.criterion_soft_triplet(feats, target, teacher=self._teacher_rows[('corr', 'clip')],
-                                           soft_weight=self.tri_soft_weight).mean()
+    def __init__(self, cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr, criterion_uncorr, logdir,
+                 teacher=None, soft_weight=0.5, tri_soft_weight=0.0):
+        from grl_amd.reid.loss import SoftHybridMemoryLoss
+        self._init_teacher('MeanTeacherHybridSEQTrainer', SoftHybridMemoryLoss, criterion_corr, criterion_uncorr, teacher,
+                           soft_weight, tri_soft_weight)
+        super(MeanTeacherHybridSEQTrainer, self).__init__(cnn_model, siamese_model, siamese_model_uncorr, criterion_veri,
+                                                          criterion_corr, criterion_uncorr, logdir)
+        self._set_teacher(teacher, soft_weight, tri_soft_weight)
 
-    def train(self, epoch, data_loader, optimizer1):
-        hook = optimizer1.register_step_post_hook(lambda *_: self.teacher.update())
-        try:
-            super(MeanTeacherSEQTrainer, self).train(epoch, data_loader, optimizer1)
-        finally:
-            hook.remove()
-            self._teacher_rows = None
+    def _id_extra(self, rows):
+        return {'index': self._index_rows[rows]}
+
+
+class MeanTeacherCameraSEQTrainer(MeanTeacherMixin, CameraSEQTrainer):
+    """``CameraSEQTrainer`` with a mean teacher (DESIGN.md 4an): ``MeanTeacherSEQTrainer``'s three extra arguments;
+    ``criterion_corr`` and ``criterion_uncorr`` are two ``SoftProxyMemoryLoss`` and are called as
+    ``criterion(feats, targets, cams=cams, teacher=rows, soft_weight=soft_weight)``."""
+
+    def __init__(self, cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr, criterion_uncorr, logdir,
+                 teacher=None, soft_weight=0.5, tri_soft_weight=0.0):
+        from grl_amd.reid.loss import SoftProxyMemoryLoss
+        self._init_teacher('MeanTeacherCameraSEQTrainer', SoftProxyMemoryLoss, criterion_corr, criterion_uncorr, teacher,
+                           soft_weight, tri_soft_weight)
+        super(MeanTeacherCameraSEQTrainer, self).__init__(cnn_model, siamese_model, siamese_model_uncorr, criterion_veri,
+                                                          criterion_corr, criterion_uncorr, logdir)
+        self._set_teacher(teacher, soft_weight, tri_soft_weight)
+
+    def _id_extra(self, rows):
+        return {'cams': self._cam_rows[rows]}

@@ -25,10 +25,11 @@ class GraphedTrainStep(object):
         The capture itself executes nothing."""
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             raise RuntimeError('GraphedTrainStep captures a single-GPU step (the RCCL gradient exchange is not captured)')
-        from .reid.train.teacher import MeanTeacherSEQTrainer
-        if isinstance(trainer, MeanTeacherSEQTrainer):
-            raise ValueError('GraphedTrainStep does not capture a MeanTeacherSEQTrainer step: the teacher\'s eval forward and '
-                             'its update after the optimizer step are not part of the captured graph (DESIGN.md 4al)')
+        from .reid.train.teacher import MeanTeacherMixin
+        if isinstance(trainer, MeanTeacherMixin):
+            raise ValueError('GraphedTrainStep does not capture a %s step: the teacher\'s eval forward and '
+                             'its update after the optimizer step are not part of the captured graph (DESIGN.md 4al)'
+                             % type(trainer).__name__)
         self.trainer, self.opt = trainer, optimizer
         self.mods = (trainer.model, trainer.siamese_model, trainer.siamese_model_uncorr)
         self.clips, self.pids = clips.clone(), pids.clone()

@@ -657,6 +657,74 @@ int grl_soft_ce(const float* logits, int64_t ld, const float* tlogits, int64_t l
                 float w_soft, int n, int c, float* loss, float* correct, float* dlogits, int64_t ldd,
                 float* ws, void* stream);
 
+/* Hybrid-memory cross entropy against a hard class blended with a teacher's softmax over the same classes
+ * (soft_hybrid.hip, SoftHybridMemoryLoss): grl_hybrid_ce's classes with grl_soft_ce's target, forward and
+ * gradient in one call.  Additive: GRL_ABI_VERSION stays 10.  logits [n][ld] and tlogits [n][ldt] (N columns used of
+ * each) are the student's and the teacher's scaled similarities to the same N instance-memory rows; targets and the class
+ * tables are grl_hybrid_ce's, with the same validity rule and the same caller-side validation.
+ * For a valid row i with target y, w = w_soft, omw = fl(1 - w):
+ *   z_c = grl_hybrid_ce's: logits[i][j] over the members j of c, added one by one in list order from the first member,
+ *         / (float)|c|;  t_c = the same formula on tlogits[i].
+ *   mx = max_c z_c;  lse = logf(sum_c expf(z_c - mx));  p_c = expf(fl(fl(z_c - mx) - lse))
+ *   mt = max_c t_c;  lt  = logf(sum_c expf(t_c - mt));  q_c = expf(fl(fl(t_c - mt) - lt))
+ *   X   = sum_c fl(q_c * fl(z_c - mx))
+ *   L_i = fl(fl(lse - fl(omw * fl(z_y - mx))) - fl(w * X))
+ *   d_c = fl(fl(p_c - fl(omw * [c == y])) - fl(w * q_c))
+ * With w = 0 the terms in w are not evaluated, tlogits is never read (it may be NULL) and only the first 3 n floats of ws
+ * are touched.
+ * nv = the number of valid rows.  loss[0] = sum over the valid rows of fl(fl(1 / nv) L_i), added in index order from 0
+ * (0 if nv = 0).  dlogits[i][j] (may be NULL) = fl(fl(1 / nv) * fl(d_c / (float)|c|)) with c = inst_class[j]; the teacher
+ * gets no gradient.
+ * correct[0] (may be NULL) = the number of valid rows whose arg-max CLASS of the STUDENT equals y (first class on ties).
+ * ws: 3 * n floats of scratch when w_soft = 0, 3 * n + n * C floats otherwise -- the student's z fills the LDS budget, so
+ *   the teacher's class logits (then q) of row i live in ws[3 n + i C ..); lane t writes and reads back the entries
+ *   t + 256 k only.
+ * With w_soft = 0, loss, dlogits and correct are grl_hybrid_ce's bit for bit.  With C = N singleton classes in identity
+ * order they are grl_soft_ce's bit for bit, as grl_hybrid_ce's are grl_softmax_ce's.
+ * Limits, each refused with GRL_EINVAL before anything is launched: everything grl_hybrid_ce refuses (C >
+ * GRL_HYBRID_MAX_CLASSES included: no LDS opt-in is taken), w_soft outside [0, 1] (a NaN included), w_soft != 0 with
+ * tlogits NULL or ldt < N.
+ * A NaN logit gives unspecified values, never an access outside the arrays.
+ * Two launches.  First one 256-lane workgroup per row: lane t takes the classes t + 256 k, adding its terms in that order
+ * from 0; every max and sum is a wave64 xor tree followed by the four waves' totals in sequence, as grl_hybrid_ce.  The
+ * second launch is grl_proxy_ce's.  No atomics: the same bits on every run. */
+int grl_soft_hybrid_ce(const float* logits, int64_t ld, const float* tlogits, int64_t ldt, const int64_t* targets,
+                       const int32_t* class_ptr, const int32_t* class_members, const int32_t* inst_class, float w_soft,
+                       int n, int N, int C, float* loss, float* correct, float* dlogits, int64_t ldd, float* ws,
+                       void* stream);
+
+/* Camera-aware proxy cross entropy against hard targets blended with a teacher's softmaxes (soft_proxy.hip,
+ * SoftProxyMemoryLoss): grl_proxy_ce's two cross entropies, each against (1 - w) its hard target + w the
+ * teacher's softmax over the same set.  Additive: GRL_ABI_VERSION stays 10.  tlogits [n][ldt] (P columns used) are the
+ * teacher's scaled similarities to the same P proxies; every other argument is grl_proxy_ce's.
+ * own_i, A_i, Pos_i, N_i, Neg_i, U_i, negsel and correct come from the STUDENT's logits exactly as in grl_proxy_ce; the
+ * teacher is read at the student's selection (the rule of grl_soft_triplet_fwd).
+ * For a valid row, z = logits[i], t = tlogits[i], w = w_soft, omw = fl(1 - w), S one of A_i, U_i:
+ *   mx_S = max_{j in S} z_j;  lse_S = logf(sum_{j in S} expf(z_j - mx_S));  p^S_j = expf(fl(fl(z_j - mx_S) - lse_S))
+ *   mt_S = max_{j in S} t_j;  lt_S  = logf(sum_{j in S} expf(t_j - mt_S));  q^S_j = expf(fl(fl(t_j - mt_S) - lt_S))
+ *   X_S  = sum_{j in S} fl(q^S_j * fl(z_j - mx_S))
+ *   h_A  = fl(z[own_i] - mx_A);   h_U = fl((sum_{j in Pos_i} fl(z_j - mx_U)) * fl(1 / |Pos_i|))
+ *   L_S  = fl(fl(lse_S - fl(omw * h_S)) - fl(w * X_S))
+ *   L_i  = fl(fl(w_intra * L_A) + fl(w_inter * L_U))
+ *        = w_intra (lse_A(z) - (1 - w) z[own] - w sum_A q^A_j z_j) + w_inter (lse_U(z) - (1 - w) mean_Pos z - w sum_U q^U_j z_j):
+ *          both target vectors sum to 1, so the shifts cancel.
+ *   g^A_j = fl(fl(p^A_j - fl(omw * [j == own_i])) - fl(w * q^A_j)),
+ *   g^U_j = fl(fl(p^U_j - fl(omw * ([j in Pos_i] ? fl(1 / |Pos_i|) : 0))) - fl(w * q^U_j))
+ *   d_ij  = fl([j in A_i] fl(w_intra * g^A_j) + [j in U_i] fl(w_inter * g^U_j))
+ * With w = 0 the terms in w are not evaluated and tlogits is never read (it may be NULL).
+ * loss, dlogits (= fl(fl(1 / nv) d_ij)), correct, own, negsel and ws (3 * n floats) are laid out as grl_proxy_ce's.
+ * With w_soft = 0 every output is grl_proxy_ce's bit for bit.
+ * Limits, each refused with GRL_EINVAL before anything is launched: everything grl_proxy_ce refuses, w_soft outside
+ * [0, 1] (a NaN included), w_soft != 0 with tlogits NULL or ldt < P.  The teacher's row stays in global memory:
+ * GRL_PROXY_MAX_P and the LDS budget are grl_proxy_ce's.
+ * A NaN logit gives unspecified values, never an access outside the arrays.
+ * Two launches, as grl_proxy_ce: lane t takes the columns t + 256 k, adding its terms in that order from 0; every max, sum
+ * and count is a wave64 xor tree followed by the four waves' totals in sequence.  No atomics: the same bits on every run. */
+int grl_soft_proxy_ce(const float* logits, int64_t ld, const float* tlogits, int64_t ldt, const int64_t* labels,
+                      const int64_t* cams, const int32_t* proxy_cluster, const int32_t* proxy_cam, float w_soft, int n,
+                      int P, int k_neg, float w_intra, float w_inter, float* loss, float* correct, float* dlogits,
+                      int64_t ldd, int64_t* own, int32_t* negsel, float* ws, void* stream);
+
 /* Exponential moving average of a set of tensors in ONE launch (ema.hip, MeanTeacher).  Additive:
  * GRL_ABI_VERSION stays 10.  table_dev: `count` entries in DEVICE memory, built once per model by the host; for every
  * entry and every element
