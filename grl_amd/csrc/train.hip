@@ -1977,6 +1977,13 @@ extern "C" int grl_conv_wgrad_f32(const GrlWgrad* desc, void* stream) {
     } else {
         GRL_REQUIRE(d.ldx % 4 == 0, "wgrad: ldx % 4");
     }
+    // (every argument check sits in front of the first launch: a rejected call launches nothing)
+    const int taps = d.conv ? d.kh * d.kw : 1;
+    const int Cc = d.conv ? d.C : d.K;
+    const int kout = d.k_out > 0 ? d.k_out : d.K;      // stem: K padded to 160, 147 real
+    GRL_REQUIRE(taps == 1 || kout == d.K, "wgrad conv: k_out is a dense-only option");
+    GRL_REQUIRE(kout == d.K || ((uintptr_t)d.dw & 3) == 0, "wgrad: dw alignment");
+    GRL_REQUIRE(kout != d.K || taps > 1 || ((uintptr_t)d.dw & 15) == 0, "wgrad: dw must be 16-byte aligned");
     int bm, bn;
     wgrad_tile(d, &bm, &bn);
     const int splits = wgrad_splits(d, bm, bn);
@@ -2023,12 +2030,6 @@ extern "C" int grl_conv_wgrad_f32(const GrlWgrad* desc, void* stream) {
     else if (bm == 64 && bn == 128) GRL_WGRAD_LAUNCH(64, 128);
     else GRL_WGRAD_LAUNCH(64, 64);
 #undef GRL_WGRAD_LAUNCH
-    const int taps = d.conv ? d.kh * d.kw : 1;
-    const int Cc = d.conv ? d.C : d.K;
-    const int kout = d.k_out > 0 ? d.k_out : d.K;      // stem: K padded to 160, 147 real
-    GRL_REQUIRE(taps == 1 || kout == d.K, "wgrad conv: k_out is a dense-only option");
-    GRL_REQUIRE(kout == d.K || ((uintptr_t)d.dw & 3) == 0, "wgrad: dw alignment");
-    GRL_REQUIRE(kout != d.K || taps > 1 || ((uintptr_t)d.dw & 15) == 0, "wgrad: dw must be 16-byte aligned");
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_even((int64_t)d.N * (d.K / 4))), dim3(256), 0, s, d.workspace,
                        real_splits, a.slab_stride, d.N, Cc, taps, d.K, d.dw, kout, d.accumulate);
     return grl_check_launch("grl_conv_wgrad_f32");

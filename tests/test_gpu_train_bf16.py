@@ -165,7 +165,12 @@ def test_bn_backward_and_column_statistics_twins(dev, M, Cc):
 
 @pytest.mark.parametrize('M,N,K,conv', [(4096, 128, 2048, None), (1000, 64, 64, None), (5000, 256, 64, None), (260, 2048, 128, None),
                                         (1024, 64, 160, None),
-                                        (4096, 512, 2048, None), (5000, 264, 520, None), (33, 256, 256, None),     # (the 256 x 256 LDS-DMA tile)
+                                        # wgrad_tile() takes the 256 x 256 LDS-DMA tile only when N >= 256, K >= 256 and
+                                        # N K >= 2^19: of the next three, (4096, 512, 2048) does; (5000, 264, 520) -- N K =
+                                        # 137 280 -- and (33, 256, 256) -- 65 536 -- run the 128 x 128 kernel, ragged.  Of the
+                                        # conv shapes below only the C = 512 3x3 (512 x 4608) takes the 256-wide tile.  Ragged
+                                        # and tap-straddling 256-wide tiles: test_gpu_wgrad_float64.py
+                                        (4096, 512, 2048, None), (5000, 264, 520, None), (33, 256, 256, None),
                                         (4 * 16 * 8, 512, 9 * 512, (16, 8, 512, 16, 8, 3, 3, 1, 1)),
                                         (2 * 16 * 8, 128, 9 * 128, (16, 8, 128, 16, 8, 3, 3, 1, 1)),
                                         (3 * 16 * 8, 64, 9 * 64, (16, 8, 64, 16, 8, 3, 3, 1, 1)),
