@@ -11,6 +11,7 @@ The hidden pids are only used to print how good the clusters were.  Run:
     PYTHONPATH=.:dropin python examples/train_unsupervised_synthetic.py --epochs 2 --hybrid-memory --self-paced 0.02
     PYTHONPATH=.:dropin python examples/train_unsupervised_synthetic.py --epochs 2 --mean-teacher 0.999 --soft-weight 0.5 --eval-teacher
     PYTHONPATH=.:dropin python examples/train_unsupervised_synthetic.py --epochs 2 --mean-teacher 0.999 --soft-weight 0.5 --soft-tri-weight 0.8
+    PYTHONPATH=.:dropin python examples/train_unsupervised_synthetic.py --epochs 2 --mean-teacher 0.999 --soft-weight 0.5 --ins-hard-weight 1 --ins-soft-weight 0.4
 
 (the second form: camera-aware proxies, one memory row per cluster and camera -- ProxyMemoryLoss under CameraSEQTrainer;
 the third: a hybrid memory with one row per tracklet, the samples the clustering calls noise trained on as classes of their
@@ -18,7 +19,8 @@ own, and only the clusters that are stable under eps -/+ 0.02 kept -- HybridMemo
 the fourth: a mean teacher -- an averaged copy of the model whose softmax over the cluster memory is a soft target next to
 the hard cluster id, SoftClusterMemoryLoss under MeanTeacherSEQTrainer, and with --eval-teacher the model that is evaluated
 and clustered with; the fifth: the teacher's distances at the student's batch-hard indices as a soft target of
-the triplet term too, SoftTripletLoss)
+the triplet term too, SoftTripletLoss; the sixth: the hard instance contrast and the soft instance consistency
+of the batch's rows against the teacher's, InstanceContrastLoss)
 
 Every identity is a low-frequency colour layout ("a person in front of a background", as grl_amd.synthetic.
 synth_clips_structured); a tracklet is a small deviation from its identity's layout, a frame a smaller one, plus pixel noise.
@@ -89,6 +91,9 @@ def refuse_conflicts(args):
         raise SystemExit('--soft-weight and --eval-teacher need --mean-teacher ALPHA')
     if args.mean_teacher is None and getattr(args, 'soft_tri_weight', None) is not None:
         raise SystemExit('--soft-tri-weight needs --mean-teacher ALPHA')
+    for flag in ('ins_hard_weight', 'ins_soft_weight', 'ins_tau'):
+        if args.mean_teacher is None and getattr(args, flag, None) is not None:
+            raise SystemExit('--%s needs --mean-teacher ALPHA' % flag.replace('_', '-'))
     if args.mean_teacher is not None and (args.camera_proxies or args.hybrid_memory):
         raise SystemExit('--mean-teacher is built for the plain cluster memory: it excludes --camera-proxies and '
                          '--hybrid-memory (DESIGN.md 4al, out of scope)')
@@ -146,7 +151,10 @@ def main(args):
         trainer = MeanTeacherSEQTrainer(cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr,
                                         criterion_uncorr, osp.join(args.logs_dir, 'train_log'), teacher=teacher,
                                         soft_weight=0.5 if args.soft_weight is None else args.soft_weight,
-                                        tri_soft_weight=0.0 if args.soft_tri_weight is None else args.soft_tri_weight)
+                                        tri_soft_weight=0.0 if args.soft_tri_weight is None else args.soft_tri_weight,
+                                        ins_hard_weight=0.0 if args.ins_hard_weight is None else args.ins_hard_weight,
+                                        ins_soft_weight=0.0 if args.ins_soft_weight is None else args.ins_soft_weight,
+                                        ins_tau=0.1 if args.ins_tau is None else args.ins_tau)
         teacher_evaluator = ATTEvaluator(*teacher.models, only_eval=False)
         if args.eval_teacher:                                # the teacher's features are clustered, and it is what is scored
             evaluator, student_evaluator = teacher_evaluator, evaluator
@@ -226,6 +234,13 @@ if __name__ == '__main__':
     ap.add_argument('--soft-tri-weight', type=float, default=None, metavar='W',
                     help="with --mean-teacher: weight of the teacher's soft target in the batch-hard triplet term, SoftTripletLoss "
                          '(DESIGN.md 4am; default 0: the hard triplet)')
+    ap.add_argument('--ins-hard-weight', type=float, default=None, metavar='W',
+                    help="with --mean-teacher: weight of the hard instance contrast against the teacher's rows, "
+                         'InstanceContrastLoss (DESIGN.md 4ao; default 0: off)')
+    ap.add_argument('--ins-soft-weight', type=float, default=None, metavar='W',
+                    help='with --mean-teacher: weight of the soft instance consistency (default 0: off)')
+    ap.add_argument('--ins-tau', type=float, default=None, metavar='T',
+                    help='with --mean-teacher: temperature of both instance terms (default 0.1)')
     ap.add_argument('--eval-teacher', action='store_true',
                     help='with --mean-teacher: evaluate and cluster with the teacher (ATTEvaluator on teacher.models)')
     ap.add_argument('--seed', type=int, default=0)

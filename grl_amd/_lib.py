@@ -167,6 +167,8 @@ _SIGNATURES = {
     'grl_triplet_bwd': ([_fp] * 5 + [C.c_int, C.c_float, _fp, C.c_int, C.c_int, _fp], C.c_int),
     'grl_soft_triplet_fwd': ([_fp, _fp, _fp, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp, _fp, _fp, _fp], C.c_int),
     'grl_soft_triplet_bwd': ([_fp] * 6 + [C.c_float, _fp, C.c_int, C.c_int, _fp], C.c_int),
+    'grl_ins_contrast_fwd': ([_fp, _fp, _fp, C.c_int, C.c_int] + [C.c_float] * 4 + [_fp] * 5, C.c_int),
+    'grl_ins_contrast_bwd': ([_fp] * 4 + [C.c_float, _fp, C.c_int, C.c_int, _fp], C.c_int),
     'grl_softmax2': ([_fp, _fp, _fp, _i64, _fp], C.c_int),
     'grl_softmax2_bwd': ([_fp, _fp, _fp, _fp, _i64, _fp], C.c_int),
     'grl_normalize_u8': ([_fp, _fp, _fp, C.c_int, _i64, _fp], C.c_int),

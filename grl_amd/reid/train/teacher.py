@@ -1,6 +1,7 @@
 """Mean teacher for unsupervised training on MI355X (Mean Teacher, Tarvainen & Valpola 2017; MMT, Ge et al.
 2020): a second copy of the CNN and the Siamese head that holds the exponential moving average of the student's weights,
-gives the soft targets of ``SoftClusterMemoryLoss`` and ``SoftTripletLoss`` and is the model one evaluates and clusters with.
+gives the soft targets of ``SoftClusterMemoryLoss`` and ``SoftTripletLoss`` and the rows ``InstanceContrastLoss`` contrasts the
+batch against, and is the model one evaluates and clusters with.
 
 ``MeanTeacher.update()`` is ONE `grl_ema_update` launch over a device table of every float32 parameter and buffer of both
 modules (built once per model), then ``engine.touch_state`` on both copies: the kernel writes through raw pointers, which
@@ -187,10 +188,16 @@ class MeanTeacherMixin(object):
     (``MeanTeacherSEQTrainer``, ``MeanTeacherHybridSEQTrainer``, ``MeanTeacherCameraSEQTrainer``): the teacher's rows fetched
     before the base's forward, the identity criteria called with ``teacher=`` / ``soft_weight=`` next to what the base hands
     them, the soft triplet term, and the teacher's update hooked behind ``optimizer.step()``.  ``GraphedTrainStep`` refuses
-    every trainer that carries it."""
+    every trainer that carries it.  With ``ins_hard_weight`` / ``ins_soft_weight`` != 0 the triplet term is followed by an owned
+    ``InstanceContrastLoss`` on the same rows; with the defaults 0 nothing is called."""
 
-    def _init_teacher(self, who, soft_class, criterion_corr, criterion_uncorr, teacher, soft_weight, tri_soft_weight):
+    ins_hard_weight = 0.0
+    ins_soft_weight = 0.0
+
+    def _init_teacher(self, who, soft_class, criterion_corr, criterion_uncorr, teacher, soft_weight, tri_soft_weight,
+                      ins_hard_weight=0.0, ins_soft_weight=0.0, ins_tau=0.1, ins_teacher_tau=None):
         """The constructor's checks, each a ValueError naming the argument, before anything is stored."""
+        from grl_amd.reid.loss.ins_contrast import check_ins_weights, check_temperature
         for name, crit in (('criterion_corr', criterion_corr), ('criterion_uncorr', criterion_uncorr)):
             if not isinstance(crit, soft_class):
                 raise ValueError('%s: %s must be a %s (got %s)' % (who, name, soft_class.__name__, type(crit).__name__))
@@ -203,13 +210,22 @@ class MeanTeacherMixin(object):
             raise ValueError('%s: soft_weight must be in [0, 1] (got %r)' % (who, soft_weight))
         if not 0.0 <= float(tri_soft_weight) <= 1.0:
             raise ValueError('%s: tri_soft_weight must be in [0, 1] (got %r)' % (who, tri_soft_weight))
+        check_ins_weights(ins_hard_weight, ins_soft_weight, who=who, names=('ins_hard_weight', 'ins_soft_weight'),
+                          allow_both_zero=True)
+        check_temperature('ins_tau', ins_tau, who=who)
+        if ins_teacher_tau is not None:
+            check_temperature('ins_teacher_tau', ins_teacher_tau, who=who)
 
-    def _set_teacher(self, teacher, soft_weight, tri_soft_weight):
-        from grl_amd.reid.loss import SoftTripletLoss
+    def _set_teacher(self, teacher, soft_weight, tri_soft_weight, ins_hard_weight=0.0, ins_soft_weight=0.0, ins_tau=0.1,
+                     ins_teacher_tau=None):
+        from grl_amd.reid.loss import SoftTripletLoss, InstanceContrastLoss
         self.teacher = teacher
         self.soft_weight = float(soft_weight)
         self.tri_soft_weight = float(tri_soft_weight)
         self.criterion_soft_triplet = SoftTripletLoss()
+        self.ins_hard_weight = float(ins_hard_weight)
+        self.ins_soft_weight = float(ins_soft_weight)
+        self.criterion_ins = InstanceContrastLoss(tau=ins_tau, teacher_tau=ins_teacher_tau)
         self._teacher_rows = None
 
     def _id_extra(self, rows):
@@ -219,7 +235,8 @@ class MeanTeacherMixin(object):
     def _forward(self, inputs, targets, i, epoch):
         """The teacher's rows first, on the launch stream and BEFORE the base forks its side stream, which reads them (the
         constraint of ``HybridSEQTrainer._parse_data``).  Both weights 0: no teacher pass, the base's launches."""
-        need = self.soft_weight != 0.0 or self.tri_soft_weight != 0.0
+        need = (self.soft_weight != 0.0 or self.tri_soft_weight != 0.0 or self.ins_hard_weight != 0.0
+                or self.ins_soft_weight != 0.0)
         self._teacher_rows = self.teacher.rows(inputs[0], self.siamese_model_uncorr) if need else None
         return super(MeanTeacherMixin, self)._forward(inputs, targets, i, epoch)
 
@@ -232,9 +249,14 @@ class MeanTeacherMixin(object):
 
     def _tri_loss(self, feats, target):
         if self.tri_soft_weight == 0.0:
-            return super(MeanTeacherMixin, self)._tri_loss(feats, target)
-        return self.criterion_soft_triplet(feats, target, teacher=self._teacher_rows[('corr', 'clip')],
-                                           soft_weight=self.tri_soft_weight).mean()
+            tri = super(MeanTeacherMixin, self)._tri_loss(feats, target)
+        else:
+            tri = self.criterion_soft_triplet(feats, target, teacher=self._teacher_rows[('corr', 'clip')],
+                                              soft_weight=self.tri_soft_weight).mean()
+        if self.ins_hard_weight == 0.0 and self.ins_soft_weight == 0.0:
+            return tri
+        return tri + self.criterion_ins(feats, target, teacher=self._teacher_rows[('corr', 'clip')],
+                                        hard_weight=self.ins_hard_weight, soft_weight=self.ins_soft_weight).mean()
 
     def train(self, epoch, data_loader, optimizer1):
         hook = optimizer1.register_step_post_hook(lambda *_: self.teacher.update())
@@ -250,16 +272,19 @@ class MeanTeacherSEQTrainer(MeanTeacherMixin, SEQTrainer):
     ``soft_weight=`` and ``tri_soft_weight=``; ``criterion_corr`` and ``criterion_uncorr`` are two ``SoftClusterMemoryLoss``
     and are called as ``criterion(feats, targets, teacher=rows, soft_weight=soft_weight)``.  With ``tri_soft_weight`` != 0 the
     batch-hard triplet term is an owned ``SoftTripletLoss`` against the teacher's ('corr', 'clip') rows; with
-    the default 0 it is SEQTrainer's.  ``train`` updates the teacher behind every optimizer step."""
+    the default 0 it is SEQTrainer's.  With ``ins_hard_weight`` / ``ins_soft_weight`` != 0 (temperatures ``ins_tau``,
+    ``ins_teacher_tau``; None: ``ins_tau``) an owned ``InstanceContrastLoss`` on the same rows is added to it.
+    ``train`` updates the teacher behind every optimizer step."""
 
     def __init__(self, cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr, criterion_uncorr, logdir,
-                 teacher=None, soft_weight=0.5, tri_soft_weight=0.0):
+                 teacher=None, soft_weight=0.5, tri_soft_weight=0.0, ins_hard_weight=0.0, ins_soft_weight=0.0, ins_tau=0.1,
+                 ins_teacher_tau=None):
         from grl_amd.reid.loss import SoftClusterMemoryLoss
         self._init_teacher('MeanTeacherSEQTrainer', SoftClusterMemoryLoss, criterion_corr, criterion_uncorr, teacher,
-                           soft_weight, tri_soft_weight)
+                           soft_weight, tri_soft_weight, ins_hard_weight, ins_soft_weight, ins_tau, ins_teacher_tau)
         super(MeanTeacherSEQTrainer, self).__init__(cnn_model, siamese_model, siamese_model_uncorr, criterion_veri,
                                                     criterion_corr, criterion_uncorr, logdir)
-        self._set_teacher(teacher, soft_weight, tri_soft_weight)
+        self._set_teacher(teacher, soft_weight, tri_soft_weight, ins_hard_weight, ins_soft_weight, ins_tau, ins_teacher_tau)
 
 
 class MeanTeacherHybridSEQTrainer(MeanTeacherMixin, HybridSEQTrainer):
@@ -269,13 +294,14 @@ class MeanTeacherHybridSEQTrainer(MeanTeacherMixin, HybridSEQTrainer):
     as ``HybridSEQTrainer``'s do."""
 
     def __init__(self, cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr, criterion_uncorr, logdir,
-                 teacher=None, soft_weight=0.5, tri_soft_weight=0.0):
+                 teacher=None, soft_weight=0.5, tri_soft_weight=0.0, ins_hard_weight=0.0, ins_soft_weight=0.0, ins_tau=0.1,
+                 ins_teacher_tau=None):
         from grl_amd.reid.loss import SoftHybridMemoryLoss
         self._init_teacher('MeanTeacherHybridSEQTrainer', SoftHybridMemoryLoss, criterion_corr, criterion_uncorr, teacher,
-                           soft_weight, tri_soft_weight)
+                           soft_weight, tri_soft_weight, ins_hard_weight, ins_soft_weight, ins_tau, ins_teacher_tau)
         super(MeanTeacherHybridSEQTrainer, self).__init__(cnn_model, siamese_model, siamese_model_uncorr, criterion_veri,
                                                           criterion_corr, criterion_uncorr, logdir)
-        self._set_teacher(teacher, soft_weight, tri_soft_weight)
+        self._set_teacher(teacher, soft_weight, tri_soft_weight, ins_hard_weight, ins_soft_weight, ins_tau, ins_teacher_tau)
 
     def _id_extra(self, rows):
         return {'index': self._index_rows[rows]}
@@ -287,13 +313,14 @@ class MeanTeacherCameraSEQTrainer(MeanTeacherMixin, CameraSEQTrainer):
     ``criterion(feats, targets, cams=cams, teacher=rows, soft_weight=soft_weight)``."""
 
     def __init__(self, cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr, criterion_uncorr, logdir,
-                 teacher=None, soft_weight=0.5, tri_soft_weight=0.0):
+                 teacher=None, soft_weight=0.5, tri_soft_weight=0.0, ins_hard_weight=0.0, ins_soft_weight=0.0, ins_tau=0.1,
+                 ins_teacher_tau=None):
         from grl_amd.reid.loss import SoftProxyMemoryLoss
         self._init_teacher('MeanTeacherCameraSEQTrainer', SoftProxyMemoryLoss, criterion_corr, criterion_uncorr, teacher,
-                           soft_weight, tri_soft_weight)
+                           soft_weight, tri_soft_weight, ins_hard_weight, ins_soft_weight, ins_tau, ins_teacher_tau)
         super(MeanTeacherCameraSEQTrainer, self).__init__(cnn_model, siamese_model, siamese_model_uncorr, criterion_veri,
                                                           criterion_corr, criterion_uncorr, logdir)
-        self._set_teacher(teacher, soft_weight, tri_soft_weight)
+        self._set_teacher(teacher, soft_weight, tri_soft_weight, ins_hard_weight, ins_soft_weight, ins_tau, ins_teacher_tau)
 
     def _id_extra(self, rows):
         return {'cams': self._cam_rows[rows]}

@@ -792,6 +792,37 @@ int grl_soft_triplet_fwd(const float* feat, const float* tfeat, const int64_t* i
                          float* loss, float* dist, int32_t* sel, float* z, float* q, void* stream);
 int grl_soft_triplet_bwd(const float* feat, const float* dist, const int32_t* sel, const float* z, const float* q,
                          const float* dloss, float w_soft, float* dfeat, int n, int D, void* stream);
+/* Hard instance contrast and soft instance consistency against a mean teacher (ins_contrast.hip, InstanceContrastLoss,
+ * DESIGN.md 4ao; the instance terms of ICE, Chen et al. 2021).  Additive: GRL_ABI_VERSION stays 10.
+ * feat [n][D] the student's rows, tfeat [n][D] the teacher's rows of the same samples (no gradient), ids [n] int64 of any value.
+ *   u_i = f_i / max(|f_i|, 1e-12),  v_j = m_j / max(|m_j|, 1e-12)   (F.normalize's clamp),  c_ij = <u_i, v_j>,  t_ij = <v_i, v_j>.
+ * Selection, per anchor i: one column per distinct id of the batch -- of the anchor's own id (i counts as a member) the member
+ * with the SMALLEST c_ij, the hard positive p_i; of every other id the member with the LARGEST c_ij; among equal values the lowest
+ * column index.  K_i is the selected set.  Over K_i, the row maximum subtracted in both softmaxes:
+ *   P = softmax(c_ik / tau),  Q = softmax(t_ik / tau_t)      (the teacher's similarities at the STUDENT's selection),
+ *   loss[i] = fl( fl(w_hard nl_p) + fl(w_soft sum_k fl(Q_k nl_k)) ),   nl_k = -log P_k = fl( logf(S) - fl(fl(c_ik / tau) - max) ),
+ *   coef[i][k] = g_ik = dloss_i / d(c_ik / tau) = fl( fl(w_hard fl(P_k - [k = p_i])) + fl(w_soft fl(P_k - Q_k)) ),
+ * with P_k = e_k / S, e_k = expf(fl(c_ik / tau) - max), S = sum_k e_k, and Q_k likewise from t and tau_t.  With w_soft = 0 t, Q
+ * and the w_soft terms are never computed.  A batch with one id gives loss = 0 and coef = 0 exactly.
+ * Outputs: loss [n]; cos [n][n] = c_ij; sel [n][n] int32 = 0 unselected / 1 a selected negative / 2 the hard positive;
+ * coef [n][n] = g_ik, 0 where unselected.
+ * Orders (no atomics, no fused multiply-add, the same bits every run): every dot product over D is one wave's -- lane l takes the
+ * float4 l + 64 t, adds its four products left to right and its trips in sequence from 0, then the wave64 xor tree (offsets 32 ..
+ * 1), the shape of the triplet kernels' distance -- and c_ij = fl(fl(<f_i, m_j> inv_f_i) inv_m_j) with inv = 1 / max(sqrtf(ss),
+ * 1e-12f); the inverse norms are recomputed by every workgroup, none is stored.  S, the teacher's sum and sum_k Q_k nl_k run over
+ * ascending column index.
+ * Backward, one 256-lane workgroup per row, every element of dfeat written by one lane:
+ *   w_k = fl(coef[i][k] inv_m_k),  gu = fl( (sum over ascending k with w_k != 0 of fl(m_k w_k)) fl(1 / tau) ),  u = fl(f_i inv_f_i),
+ *   dot = <u, gu> (lane l takes the float4 l + 256 t, four products left to right, trips in sequence, wave tree, the four waves
+ *   added in sequence),   dfeat[i] = fl( fl( fl(gu - fl(u dot)) inv_f_i ) dloss[i] );
+ * a row under the clamp (sqrtf(|f_i|^2) < 1e-12f, a zero row) gets dfeat[i] = 0.
+ * Limits, each refused with GRL_EINVAL before anything is launched: a NULL pointer, n < 1, n > 2048 (the forward keeps 6 n words
+ * of LDS: 48 KiB at the cap), D < 4, D % 4 != 0, tau or tau_t not > 0 or not finite, a negative or non-finite weight, both
+ * weights 0.  One launch each; LDS is touched with 32-bit accesses only. */
+int grl_ins_contrast_fwd(const float* feat, const float* tfeat, const int64_t* ids, int n, int D, float tau, float tau_t,
+                         float w_hard, float w_soft, float* loss, float* cos, int32_t* sel, float* coef, void* stream);
+int grl_ins_contrast_bwd(const float* feat, const float* tfeat, const float* coef, const float* dloss, float tau, float* dfeat,
+                         int n, int D, void* stream);
 /* prob[t] = softmax(scores[t][0..1])[1] (reid/train/trainer.py:146-148; prob0, optional, keeps the
  * class-0 probability for the backward) and its backward, term for term as torch's softmax backward */
 int grl_softmax2(const float* scores, float* prob, float* prob0, int64_t m, void* stream);
