@@ -849,6 +849,7 @@ extern "C" int grl_stem_conv7x7_u8(const uint8_t* x, const float* mean_std, cons
 static int stem_launch(const float* x, const float* norm, const float* w, const float* scale, const float* shift,
                        float* y, int n, int H, int W, int relu, const float* wp, void* stream) {
     GRL_REQUIRE(x && w && scale && shift && y && n > 0, "stem: null/empty");
+    GRL_REQUIRE(H > 0 && W > 0, "stem: H and W must be positive");
     GRL_REQUIRE(H % 2 == 0 && W % 2 == 0, "stem: H and W must be even");
     const int Ho = H / 2, Wo = W / 2;
     static const int use_valu = getenv("GRL_STEM_VALU") ? 1 : 0;     // kernel tuning only
@@ -1067,6 +1068,7 @@ extern "C" int grl_stem_pack_weight_pool(const float* w, float* wq, void* stream
 extern "C" int grl_stem_pool_f32(const void* x, int x_is_u8, const float* mean_std, const float* scale, const float* shift,
                                  float* y, int n, int H, int W, const float* wq, void* stream) {
     GRL_REQUIRE(x && scale && shift && y && wq && n > 0, "stem_pool_f32: null/empty");
+    GRL_REQUIRE(H > 0 && W > 0, "stem_pool_f32: H and W must be positive");      // (H == 0: strip_prows == 0, a division by zero below)
     GRL_REQUIRE(W == 2 * FP_TW && H % 4 == 0, "stem_pool_f32: needs W == 128 and H % 4 == 0");
     GRL_REQUIRE(!x_is_u8 || mean_std, "stem_pool_f32: u8 input needs mean_std");
     GRL_REQUIRE(((uintptr_t)x & 7) == 0 || x_is_u8, "stem_pool_f32: x must be 8-byte aligned");
@@ -1093,7 +1095,7 @@ extern "C" int grl_stem_pool_f32(const void* x, int x_is_u8, const float* mean_s
 }
 
 extern "C" int grl_maxpool3x3s2(const float* x, float* y, int n, int H, int W, int C, void* stream) {
-    GRL_REQUIRE(x && y && n > 0 && C % 4 == 0, "maxpool: bad args");
+    GRL_REQUIRE(x && y && n > 0 && H > 0 && W > 0 && C % 4 == 0, "maxpool: bad args");
     const int64_t total = (int64_t)n * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);
     hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, y, n, H, W, C);
     return grl_check_launch("grl_maxpool3x3s2");

@@ -355,6 +355,7 @@ extern "C" int grl_stem_conv7x7_u8_bf16(const uint8_t* x, const float* mean_std,
 static int stem_b16_launch(const float* x, const float* norm, const float* w, const float* scale,
                            const float* shift, void* y, int n, int H, int W, int relu, const void* wp, void* stream) {
     GRL_REQUIRE(x && w && scale && shift && y && n > 0, "stem_bf16: null/empty");
+    GRL_REQUIRE(H > 0 && W > 0, "stem_bf16: H and W must be positive");
     GRL_REQUIRE(H % 2 == 0 && W % 2 == 0, "stem_bf16: H and W must be even");
     const int Ho = H / 2, Wo = W / 2;
     const size_t lds = (size_t)(128 + 64) * SB_ROWB + (size_t)SB_PATCH * sizeof(__bf16);
@@ -718,6 +719,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool2_b16_kernel(
 extern "C" int grl_stem_pool_bf16(const void* x, int x_is_u8, const float* mean_std, const float* scale, const float* shift,
                                   void* y, int n, int H, int W, const void* wp, void* stream) {
     GRL_REQUIRE(x && scale && shift && y && wp && n > 0, "stem_pool_bf16: null/empty");
+    GRL_REQUIRE(H > 0 && W > 0, "stem_pool_bf16: H and W must be positive");     // (H == 0: strip_rows == 0, a division by zero below)
     GRL_REQUIRE(W == 2 * SP_TW && H % 4 == 0, "stem_pool_bf16: needs W == 128 and H % 4 == 0");
     GRL_REQUIRE(!x_is_u8 || mean_std, "stem_pool_bf16: u8 input needs mean_std");
     GRL_REQUIRE(!x_is_u8 || ((uintptr_t)x & 1) == 0, "stem_pool_bf16: u8 input must be 2-byte aligned (2-byte row loads)");
@@ -750,7 +752,7 @@ extern "C" int grl_stem_pool_bf16(const void* x, int x_is_u8, const float* mean_
 }
 
 extern "C" int grl_maxpool3x3s2_bf16(const void* x, void* y, int n, int H, int W, int C, void* stream) {
-    GRL_REQUIRE(x && y && n > 0 && C % 8 == 0, "maxpool_bf16: bad args");
+    GRL_REQUIRE(x && y && n > 0 && H > 0 && W > 0 && C % 8 == 0, "maxpool_bf16: bad args");
     const int64_t total = (int64_t)n * ((H + 1) / 2) * ((W + 1) / 2) * (C / 8);
     hipLaunchKernelGGL(maxpool_b16_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, CB16(x), B16(y),
                        n, H, W, C);

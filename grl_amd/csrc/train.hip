@@ -1851,7 +1851,7 @@ extern "C" int grl_dilate2(const float* dz, float* up, int n, int Ho, int Wo, in
 
 extern "C" int grl_maxpool3x3s2_bwd(const float* x, const float* dy, float* dx, int n, int H, int W, int C,
                                     void* stream) {
-    GRL_REQUIRE(x && dy && dx && n > 0 && C % 4 == 0, "maxpool_bwd: bad args");
+    GRL_REQUIRE(x && dy && dx && n > 0 && H > 0 && W > 0 && C % 4 == 0, "maxpool_bwd: bad args");
     const int64_t total4 = (int64_t)n * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);      // 2x2 input blocks
     hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_even(total4)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, H, W,
                        C / 4, total4);
@@ -1860,7 +1860,8 @@ extern "C" int grl_maxpool3x3s2_bwd(const float* x, const float* dy, float* dx, 
 
 extern "C" int grl_bn_relu_maxpool3x3s2(const float* z, const float* mean, const float* scale, const float* beta, float* y,
                                         uint8_t* idx, int n, int H, int W, int C, void* stream) {
-    GRL_REQUIRE(z && mean && scale && y && idx && n > 0 && C % 4 == 0 && ((uintptr_t)idx & 3) == 0, "bn_relu_maxpool: bad args");
+    GRL_REQUIRE(z && mean && scale && y && idx && n > 0 && H > 0 && W > 0 && C % 4 == 0 && ((uintptr_t)idx & 3) == 0,
+                "bn_relu_maxpool: bad args");
     const int64_t total = (int64_t)n * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);
     hipLaunchKernelGGL(bn_relu_maxpool_kernel, dim3(grid_even(total)), dim3(256), 0, (hipStream_t)stream, z, mean, scale, beta,
                        y, idx, n, H, W, C);
@@ -1869,7 +1870,8 @@ extern "C" int grl_bn_relu_maxpool3x3s2(const float* z, const float* mean, const
 
 extern "C" int grl_maxpool3x3s2_bwd_idx(const uint8_t* idx, const float* dy, float* dx, int n, int H, int W, int C,
                                         void* stream) {
-    GRL_REQUIRE(idx && dy && dx && n > 0 && C % 4 == 0 && ((uintptr_t)idx & 3) == 0, "maxpool_bwd_idx: bad args");
+    GRL_REQUIRE(idx && dy && dx && n > 0 && H > 0 && W > 0 && C % 4 == 0 && ((uintptr_t)idx & 3) == 0,
+                "maxpool_bwd_idx: bad args");
     const int64_t total4 = (int64_t)n * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);      // 2x2 input blocks
     hipLaunchKernelGGL(maxpool_bwd_idx_kernel, dim3(grid_even(total4)), dim3(256), 0, (hipStream_t)stream, idx, dy, dx, H, W,
                        C / 4, total4);
@@ -1877,7 +1879,7 @@ extern "C" int grl_maxpool3x3s2_bwd_idx(const uint8_t* idx, const float* dy, flo
 }
 
 extern "C" int grl_stem_im2col(const float* x, float* col, int n, int H, int W, int Kp, void* stream) {
-    GRL_REQUIRE(x && col && n > 0 && Kp >= 147 && Kp % 32 == 0, "stem_im2col: bad args");
+    GRL_REQUIRE(x && col && n > 0 && H > 0 && W > 0 && Kp >= 147 && Kp % 32 == 0, "stem_im2col: bad args");
     const int64_t total = (int64_t)n * (H / 2) * (W / 2) * Kp;
     hipLaunchKernelGGL(stem_im2col_kernel, dim3(grid_even(total)), dim3(256), 0, (hipStream_t)stream, x, col, H, W, Kp,
                        total);

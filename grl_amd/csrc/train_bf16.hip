@@ -657,7 +657,7 @@ extern "C" int grl_dilate2_bf16(const void* dz, void* up, int n, int Ho, int Wo,
 }
 
 extern "C" int grl_maxpool3x3s2_bwd_bf16(const void* x, const void* dy, void* dx, int n, int H, int W, int C, void* stream) {
-    GRL_REQUIRE(x && dy && dx && n > 0 && C % 8 == 0 && H < 32768 && W < 32768, "maxpool_bwd_bf16: bad args");
+    GRL_REQUIRE(x && dy && dx && n > 0 && H > 0 && W > 0 && C % 8 == 0 && H < 32768 && W < 32768, "maxpool_bwd_bf16: bad args");
     const int64_t total8 = (int64_t)n * ((H + 1) / 2) * ((W + 1) / 2) * (C / 8);
     hipLaunchKernelGGL(maxpool_bwd_b16_kernel, dim3(grid_for(total8)), dim3(256), 0, (hipStream_t)stream, CB16(x), CB16(dy),
                        B16(dx), H, W, C / 8, total8);
@@ -666,7 +666,8 @@ extern "C" int grl_maxpool3x3s2_bwd_bf16(const void* x, const void* dy, void* dx
 
 extern "C" int grl_bn_relu_maxpool3x3s2_bf16(const void* z, const float* mean, const float* scale, const float* beta, void* y,
                                              uint8_t* idx, int n, int H, int W, int C, void* stream) {
-    GRL_REQUIRE(z && mean && scale && y && idx && n > 0 && C % 8 == 0 && al16(z) && al16(y) && ((uintptr_t)idx & 7) == 0,
+    GRL_REQUIRE(z && mean && scale && y && idx && n > 0 && H > 0 && W > 0 && C % 8 == 0 && al16(z) && al16(y) &&
+                    ((uintptr_t)idx & 7) == 0,
                 "bn_relu_maxpool_bf16: bad args");
     const int64_t total = (int64_t)n * ((H + 1) / 2) * ((W + 1) / 2) * (C / 8);
     hipLaunchKernelGGL(bn_relu_maxpool_b16_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, CB16(z), mean, scale,
@@ -676,7 +677,7 @@ extern "C" int grl_bn_relu_maxpool3x3s2_bf16(const void* z, const float* mean, c
 
 extern "C" int grl_maxpool3x3s2_bwd_idx_bf16(const uint8_t* idx, const void* dy, void* dx, int n, int H, int W, int C,
                                              void* stream) {
-    GRL_REQUIRE(idx && dy && dx && n > 0 && C % 8 == 0 && al16(dy) && al16(dx) && ((uintptr_t)idx & 7) == 0,
+    GRL_REQUIRE(idx && dy && dx && n > 0 && H > 0 && W > 0 && C % 8 == 0 && al16(dy) && al16(dx) && ((uintptr_t)idx & 7) == 0,
                 "maxpool_bwd_idx_bf16: bad args");
     const int64_t total8 = (int64_t)n * ((H + 1) / 2) * ((W + 1) / 2) * (C / 8);
     hipLaunchKernelGGL(maxpool_bwd_idx_b16_kernel, dim3(grid_for(total8)), dim3(256), 0, (hipStream_t)stream, idx, CB16(dy),
@@ -685,7 +686,7 @@ extern "C" int grl_maxpool3x3s2_bwd_idx_bf16(const uint8_t* idx, const void* dy,
 }
 
 extern "C" int grl_stem_im2col_bf16(const float* x, void* col, int n, int H, int W, int Kp, void* stream) {
-    GRL_REQUIRE(x && col && n > 0 && Kp >= 147 && Kp % 32 == 0, "stem_im2col_bf16: bad args");
+    GRL_REQUIRE(x && col && n > 0 && H > 0 && W > 0 && Kp >= 147 && Kp % 32 == 0, "stem_im2col_bf16: bad args");
     const int64_t total8 = (int64_t)n * (H / 2) * (W / 2) * (Kp / 8);
     hipLaunchKernelGGL(stem_im2col_b16_kernel, dim3(grid_for(total8)), dim3(256), 0, (hipStream_t)stream, x, B16(col), H, W,
                        Kp, total8);

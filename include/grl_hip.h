@@ -224,7 +224,9 @@ int grl_bn_fold(const float* gamma, const float* beta, const float* mean, const 
                 const float* bias, float eps, float* scale, float* shift, int C, void* stream);
 
 /* Stem: 7x7 stride-2 pad-3 conv on NCHW input [n][3][H][W], y = relu?(conv*scale+shift) ->
- * channels-last [n][H/2][W/2][64]   (resnets1.py:101-103 / basebranch.py:28-30). */
+ * channels-last [n][H/2][W/2][64]   (resnets1.py:101-103 / basebranch.py:28-30).
+ * Every launcher of the stem / max-pool family (the stems, grl_stem_pool_*, grl_maxpool3x3s2*, grl_bn_relu_maxpool3x3s2*,
+ * grl_stem_im2col*) returns GRL_EINVAL before anything is launched for n <= 0, H <= 0 or W <= 0. */
 int grl_stem_conv7x7(const float* x, const float* w /*[64][3][7][7]*/, const float* scale,
                      const float* shift, float* y, int n, int H, int W, int relu,
                      const float* wp /* optional: [64][164] image from grl_stem_pack_weight */,
