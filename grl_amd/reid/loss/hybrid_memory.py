@@ -6,12 +6,9 @@ the epoch.  A class's logit is the mean of its members' scaled similarities.
 The memory and its three tables are what ``PseudoLabels.hybrid()`` gives each epoch (``HybridLabels.memory``,
 ``class_ptr_dev``, ``class_members_dev``, ``inst_class_dev``); the targets are the class ids, ``index`` the rows' memory rows.
 
-forward : logits = x . memory^T / temp -- the K-blocked fp32 GEMM with the scale in its epilogue, as OIMLoss -- then ONE
-          `grl_hybrid_ce` call: loss, dlogits and the top-1 count over the classes.
-backward: `grl_oim_grad` on the saved dlogits against the memory AS IT IS WHEN THE BACKWARD RUNS (more than 5120 memory rows:
-          one call per block of 5120 columns, the blocks' results added by `grl_axpby` in block order), then `grl_oim_update`
-          over ``dist.gather_rank_order(x, index)`` with the INSTANCE index as the label: every sample, in batch order,
-          mem[index] = m mem[index] + (1 - m) x, renormalised.  An index outside [0, N) updates nothing.
+The logits GEMM, the input gradient and the update are the memory front end's (``grl_amd.reid.loss.memory``); between them
+stands ONE `grl_hybrid_ce` call -- loss, dlogits and the top-1 count over the classes -- or, against a mean teacher's rows,
+`grl_soft_hybrid_ce` (``SoftHybridMemoryLoss``).  The update is the 'instance' rule with the INSTANCE index as the label.
 
 No torch op computes here and nothing syncs with the host; there is no CPU path.  (A ``num_features`` that is no multiple
 of 32, the K the logits GEMM takes, costs zero-padded copies of the inputs and the memory per forward: keep it a multiple.)"""
@@ -21,11 +18,11 @@ import numpy as np
 import torch
 from torch import nn, autograd
 
-from grl_amd._lib import ptr, require_device, MATH_F32
-from grl_amd.reid.loss.oim import _call, _labels
+from grl_amd._lib import ptr, require_device
+from grl_amd.reid.loss import memory
+from grl_amd.reid.loss.memory import _labels, check_memory, check_table, check_devices
 
 MAX_CLASSES = 15360             # GRL_HYBRID_MAX_CLASSES of include/grl_hip.h: the class logits of a row live in LDS
-OG_MAX_COLS = 5120              # grl_oim_grad's limit: its 8 gradient rows live in LDS (160 KB)
 
 
 def check_partition(class_ptr, class_members, inst_class):
@@ -49,58 +46,43 @@ def check_partition(class_ptr, class_members, inst_class):
         raise ValueError('hybrid class tables: inst_class is not the inverse of class_ptr / class_members')
 
 
+def hybrid_ce(ctx, inputs, targets, index, mem, class_ptr, class_members, inst_class, momentum, scalar, teacher=None, w=0.0):
+    """A Function's forward: (loss, scaled logits, correct) = grl_hybrid_ce(x . mem^T * scalar, targets, the class tables); with
+    ``teacher`` rows, grl_soft_hybrid_ce against (1 - w) the target + w the softmax of the teacher's class logits."""
+    require_device(inputs, 'HybridMemory inputs')
+    require_device(mem, 'HybridMemory memory')
+    x = inputs.contiguous()
+    y, idx = _labels(targets, x.device), _labels(index, x.device)
+    n = x.size(0)
+    if y.numel() != n or idx.numel() != n:
+        raise ValueError('%sHybridMemoryLoss: %d targets and %d indices for %d rows' % (
+            '' if teacher is None else 'Soft', y.numel(), idx.numel(), n))
+    N, nc = mem.size(0), class_ptr.size(0) - 1
+    both, logits = memory.scaled_logits(x, mem, scalar, teacher)
+    # (ws: rows [3][n]; with a teacher, then its class logits [n][C])
+    loss, correct, dlogits, ws = memory.ce_outputs(logits, 3 * n + (0 if teacher is None else n * nc))
+    if teacher is None:
+        memory._call('grl_hybrid_ce', ptr(logits), N, ptr(y), ptr(class_ptr), ptr(class_members), ptr(inst_class), n, N, nc,
+                     ptr(loss), ptr(correct), ptr(dlogits), N, ptr(ws))
+    else:
+        memory._call('grl_soft_hybrid_ce', ptr(both), N, both.data_ptr() + 4 * n * N, N, ptr(y), ptr(class_ptr),
+                     ptr(class_members), ptr(inst_class), C.c_float(w), n, N, nc, ptr(loss), ptr(correct), ptr(dlogits), N,
+                     ptr(ws))
+    memory.save(ctx, x, idx, dlogits, mem, momentum, scalar, 'instance')
+    ctx.mark_non_differentiable(logits, correct)
+    return loss, logits, correct
+
+
 class HybridMemory(autograd.Function):
-    """(loss, scaled logits, correct) = grl_hybrid_ce(x . mem^T * scalar, targets, the class tables); the backward updates
-    the memory rows ``index``."""
+    """(loss, scaled logits, correct) = ``hybrid_ce``; the backward updates the memory rows ``index``."""
 
     @staticmethod
     def forward(ctx, inputs, targets, index, mem, class_ptr, class_members, inst_class, momentum, scalar):
-        from grl_amd import engine
-        require_device(inputs, 'HybridMemory inputs')
-        require_device(mem, 'HybridMemory memory')
-        x = inputs.contiguous()
-        y, idx = _labels(targets, x.device), _labels(index, x.device)
-        n, D = x.shape
-        if y.numel() != n or idx.numel() != n:
-            raise ValueError('HybridMemoryLoss: %d targets and %d indices for %d rows' % (y.numel(), idx.numel(), n))
-        N, nc = mem.size(0), class_ptr.size(0) - 1
-        scale = torch.full((N,), float(scalar), dtype=torch.float32, device=x.device)
-        logits = torch.empty((n, N), dtype=torch.float32, device=x.device)
-        xk, mk = engine._pad_features(x), engine._pad_features(mem)        # (D % 32 != 0: zero columns for the GEMM, as the engine pads)
-        engine.gemm(xk, mk, logits, n, N, xk.size(1), scale=scale, math=MATH_F32, kblock=True)
-        loss = torch.empty((), dtype=torch.float32, device=x.device)
-        correct = torch.empty((), dtype=torch.float32, device=x.device)
-        dlogits = torch.empty_like(logits)
-        ws = torch.empty(3 * n, dtype=torch.float32, device=x.device)
-        _call('grl_hybrid_ce', ptr(logits), N, ptr(y), ptr(class_ptr), ptr(class_members), ptr(inst_class), n, N, nc,
-              ptr(loss), ptr(correct), ptr(dlogits), N, ptr(ws))
-        ctx.save_for_backward(x, idx, dlogits)
-        ctx.mem, ctx.momentum, ctx.scalar = mem, momentum, float(scalar)
-        ctx.mark_non_differentiable(logits, correct)
-        return loss, logits, correct
+        return hybrid_ce(ctx, inputs, targets, index, mem, class_ptr, class_members, inst_class, momentum, scalar)
 
     @staticmethod
     def backward(ctx, gloss, _glogits, _gcorrect):
-        x, idx, dlogits = ctx.saved_tensors
-        mem, m = ctx.mem, ctx.momentum
-        n, D = x.shape
-        N = mem.size(0)
-        grad_inputs = None
-        if ctx.needs_input_grad[0]:
-            g = gloss.contiguous().float()
-            grad_inputs = torch.empty_like(x)
-            # N <= 5120: one call, as ClusterMemoryLoss.  A larger memory (MARS: 8298 tracklets) goes through grl_oim_grad in
-            # column blocks of 5120 -- dlogits and the memory offset by the block, ldd = N -- added up by grl_axpby in block order
-            part = torch.empty_like(x) if N > OG_MAX_COLS else None
-            for j0 in range(0, N, OG_MAX_COLS):
-                _call('grl_oim_grad', dlogits.data_ptr() + 4 * j0, N, mem.data_ptr() + 4 * j0 * D, ptr(g), C.c_float(ctx.scalar),
-                      ptr(part if j0 else grad_inputs), n, min(OG_MAX_COLS, N - j0), D)
-                if j0:
-                    _call('grl_axpby', ptr(grad_inputs), ptr(part), ptr(grad_inputs), C.c_float(1.0), C.c_float(1.0), n * D)
-        from grl_amd import dist as grl_dist
-        xs, idxs = grl_dist.gather_rank_order(x, idx)
-        _call('grl_oim_update', ptr(mem), ptr(xs), ptr(idxs), xs.size(0), D, N, C.c_float(m))
-        return (grad_inputs,) + (None,) * 8
+        return (memory.backward(ctx, gloss),) + (None,) * 8
 
 
 class HybridMemoryLoss(nn.Module):
@@ -134,17 +116,10 @@ class HybridMemoryLoss(nn.Module):
         tables ``class_ptr`` [C + 1], ``class_members`` [N], ``inst_class`` [N] (int32, on the same device).  The tables are
         checked once, on a host copy: a partition of 0 .. N - 1 into C <= GRL_HYBRID_MAX_CLASSES non-empty classes with
         ascending members.  The memory tensor itself becomes the buffer: the backward updates it in place."""
-        if not (torch.is_tensor(memory) and memory.dtype == torch.float32):
-            raise ValueError('HybridMemoryLoss.reset: memory must be a float32 tensor (got %s)' % (
-                memory.dtype if torch.is_tensor(memory) else type(memory).__name__))
-        if memory.dim() != 2 or memory.size(0) < 1 or memory.size(1) != self.num_features:
-            raise ValueError('HybridMemoryLoss.reset: memory must be [N >= 1, num_features = %d] (got %s)' % (
-                self.num_features, tuple(memory.shape)))
+        check_memory('HybridMemoryLoss.reset', 'memory', 'N', memory, self.num_features)
         tables = (('class_ptr', class_ptr), ('class_members', class_members), ('inst_class', inst_class))
         for name, t in tables:
-            if not (torch.is_tensor(t) and t.dtype == torch.int32):
-                raise ValueError('HybridMemoryLoss.reset: %s must be an int32 tensor (got %s)' % (
-                    name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+            check_table('HybridMemoryLoss.reset', name, t)
             if t.dim() != 1:
                 raise ValueError('HybridMemoryLoss.reset: %s must be 1-d (got %s)' % (name, tuple(t.shape)))
         N = memory.size(0)
@@ -159,12 +134,7 @@ class HybridMemoryLoss(nn.Module):
             check_partition(class_ptr.cpu().numpy(), class_members.cpu().numpy(), inst_class.cpu().numpy())
         except ValueError as e:
             raise ValueError('HybridMemoryLoss.reset: %s' % e)
-        if not memory.is_cuda:
-            raise ValueError('HybridMemoryLoss.reset: memory must be on a HIP device (got %s)' % memory.device)
-        for name, t in tables:
-            if t.device != memory.device:
-                raise ValueError('HybridMemoryLoss.reset: %s must be on the device of the memory, %s (got %s)' % (
-                    name, memory.device, t.device))
+        check_devices('HybridMemoryLoss.reset', 'memory', memory, tables)
         self.memory = memory.detach().contiguous()
         self.class_ptr = class_ptr.detach().contiguous()
         self.class_members = class_members.detach().contiguous()
@@ -172,7 +142,5 @@ class HybridMemoryLoss(nn.Module):
         return self
 
     def forward(self, inputs, targets, index):
-        loss, logits, correct = HybridMemory.apply(inputs, targets, index, self.memory, self.class_ptr, self.class_members,
-                                                   self.inst_class, self.momentum, 1.0 / self.temp)
-        logits.grl_top1 = (correct, logits.size(0))
-        return loss, logits
+        return memory.top1(HybridMemory.apply(inputs, targets, index, self.memory, self.class_ptr, self.class_members,
+                                              self.inst_class, self.momentum, 1.0 / self.temp))

@@ -18,7 +18,7 @@ from torch import autograd
 
 from grl_amd._lib import ptr, require_device
 from grl_amd.reid.loss.oim import _call, _labels
-from grl_amd.reid.loss.soft_memory import check_teacher
+from grl_amd.reid.loss.memory import check_teacher
 from grl_amd.reid.loss.triplet import _BatchHard
 
 

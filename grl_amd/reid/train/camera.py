@@ -1,6 +1,6 @@
 """SEQTrainer that carries every row's camera id to its identity criteria: what ``ProxyMemoryLoss`` needs and
 ``SEQTrainer`` drops.  The step is SEQTrainer's own -- the same forward, losses and launches; only ``_parse_data`` keeps
-``inputs[2]`` and ``_id_loss`` passes ``cams=`` in the row order of the targets it is given."""
+``inputs[2]`` and ``_id_extra`` adds ``cams=`` in the row order of the targets it is given."""
 import torch
 
 from grl_amd import dist as grl_dist
@@ -26,5 +26,5 @@ class CameraSEQTrainer(SEQTrainer):
                           'frame': cams.unsqueeze(1).expand(b, seq_len).reshape(-1)}
         return super(CameraSEQTrainer, self)._parse_data(inputs)
 
-    def _id_loss(self, criterion, feats, targets, rows):
-        return criterion(feats, targets, cams=self._cam_rows[rows])
+    def _id_extra(self, rows):
+        return {'cams': self._cam_rows[rows]}

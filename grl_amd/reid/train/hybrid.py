@@ -1,7 +1,7 @@
 """SEQTrainer that carries every row's instance index -- its row of the hybrid memory -- to its identity criteria (DESIGN.md
 4ak): what ``HybridMemoryLoss`` needs and ``SEQTrainer`` has no place for.  The step is SEQTrainer's own -- the same forward,
 losses and launches; ``_parse_data`` takes the batch's LAST element (``RawVideoDataset(index=True)``) off before the base
-sees the batch, and ``_id_loss`` passes ``index=`` in the row order of the targets it is given."""
+sees the batch, and ``_id_extra`` adds ``index=`` in the row order of the targets it is given."""
 import torch
 
 from grl_amd import dist as grl_dist
@@ -31,5 +31,5 @@ class HybridSEQTrainer(SEQTrainer):
                             'frame': index.unsqueeze(1).expand(b, seq_len).reshape(-1)}
         return super(HybridSEQTrainer, self)._parse_data(tuple(inputs[:-1]))
 
-    def _id_loss(self, criterion, feats, targets, rows):
-        return criterion(feats, targets, index=self._index_rows[rows])
+    def _id_extra(self, rows):
+        return {'index': self._index_rows[rows]}

@@ -16,6 +16,9 @@ import torch
 
 from grl_amd import dist as grl_dist
 from grl_amd._lib import ptr, GrlEmaEntry, EMA_CHUNK
+from grl_amd.reid.loss import (SoftClusterMemoryLoss, SoftHybridMemoryLoss, SoftProxyMemoryLoss, SoftTripletLoss,
+                               InstanceContrastLoss)
+from grl_amd.reid.loss.ins_contrast import check_ins_weights, check_temperature
 from grl_amd.reid.loss.oim import _call
 from grl_amd.reid.train.camera import CameraSEQTrainer
 from grl_amd.reid.train.hybrid import HybridSEQTrainer
@@ -194,10 +197,14 @@ class MeanTeacherMixin(object):
     ins_hard_weight = 0.0
     ins_soft_weight = 0.0
 
-    def _init_teacher(self, who, soft_class, criterion_corr, criterion_uncorr, teacher, soft_weight, tri_soft_weight,
-                      ins_hard_weight=0.0, ins_soft_weight=0.0, ins_tau=0.1, ins_teacher_tau=None):
-        """The constructor's checks, each a ValueError naming the argument, before anything is stored."""
-        from grl_amd.reid.loss.ins_contrast import check_ins_weights, check_temperature
+    soft_class = None               # the criterion class both identity criteria must be; a trainer sets it
+
+    def __init__(self, cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr, criterion_uncorr, logdir,
+                 teacher=None, soft_weight=0.5, tri_soft_weight=0.0, ins_hard_weight=0.0, ins_soft_weight=0.0, ins_tau=0.1,
+                 ins_teacher_tau=None):
+        """The base trainer's constructor behind the checks, each a ValueError naming the trainer and the argument, before
+        anything is stored."""
+        who, soft_class = type(self).__name__, self.soft_class
         for name, crit in (('criterion_corr', criterion_corr), ('criterion_uncorr', criterion_uncorr)):
             if not isinstance(crit, soft_class):
                 raise ValueError('%s: %s must be a %s (got %s)' % (who, name, soft_class.__name__, type(crit).__name__))
@@ -215,10 +222,8 @@ class MeanTeacherMixin(object):
         check_temperature('ins_tau', ins_tau, who=who)
         if ins_teacher_tau is not None:
             check_temperature('ins_teacher_tau', ins_teacher_tau, who=who)
-
-    def _set_teacher(self, teacher, soft_weight, tri_soft_weight, ins_hard_weight=0.0, ins_soft_weight=0.0, ins_tau=0.1,
-                     ins_teacher_tau=None):
-        from grl_amd.reid.loss import SoftTripletLoss, InstanceContrastLoss
+        super(MeanTeacherMixin, self).__init__(cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr,
+                                               criterion_uncorr, logdir)
         self.teacher = teacher
         self.soft_weight = float(soft_weight)
         self.tri_soft_weight = float(tri_soft_weight)
@@ -227,10 +232,6 @@ class MeanTeacherMixin(object):
         self.ins_soft_weight = float(ins_soft_weight)
         self.criterion_ins = InstanceContrastLoss(tau=ins_tau, teacher_tau=ins_teacher_tau)
         self._teacher_rows = None
-
-    def _id_extra(self, rows):
-        """What the base trainer hands its identity criteria besides the targets, as keyword arguments."""
-        return {}
 
     def _forward(self, inputs, targets, i, epoch):
         """The teacher's rows first, on the launch stream and BEFORE the base forks its side stream, which reads them (the
@@ -276,51 +277,21 @@ class MeanTeacherSEQTrainer(MeanTeacherMixin, SEQTrainer):
     ``ins_teacher_tau``; None: ``ins_tau``) an owned ``InstanceContrastLoss`` on the same rows is added to it.
     ``train`` updates the teacher behind every optimizer step."""
 
-    def __init__(self, cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr, criterion_uncorr, logdir,
-                 teacher=None, soft_weight=0.5, tri_soft_weight=0.0, ins_hard_weight=0.0, ins_soft_weight=0.0, ins_tau=0.1,
-                 ins_teacher_tau=None):
-        from grl_amd.reid.loss import SoftClusterMemoryLoss
-        self._init_teacher('MeanTeacherSEQTrainer', SoftClusterMemoryLoss, criterion_corr, criterion_uncorr, teacher,
-                           soft_weight, tri_soft_weight, ins_hard_weight, ins_soft_weight, ins_tau, ins_teacher_tau)
-        super(MeanTeacherSEQTrainer, self).__init__(cnn_model, siamese_model, siamese_model_uncorr, criterion_veri,
-                                                    criterion_corr, criterion_uncorr, logdir)
-        self._set_teacher(teacher, soft_weight, tri_soft_weight, ins_hard_weight, ins_soft_weight, ins_tau, ins_teacher_tau)
+    soft_class = SoftClusterMemoryLoss
 
 
 class MeanTeacherHybridSEQTrainer(MeanTeacherMixin, HybridSEQTrainer):
-    """``HybridSEQTrainer`` with a mean teacher (DESIGN.md 4an): ``MeanTeacherSEQTrainer``'s three extra arguments;
+    """``HybridSEQTrainer`` with a mean teacher (DESIGN.md 4an): ``MeanTeacherSEQTrainer``'s extra arguments;
     ``criterion_corr`` and ``criterion_uncorr`` are two ``SoftHybridMemoryLoss`` and are called as
     ``criterion(feats, targets, index=index, teacher=rows, soft_weight=soft_weight)``.  Batches carry their instance indices
     as ``HybridSEQTrainer``'s do."""
 
-    def __init__(self, cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr, criterion_uncorr, logdir,
-                 teacher=None, soft_weight=0.5, tri_soft_weight=0.0, ins_hard_weight=0.0, ins_soft_weight=0.0, ins_tau=0.1,
-                 ins_teacher_tau=None):
-        from grl_amd.reid.loss import SoftHybridMemoryLoss
-        self._init_teacher('MeanTeacherHybridSEQTrainer', SoftHybridMemoryLoss, criterion_corr, criterion_uncorr, teacher,
-                           soft_weight, tri_soft_weight, ins_hard_weight, ins_soft_weight, ins_tau, ins_teacher_tau)
-        super(MeanTeacherHybridSEQTrainer, self).__init__(cnn_model, siamese_model, siamese_model_uncorr, criterion_veri,
-                                                          criterion_corr, criterion_uncorr, logdir)
-        self._set_teacher(teacher, soft_weight, tri_soft_weight, ins_hard_weight, ins_soft_weight, ins_tau, ins_teacher_tau)
-
-    def _id_extra(self, rows):
-        return {'index': self._index_rows[rows]}
+    soft_class = SoftHybridMemoryLoss
 
 
 class MeanTeacherCameraSEQTrainer(MeanTeacherMixin, CameraSEQTrainer):
-    """``CameraSEQTrainer`` with a mean teacher (DESIGN.md 4an): ``MeanTeacherSEQTrainer``'s three extra arguments;
+    """``CameraSEQTrainer`` with a mean teacher (DESIGN.md 4an): ``MeanTeacherSEQTrainer``'s extra arguments;
     ``criterion_corr`` and ``criterion_uncorr`` are two ``SoftProxyMemoryLoss`` and are called as
     ``criterion(feats, targets, cams=cams, teacher=rows, soft_weight=soft_weight)``."""
 
-    def __init__(self, cnn_model, siamese_model, siamese_model_uncorr, criterion_veri, criterion_corr, criterion_uncorr, logdir,
-                 teacher=None, soft_weight=0.5, tri_soft_weight=0.0, ins_hard_weight=0.0, ins_soft_weight=0.0, ins_tau=0.1,
-                 ins_teacher_tau=None):
-        from grl_amd.reid.loss import SoftProxyMemoryLoss
-        self._init_teacher('MeanTeacherCameraSEQTrainer', SoftProxyMemoryLoss, criterion_corr, criterion_uncorr, teacher,
-                           soft_weight, tri_soft_weight, ins_hard_weight, ins_soft_weight, ins_tau, ins_teacher_tau)
-        super(MeanTeacherCameraSEQTrainer, self).__init__(cnn_model, siamese_model, siamese_model_uncorr, criterion_veri,
-                                                          criterion_corr, criterion_uncorr, logdir)
-        self._set_teacher(teacher, soft_weight, tri_soft_weight, ins_hard_weight, ins_soft_weight, ins_tau, ins_teacher_tau)
-
-    def _id_extra(self, rows):
-        return {'cams': self._cam_rows[rows]}
+    soft_class = SoftProxyMemoryLoss

@@ -252,9 +252,13 @@ class SEQTrainer(BaseTrainer):
 
     def _id_loss(self, criterion, feats, targets, rows):
         """One identity criterion of ``_forward``; ``rows`` says which rows ``targets`` label: 'frame' (the batch's targets
-        expanded over T) or 'clip' (probe-then-gallery).  A subclass overrides it to hand a criterion more than the targets
-        (``CameraSEQTrainer``: the rows' cameras)."""
-        return criterion(feats, targets)
+        expanded over T) or 'clip' (probe-then-gallery)."""
+        return criterion(feats, targets, **self._id_extra(rows))
+
+    def _id_extra(self, rows):
+        """What an identity criterion is handed besides the targets, as keyword arguments in the row order ``rows``.  A
+        subclass overrides it (``CameraSEQTrainer``: the rows' cameras)."""
+        return {}
 
     def _tri_loss(self, feats, target):
         """The batch-hard triplet term of ``_forward`` on the correlated branch's clip rows (``criterion_triplet``, read when

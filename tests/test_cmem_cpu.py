@@ -237,13 +237,14 @@ class _Stub(object):
 
 def test_refusals_fire_before_any_device_call(monkeypatch):
     from grl_amd import engine
-    from grl_amd.reid.loss import ClusterMemoryLoss
+    from grl_amd.reid.loss import ClusterMemoryLoss, memory
     from grl_amd.reid.train import pseudo
 
     def no_device(*a, **k):
         raise AssertionError('a device call was made')
     for name in ('_call', 'gemm', 'cluster', 'cluster_jaccard', 'hdbscan', 'kmeans', 'cluster_centroids'):
         monkeypatch.setattr(engine, name, no_device)
+    monkeypatch.setattr(memory, '_call', no_device)
     xf = torch.zeros((8, 16))
     with pytest.raises(ValueError, match="method must be one of 'jaccard', 'cosine', 'hdbscan', 'kmeans' .got 'dbscan'"):
         pseudo.pseudo_labels(xf, method='dbscan')

@@ -335,14 +335,14 @@ def test_hybrid_seqtrainer_refuses_a_batch_without_its_index(monkeypatch):
 def test_refusals_fire_before_any_device_call(monkeypatch):
     from grl_amd import engine
     from grl_amd.reid.loss import HybridMemoryLoss, ClusterMemoryLoss
-    from grl_amd.reid.loss import hybrid_memory
+    from grl_amd.reid.loss import memory
     from grl_amd.reid.train import pseudo, SEQTrainer, HybridSEQTrainer
 
     def no_device(*a, **k):
         raise AssertionError('a device call was made')
     for name in ('_call', 'gemm', 'cluster_centroids', 'cluster_jaccard', 'cluster'):
         monkeypatch.setattr(engine, name, no_device)
-    monkeypatch.setattr(hybrid_memory, '_call', no_device)
+    monkeypatch.setattr(memory, '_call', no_device)
     with pytest.raises(ValueError, match='temp must be > 0'):
         HybridMemoryLoss(16, temp=0.0)
     crit = HybridMemoryLoss(16)

@@ -155,8 +155,9 @@ def _no_device(*a, **k):
 
 
 def test_module_refusals_fire_before_any_device_call(monkeypatch):
-    from grl_amd.reid.loss import InstanceContrastLoss, ins_contrast
+    from grl_amd.reid.loss import InstanceContrastLoss, ins_contrast, memory
     monkeypatch.setattr(ins_contrast, '_call', _no_device)
+    monkeypatch.setattr(memory, '_call', _no_device)
     crit = InstanceContrastLoss()
     assert crit.tau == 0.1 and crit.teacher_tau == 0.1
     assert InstanceContrastLoss(tau=0.05).teacher_tau == 0.05 and InstanceContrastLoss(0.05, 0.2).teacher_tau == 0.2

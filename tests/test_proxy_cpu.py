@@ -166,13 +166,14 @@ def test_proxy_labels_numbering_and_noise():
 
 def test_refusals_fire_before_any_device_call(monkeypatch):
     from grl_amd import engine
-    from grl_amd.reid.loss import ProxyMemoryLoss, ClusterMemoryLoss
+    from grl_amd.reid.loss import ProxyMemoryLoss, ClusterMemoryLoss, memory
     from grl_amd.reid.train import pseudo, SEQTrainer, CameraSEQTrainer
 
     def no_device(*a, **k):
         raise AssertionError('a device call was made')
     for name in ('_call', 'gemm', 'cluster_centroids', 'cluster_jaccard'):
         monkeypatch.setattr(engine, name, no_device)
+    monkeypatch.setattr(memory, '_call', no_device)
     with pytest.raises(ValueError, match="mode must be 'hard', 'mean' or 'instance' .got 'soft'"):
         ProxyMemoryLoss(16, mode='soft')
     with pytest.raises(ValueError, match='temp must be > 0'):

@@ -128,12 +128,12 @@ def test_the_sweeps_hold_what_the_kernels_can_get_wrong():
 # refusals, before any device call
 def _no_device(monkeypatch):
     from grl_amd import engine
-    from grl_amd.reid.loss import soft_memory, soft_hybrid_memory, soft_proxy_memory, hybrid_memory, proxy_memory
+    from grl_amd.reid.loss import memory
 
     def no_device(*a, **k):
         raise AssertionError('a device call was made')
-    for mod, name in ((engine, '_call'), (engine, 'gemm'), (soft_memory, '_call'), (soft_hybrid_memory, '_call'),
-                      (soft_proxy_memory, '_call'), (hybrid_memory, '_call'), (proxy_memory, '_call')):
+    # (the hard and soft memory criteria launch through memory._call and engine.gemm alone: they hold no _call of their own)
+    for mod, name in ((engine, '_call'), (engine, 'gemm'), (memory, '_call')):
         monkeypatch.setattr(mod, name, no_device)
 
 

@@ -198,12 +198,12 @@ def test_mean_teacher_refusals_fire_before_any_device_call(monkeypatch):
 
 def test_criterion_and_trainer_refusals_fire_before_any_device_call(monkeypatch):
     from grl_amd import engine, train_graph
-    from grl_amd.reid.loss import ClusterMemoryLoss, SoftClusterMemoryLoss, soft_memory
+    from grl_amd.reid.loss import ClusterMemoryLoss, SoftClusterMemoryLoss, memory
     from grl_amd.reid.train import MeanTeacher, MeanTeacherSEQTrainer
 
     def no_device(*a, **k):
         raise AssertionError('a device call was made')
-    for mod, name in ((engine, '_call'), (engine, 'gemm'), (soft_memory, '_call')):
+    for mod, name in ((engine, '_call'), (engine, 'gemm'), (memory, '_call')):
         monkeypatch.setattr(mod, name, no_device)
     assert issubclass(SoftClusterMemoryLoss, ClusterMemoryLoss)
     crit = SoftClusterMemoryLoss(16, 4, temp=0.05, momentum=0.2, mode='mean')
